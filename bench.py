@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """
-bench.py -- EI evaluations/second of the fused candidate sweep (+ GP-fit ms).
+bench.py -- EI evaluations/second of the fused candidate sweep (+ GP-fit ms with --full).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs W untimed and K timed steps and prints the line: `value`, `ms_per_step` (one
+timed step) and the roofline of the timed kernels.  --full adds what takes work of its own: GP-fit ms,
+the `configs` object and the CPU baseline (default config only).  --dump-outputs DIR writes what the
+last timed step returned (rank 0's view) as float64 DIR/<name>.npy; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 
 Both launch forms work.  Called plainly with --gpus N > 1 the script starts N fresh rank
 processes itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_PORT / IBO_COMM_ID_FILE in their
@@ -31,11 +37,11 @@ One JSON line on rank 0; `value` = all ranks' units * steps / max-over-ranks tim
 roofline: the sweep kernel is fp64-MFMA bound; algorithmic flops per evaluation
 F = N^2 + 3ND + 4N, achieved = F * M / mean kernel time measured with HIP
 events on the kernel's own stream inside the timed region.
-`configs` (default config only, after the timed region): the other halves of the metric on
+`configs` (--full, default config only, after the timed region): the other halves of the metric on
 the same clock -- GP-fit ms at N=1024/2048/4096, the C3 shard sweep and gallery-8, the C4
 preference GP (one GPU only) and the C5 grid, each with its own roofline block from SURVEY
 8(d)'s flop counts.
-cpu_baseline (rank 0, N=1 only): the reference's own compiled C++ (oracle/_ref/libego.so,
+cpu_baseline (--full, rank 0, N=1 only): the reference's own compiled C++ (oracle/_ref/libego.so,
 negei through acqmaxGP with every dimension fixed = exactly one evaluation per call) on a
 bounded sample of the same candidates; falls back to the plain-C port if _ref is absent.
 """
@@ -81,6 +87,15 @@ def roofline_mfma(flops, seconds, **extra):
            "traffic": None}
     out.update(extra)
     return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float64 .npy per array the last timed step returned"""
+    if path is None:
+        return
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.atleast_1d(np.asarray(a, dtype=np.float64)))
 
 
 def synth(seed, N, D):
@@ -400,6 +415,7 @@ def worker(args):
         GP, cand, host, start = c3_setup(C3_M_TOTAL)
         elapsed, outs = timed(lambda: c3_step(GP, cand, host, start), args.steps, args.warmup)
         if rank == 0:
+            dump_outputs(args.dump_outputs, {"best_value": outs[-1][0], "best_index": outs[-1][1]})
             kmean = float(np.mean([o[2] for o in outs])) * 1e-3
             out = dict(base)
             out.update({
@@ -420,6 +436,7 @@ def worker(args):
         X, Y, thetas = c5_setup()
         elapsed, outs = timed(lambda: c5_step(X, Y, thetas), args.steps, args.warmup)
         if rank == 0:
+            dump_outputs(args.dump_outputs, {"nlml_values": outs[-1][0], "nlml_argmin": outs[-1][1]})
             per_theta = elapsed / args.steps / C5_T            # each GPU does C5_T points per step
             out = dict(base)
             out.update({
@@ -441,7 +458,7 @@ def worker(args):
         X, Y = synth(2, N_OBS, DIM)
         GP = GaussianProcess(GaussianKernel_ard([.3] * DIM), X, Y, noise=.1, device=local_rank)
         fit_ms = []
-        for _ in range(5):                                  # GP-fit ms: host X,Y -> K, L, L^-1, alpha on device
+        for _ in range(5 if args.full else 0):              # GP-fit ms: host X,Y -> K, L, L^-1, alpha on device
             t0 = time.perf_counter()
             GP._fit_device()
             fit_ms.append((time.perf_counter() - t0) * 1e3)
@@ -464,6 +481,7 @@ def worker(args):
 
         elapsed, outs = timed(step, args.steps, args.warmup)
         if rank == 0:
+            dump_outputs(args.dump_outputs, {"best_value": outs[-1][0], "best_index": outs[-1][1]})
             total = float(M_PER_GPU) * world * args.steps
             fe = f_eval(N_OBS, DIM)
             kmean = float(np.mean([o[2] for o in outs])) * 1e-3
@@ -476,12 +494,13 @@ def worker(args):
                                        "2^20 candidates per GPU resident in HBM, arg-max to host each step",
                            "n_obs": N_OBS, "dim": DIM, "candidates_per_gpu": M_PER_GPU,
                            "parallelism": "candidate-sharded x%d, replicated GP, 1 RCCL arg-max exchange/step" % world},
-                "gp_fit_ms": {"host_to_ready_median": float(np.median(fit_ms)), "device_events": fit_dev_ms,
-                              "N": N_OBS, "D": DIM},
                 "best": {"value": outs[-1][0], "index": int(outs[-1][1])},
                 "roofline": roofline_mfma(fe * float(M_PER_GPU), kmean, kernel=outs[-1][3], kernel_ms=kmean * 1e3,
                                           flops_per_eval=fe, evals_per_launch=M_PER_GPU),
             })
+            if args.full:
+                out["gp_fit_ms"] = {"host_to_ready_median": float(np.median(fit_ms)), "device_events": fit_dev_ms,
+                                    "N": N_OBS, "D": DIM}
             j, src, sha = pmc_numbers()
             out["roofline"]["algorithmic_bytes_per_launch"] = (8 * DIM + 16) * M_PER_GPU
             out["roofline"]["kernel_source_sha"] = sha
@@ -492,7 +511,7 @@ def worker(args):
             else:
                 out["roofline"]["traffic_source"] = "no committed PMC summary matches this build of the kernel"
 
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             # ------------------------------------------------ the rest of the metric, on the same clock
             cfgs = {}
             # GP-fit ms (rank 0 is enough: the fit is single-GPU and replicated)
@@ -713,7 +732,7 @@ def worker(args):
                 del GPn, candn
             if rank == 0:
                 out["configs"] = cfgs
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(X, Y, cand_host)
 
     if rank == 0:
@@ -738,11 +757,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=("c2", "c3", "c5"), default="c2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the `configs` object (fit / C3 / C4 / C5 numbers)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure GP-fit ms, the `configs` object and the CPU baseline (default config only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the `configs` object (fit / C3 / C4 / C5 numbers)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     launched = "WORLD_SIZE" in os.environ or "RANK" in os.environ
     if not launched and (args.gpus > 1 or os.environ.get("IBO_BENCH_FORCE_SPAWN")):
         # no GPU call has been made in this process (ibo_amd is imported by the workers only)

@@ -412,10 +412,36 @@ def g10_testfunctions():
     save("g10_testfunctions", **out)
 
 
+# ---------------------------------------------------------------- G11 the compiled reference's searches
+def g11_ref_direct():
+    """the compiled reference's answers to the searches that tests/test_cpu_host.py and tests/test_oracle_golden.py hold
+    against it, for a checkout where oracle/_ref/libego.so cannot be built"""
+    root = os.path.dirname(os.path.dirname(OUT))
+    sys.path[:0] = [root, os.path.join(root, "tests")]
+    from oracle import oracle as orc
+    from test_cpu_host import random_direct_runs
+    from test_oracle_golden import REF_ACQMAX, _gp_from_case, shekel5
+    ref = orc.RefLib(LIBEGO)
+    runs = [ref.direct(fb, b, maxiter=mi, maxsample=ms) for fb, b, mi, ms, _ in random_direct_runs()]
+    out = {"rand_fmin": np.array([r[0] for r in runs]),
+           "rand_xmin": np.array([np.r_[r[1], [np.nan] * (7 - len(r[1]))] for r in runs]),
+           "rand_ns": np.array([r[2] for r in runs], dtype=np.int64)}
+    g = np.load(os.path.join(OUT, "g3_cases.npz"))
+    for name in g["names"]:
+        gp, p = _gp_from_case(orc, g, str(name))
+        for acq, parm in REF_ACQMAX:
+            r, rx = ref.acqmax(gp, g[p + "bounds"].tolist(), acq, parm, maxiter=15)
+            out["acqmax/%s/%d" % (name, acq)] = np.r_[r, rx]
+    g4 = np.load(os.path.join(OUT, "g4_direct.npz"))
+    fm, xm, ns = ref.direct(shekel5(g4), g4["shekel_bounds"].tolist(), maxiter=25)
+    out["shekel_direct"] = np.r_[fm, xm, ns]
+    save("g11_ref_direct", **out)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g6", "g7", "g8", "g9", "g10"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g6", "g7", "g8", "g9", "g10", "g11"]
     fns = dict(g1=g1_demo, g2=g2_hyper, g3=g3_cases, g4=g4_direct, g6=g6_sweeps, g7=g7_prefs, g8=g8_nlml, g9=g9_lhc,
-               g10=g10_testfunctions)
+               g10=g10_testfunctions, g11=g11_ref_direct)
     for w in which:
         fns[w]()
     shutil.rmtree(TMP, ignore_errors=True)

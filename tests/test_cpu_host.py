@@ -177,17 +177,10 @@ def test_direct_grouped_selection_matches_the_all_pairs_reference(oracle):
         assert ns == ref[2] and fm == ref[0] and np.array_equal(xm, ref[1])
 
 
-def test_direct_against_the_compiled_reference_on_random_objectives(oracle):
-    """csrc/direct_host.cpp (per-class decisions, hull witnesses, one batch per iteration) against the reference's OWN compiled search
-    (oracle/_ref/libego.so, cpp/direct.cpp:329-581) on 160 random objectives in 1..7 dimensions -- smooth, rippled, terraced (ties inside
-    every size class), clipped at zero like an expected improvement (exact zeros over most of the box), shifted boxes, boxes with a fixed dimension -- at two budgets:
-    the same minimum, the same point, the same number of samples, value for value"""
-    if not oracle.RefLib.available():
-        pytest.skip("oracle/_ref/libego.so not built")
-    from ibo_amd.utils.optimize import cdirect
-    ref = oracle.RefLib()
+def random_direct_runs():
+    """(fb, bounds, maxiter, maxsample, label) of the 320 searches below; tests/golden/make_golden.py g11 stores the compiled
+    reference's answers to them"""
     rs = np.random.RandomState(4242)
-    ncase = 0
     for case in range(160):
         D = 1 + case % 7
         c = rs.rand(D); w = rs.uniform(.5, 3, D); ph = rs.rand(D) * 6
@@ -202,10 +195,27 @@ def test_direct_against_the_compiled_reference_on_random_objectives(oracle):
         # (a fixed dimension maps to 0: the compiled reference does not survive an objective that returns NaN)
         fb = (lambda x, f=f, b=b: f((np.asarray(x) - np.array([q[0] for q in b])) / np.array([(q[1] - q[0]) or 1.0 for q in b])))
         for maxiter, maxsample in ((6, 20000), (28, 1500)):
-            fm, xm, ns = cdirect(fb, b, maxiter=maxiter, maxsample=maxsample, return_samples=True)
+            yield fb, b, maxiter, maxsample, (case, D, kind, maxiter)
+
+
+def test_direct_against_the_compiled_reference_on_random_objectives(oracle):
+    """csrc/direct_host.cpp (per-class decisions, hull witnesses, one batch per iteration) against the reference's OWN compiled search
+    (oracle/_ref/libego.so, cpp/direct.cpp:329-581) on 160 random objectives in 1..7 dimensions -- smooth, rippled, terraced (ties inside
+    every size class), clipped at zero like an expected improvement (exact zeros over most of the box), shifted boxes, boxes with a fixed dimension -- at two budgets:
+    the same minimum, the same point, the same number of samples, value for value.  Without oracle/_ref (no reference sources to
+    build it from) the compiled reference's answers come from tests/golden/g11_ref_direct.npz."""
+    from ibo_amd.utils.optimize import cdirect
+    ref = oracle.RefLib() if oracle.RefLib.available() else None
+    g = load_golden("g11_ref_direct")
+    ncase = 0
+    for fb, b, maxiter, maxsample, label in random_direct_runs():
+        fm, xm, ns = cdirect(fb, b, maxiter=maxiter, maxsample=maxsample, return_samples=True)
+        if ref is not None:
             r = ref.direct(fb, b, maxiter=maxiter, maxsample=maxsample)
-            assert ns == r[2] and fm == r[0] and np.array_equal(xm, r[1]), (case, D, kind, maxiter, ns, r[2])
-            ncase += 1
+        else:
+            r = (g["rand_fmin"][ncase], g["rand_xmin"][ncase][:len(b)], g["rand_ns"][ncase])
+        assert ns == r[2] and fm == r[0] and np.array_equal(xm, r[1]), label + (ns, r[2])
+        ncase += 1
     assert ncase == 320
 
 

@@ -1143,7 +1143,7 @@ def test_two_rank_rccl_bench_when_two_gpus_are_visible(ibo):
         pytest.skip("one GPU visible")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "IBO_COMM_ID_FILE")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     j = json.loads(p.stdout.strip().splitlines()[-1])
     assert j["n_gpus"] == 2 and j["rccl_nranks"] == 2 and j["value"] > 0

@@ -92,13 +92,13 @@ def test_a_failing_rank_fails_the_launch(launch_ranks):
 
 
 def test_bench_line_with_two_ranks_on_one_device(launch_ranks):
-    """bench.py --gpus 2 as the driver runs it (its own launcher, fresh rank processes, barriers, max-over-ranks timing, the
+    """bench.py --gpus 2 --full as a two-GPU node would run it (its own launcher, fresh rank processes, barriers, max-over-ranks timing, the
     candidate-sharded sweep with one arg-max exchange per step, the sharded C3 gallery and C5 grid of the `configs` block) on a box with ONE
     GPU: IBO_BENCH_ONE_DEVICE=1 puts both ranks on device 0 and the exchange on the socket transport.  The numbers mean nothing (the ranks
     share the GPU); the line's structure, the agreement of the ranks and the sharded configs' results are what is checked."""
     import json
     env = {"IBO_BENCH_ONE_DEVICE": "1"}
-    res = launch_ranks([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], 1, env=env,
+    res = launch_ranks([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], 1, env=env,
                        timeout=900, rank_env=False)
     assert res["rc"] == [0], res["err"][0][-3000:]
     lines = [l for l in res["out"][0].splitlines() if l.strip()]
@@ -114,13 +114,13 @@ def test_bench_line_with_two_ranks_on_one_device(launch_ranks):
 
 
 def test_bench_line_with_eight_ranks_on_one_device(launch_ranks):
-    """The exact command line the driver issues on the 8-GPU node -- `python bench.py --gpus 8 --steps 2 --warmup 1` -- minus RCCL:
+    """The eight-GPU command line -- `python bench.py --gpus 8 --steps 2 --warmup 1 --full` -- minus RCCL:
     IBO_BENCH_ONE_DEVICE=1 puts the eight rank processes on device 0 and the exchange on the socket transport.  Eight slots in every
     exchange, seven of eight ranks losing each one, the C3 gallery over eight 2^19-candidate shards (= BASELINE configs[2]'s 4M candidates)
     and the C5 grid with 64 theta-points per rank (= configs[4]'s 512) of the `configs` block.  Numbers mean nothing (the ranks share the GPU)."""
     import json
     env = {"IBO_BENCH_ONE_DEVICE": "1"}
-    res = launch_ranks([os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], 1, env=env,
+    res = launch_ranks([os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], 1, env=env,
                        timeout=1500, rank_env=False)
     assert res["rc"] == [0], res["err"][0][-3000:]
     lines = [l for l in res["out"][0].splitlines() if l.strip()]

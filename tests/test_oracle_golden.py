@@ -4,11 +4,11 @@ reference (tests/golden/make_golden.py) and, when present, against the
 reference's own compiled C++ (oracle/_ref/libego.so).  CPU only.
 """
 import numpy as np
-import pytest
 
 from conftest import load_golden, kern_from_golden, synth
 
 RT = 1e-9   # oracle-vs-reference tolerance (same algorithm, same fp64; only summation order differs)
+REF_ACQMAX = ((0, .01), (1, .05), (2, 1.3))   # (acquisition, parameter) of the acqmaxGP runs held against the compiled reference: EI, PI, UCB
 
 
 def close(a, b, rtol=RT, atol=1e-12):
@@ -198,22 +198,29 @@ def test_g8_nlml(oracle):
 
 
 def test_oracle_matches_compiled_reference(oracle):
-    """oracle/_ref/libego.so = the reference's own C++; compare DIRECT runs sample-for-sample."""
-    if not oracle.RefLib.available():
-        pytest.skip("oracle/_ref/libego.so not built (no /root/reference here)")
-    ref = oracle.RefLib()
+    """oracle/_ref/libego.so = the reference's own C++; compare DIRECT runs sample-for-sample.  Without oracle/_ref (no
+    reference sources to build it from) the compiled reference's answers come from tests/golden/g11_ref_direct.npz."""
+    ref = oracle.RefLib() if oracle.RefLib.available() else None
+    stored = load_golden("g11_ref_direct")
     g = load_golden("g3_cases")
     for name in g["names"]:
         gp, p = _gp_from_case(oracle, g, str(name))
         bounds = g[p + "bounds"].tolist()
-        for acq, parm in ((oracle.ACQ_EI, .01), (oracle.ACQ_PI, .05), (oracle.ACQ_UCB, 1.3)):
+        for acq, parm in REF_ACQMAX:
             o, ox, _ = oracle.acqmax_native(gp, bounds, acq, parm, maxiter=15)
-            r, rx = ref.acqmax(gp, bounds, acq, parm, maxiter=15)
+            if ref is not None:
+                r, rx = ref.acqmax(gp, bounds, acq, parm, maxiter=15)
+            else:
+                r, rx = stored["acqmax/%s/%d" % (name, acq)][0], stored["acqmax/%s/%d" % (name, acq)][1:]
             close(o, r, rtol=1e-12, atol=1e-14); close(ox, rx, rtol=1e-13)
     g4 = load_golden("g4_direct")
     f = shekel5(g4)
     a = oracle.cdirect(f, g4["shekel_bounds"].tolist(), maxiter=25)
-    b = ref.direct(f, g4["shekel_bounds"].tolist(), maxiter=25)
+    if ref is not None:
+        b = ref.direct(f, g4["shekel_bounds"].tolist(), maxiter=25)
+    else:
+        s = stored["shekel_direct"]
+        b = (s[0], s[1:-1], s[-1])
     assert a[2] == b[2]
     close(np.r_[a[0], a[1]], np.r_[b[0], b[1]], rtol=0, atol=0)
 

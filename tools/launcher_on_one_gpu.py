@@ -8,7 +8,7 @@ arg-max exchange -- everything the 8-GPU run does except a second rank.  Checks:
   * launcher == "self (bench.py children)", rccl_nranks == 1
   * same arg-max (index and value) as the plain single-process run, `value` within 2 % of it
   * the private rendezvous directory is gone afterwards
-  * the sharded gallery / sharded NLML grid run under the launcher too (--gpus 1 without --no-extras)
+  * the sharded gallery / sharded NLML grid run under the launcher too (--gpus 1 --full)
 Exit status non-zero on any failure.   python3 tools/launcher_on_one_gpu.py [out.json]"""
 import glob
 import json
@@ -50,7 +50,7 @@ def main():
     report["value_ratio_spawned_over_plain"] = ratio
     assert abs(ratio - 1.0) < 0.02, ratio
     # the sharded gallery and NLML grid through the same path (world of one rank, RCCL collectives and all)
-    full = run({"IBO_BENCH_FORCE_SPAWN": "1"}, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    full = run({"IBO_BENCH_FORCE_SPAWN": "1"}, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert full["launcher"] == "self (bench.py children)" and full["rccl_nranks"] == 1
     cfg = full["configs"]
     report["spawned_configs"] = {"c3_gallery8_ms": cfg["c3_gallery8"]["ms"], "c3_gallery_min_dist": cfg["c3_gallery8"]["min_pairwise_distance"],

@@ -6,7 +6,7 @@ mkdir -p gpurun_out/final_$TAG profiles
 O=gpurun_out/final_$TAG
 bash tools/profile_bench.sh $TAG > $O/profile_bench.log 2>&1
 bash tools/profile_configs.sh $TAG > $O/profile_configs.log 2>&1
-python3 bench.py --steps 20 --warmup 3 > profiles/${TAG}_bench_n1.json 2> $O/bench.err
+python3 bench.py --steps 20 --warmup 3 --full > profiles/${TAG}_bench_n1.json 2> $O/bench.err
 python3 bench.py --config c3 --steps 3 --warmup 1 --no-cpu-baseline > profiles/${TAG}_bench_c3_n1.json 2> $O/bench_c3.err
 python3 bench.py --config c5 --steps 3 --warmup 1 --no-cpu-baseline > profiles/${TAG}_bench_c5_n1.json 2> $O/bench_c5.err
 python3 tools/run_configs.py c2 c3 c4 c5 > profiles/${TAG}_configs_c2_c5.jsonl 2> $O/configs.err
