@@ -122,6 +122,7 @@ static int fit_factor(ibo_gp *g, const KParams &kp, int N, double noise, bool ha
     HIP_TRY(hipEventRecord(g->fit0, s));
     // R, and in the same pass the identity-padded copy the factorisation works on
     const bool fused = single_level_order(Np);                   // (else the two-level order; both out of place: the matrix in T, the factor into L)
+    if (!u3_fits(Np)) return fail(IBO_ERR_ARG, "at most 23168 rows: the factorisation's packed store must lie inside 2^32 - 1 bytes (model: %d padded rows)", Np);
     // from g_super_min_nb block columns on the single-level order runs in super-panels: the matrix and the ride-along's identity are the two
     // halves of ONE tall buffer (launch_cholesky_super), T and W are outputs only
     const bool super = super_order(Np);

@@ -155,7 +155,12 @@ static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 // ibo_gp_fit, the preference GP's factorisations and ibo_nlml_grad: the order fixes the last bits of L and W.
 static inline bool single_level_order(int Np) { return Np / 64 < g_fused2_min_nb; }
 
-static inline bool super_order(int Np) { return single_level_order(Np) && Np / 64 >= g_super_min_nb; }
+// The super-panels address their tall store [A ; E] (2 Np^2 doubles) through a buffer descriptor with 32-bit offsets: only while it lies inside
+// 2^31 - 1 bytes (11584 rows; an option that keeps a larger matrix in the single-level order takes the step-by-step launches instead)
+static inline bool super_order(int Np) { return single_level_order(Np) && Np / 64 >= g_super_min_nb && 2 * (size_t)Np * Np * sizeof(double) <= 0x7fffffffu; }
+// The packed stores of the left-looking updates (update3.hip) are addressed with 32-bit unsigned byte offsets: one matrix must lie inside
+// 2^32 - 1 bytes (23168 rows)
+static inline bool u3_fits(int Np) { return (size_t)Np * Np * sizeof(double) <= 0xffffffffu; }
 
 // ---- helpers one unit lends another
 int exp_table(int device, const double **out);                                                            // abi_sweep.hip: 2^(j/2048), one per device

@@ -242,6 +242,7 @@ extern "C" int ibo_nlml_grad(int device, int ktype, int N, int D, const double *
     // up to 2048 rows: the fit's route -- fused steps with W = L^-1 riding along (dT: the matrix being reduced, dKi: (L^-1)^T
     // until the transpose) -- instead of the three-kernel columns and the recursive-doubling inversion
     const bool fused = single_level_order(Np);
+    if (!u3_fits(Np)) return fail(IBO_ERR_ARG, "at most 23168 rows: the factorisation's packed store must lie inside 2^32 - 1 bytes (model: %d padded rows)", Np);
     if (!ws.t0) { HIP_TRY(hipEventCreate(&ws.t0)); HIP_TRY(hipEventCreate(&ws.t1)); }
     HIP_TRY(hipEventRecord(ws.t0, s));
     if (fused && super_order(Np)) {

@@ -65,7 +65,10 @@ static int run_sweep(ibo_gp *g, int64_t M, const double *cand_dev, int acq, doub
     // They beat the GEMV kernel down to a single candidate (N = 2048: 22 us against 87; N = 1024: 16 against 38), which
     // is left with the models they do not take (no dot form, rows beyond sweep2's LDS budget).
     const bool small2_ok = g_force_path == 0 && M <= 4096 && a.dot_form && sweep2_fits(a.Npad);
-    bool gemv = (g_force_path == 1) || (g_force_path == 0 && M <= 16 && !small2_ok);
+    // (the GEMV kernel holds k* of a candidate in LDS: beyond 20416 rows a few candidates go to the panel-split kernel)
+    bool gemv = (g_force_path == 1) || (g_force_path == 0 && M <= 16 && !small2_ok && sweep_gemv_fits(a.Npad));
+    if (gemv && !sweep_gemv_fits(a.Npad))
+        return fail(IBO_ERR_ARG, "the GEMV sweep kernel holds at most 20416 rows in its 160 KiB of LDS (model: %d padded rows)", a.Npad);
     // small batches: spread the IBO_SPLIT_PANEL-row panels over the grid too (one tile per 64 candidates alone
     // would leave most of the 256 CUs idle); above ~128 tiles the plain kernel fills the chip
     // (4097 .. 8192 candidates are at most 256 tiles of the large-batch kernel -- one round of the chip, 134 us at N = 1024 and

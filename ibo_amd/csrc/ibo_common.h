@@ -234,6 +234,7 @@ int sweep2_part_nlev(int Npad);                   // levels a new kept state get
 void set_part_levels(int v);
 int sweep2_part_levels(int Npad, int *h);        // the row splits h[0] < h[1] < .. (multiples of 128, at most 3): level l covers rows [h[l-1], h[l]); returns the number of levels
 bool sweep2_fits(int Npad);
+bool sweep_gemv_fits(int Npad);      // sweep.hip: k* of one candidate in LDS, 8 Npad + 96 bytes <= 160 KiB (20416 rows)
 bool sweep2_rank1_fits(int Npad, int D);
 // small batches (16 < M <= 8192), dot form: k* to HBM, one workgroup per 16-row block of W, fixed-order sums (small2.hip)
 int launch_sweep_small(const SweepArgs &a, double *ws, hipStream_t s, hipEvent_t e0, hipEvent_t e1);

@@ -563,8 +563,12 @@ int launch_sweep_mfma(const SweepArgs &a, hipStream_t s, hipEvent_t e0, hipEvent
     return launch_argmax_final(a, ntiles, s);
 }
 
+// k* of one candidate (8 Npad bytes, dynamic) and red[4][3] (96 bytes, static) in the 160 KiB of LDS a workgroup may hold on gfx950: 20416 rows
+bool sweep_gemv_fits(int Npad) { return sizeof(double) * ((size_t)Npad + 12) <= 160 * 1024; }
+
 int launch_sweep_gemv(const SweepArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
+    if (!sweep_gemv_fits(a.Npad)) return (int)hipErrorInvalidConfiguration;     // (run_sweep reports it before anything is launched)
     int nrc = a.Npad / 64;
     dim3 grid(nrc, (unsigned)a.M);
     if (sizeof(double) * a.Npad > 64 * 1024) {     // up to 160 KiB of LDS per workgroup on gfx950

@@ -198,9 +198,10 @@ int launch_pack_xa(const double *Xs, const double *ak, int N, int Npad, int DP, 
 
 // dynamic LDS: a window of the two alpha vectors, at most s2_awin rows (64 or 48 KiB); static: 64 KiB of k* stages,
 // 16 KiB exp table, candidates (32 x 21 doubles up to 16 dimensions, 32 x 37 up to 32), q and mean partials (4 + 4 KiB):
-// 93.3 / 97.3 KiB.  Any N whose packed W the 2 GiB buffer descriptor covers (16384 rows) fits; the refresh kernel keeps
-// three whole vectors (24 B/row + 27.3 / 31.3 KiB).
-bool sweep2_fits(int Npad) { return Npad <= 16384; }
+// 93.3 / 97.3 KiB.  The packed W is read through a buffer descriptor clamped to 2^31 - 1 bytes: the kernels take models whose packed W
+// lies inside it, up to 16320 rows (at 16384 rows it is exactly 2^31 bytes, and the large-batch kernel's variances came out wrong there);
+// the refresh kernel keeps three whole vectors (24 B/row + 27.3 / 31.3 KiB).
+bool sweep2_fits(int Npad) { return (size_t)Npad * Npad * sizeof(double) <= 0x7fffffffu; }
 bool sweep2_rank1_fits(int Npad, int D) { return (size_t)((Npad + 127) & ~127) * 24 + (D <= 18 ? 28 : 32) * 1024 <= 160 * 1024; }
 
 

@@ -36,9 +36,11 @@ typedef double d2_t __attribute__((ext_vector_type(2)));
 
 typedef unsigned u3_v4 __attribute__((ext_vector_type(4)));
 
+// num_records is an unsigned 32-bit field and the byte offsets below are unsigned: the descriptor covers the exact byte count up to
+// 2^32 - 1 (a packed store of 16384 rows is exactly 2^31 bytes; one of 20480 rows 3.4e9).  Beyond, fits are refused (u3_fits).
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t u3_rsrc(const void *p, size_t bytes)
 {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)(bytes > 0x7fffffffu ? 0x7fffffffu : bytes), 0x00020000);
+    return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)(unsigned)(bytes > 0xffffffffu ? 0xffffffffu : bytes), 0x00020000);
 }
 __device__ __forceinline__ double u3_lo(const u3_v4 &v) { return __hiloint2double((int)v.y, (int)v.x); }
 __device__ __forceinline__ double u3_hi(const u3_v4 &v) { return __hiloint2double((int)v.w, (int)v.z); }
@@ -198,7 +200,7 @@ __global__ __launch_bounds__(U3_NW * 64, 4) void chol_update3_kernel(double *L, 
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             const int f = wave + 8 * (2 * half + u);
-            v[u] = __builtin_amdgcn_raw_buffer_load_b128(rP, lane16, (unsigned)(((gB + (f & 7)) * nk8s + kb8 + st * (U3_KS / 8) + (f >> 3)) * 1024), 0);
+            v[u] = __builtin_amdgcn_raw_buffer_load_b128(rP, lane16, (unsigned)((gB + (f & 7)) * nk8s + kb8 + st * (U3_KS / 8) + (f >> 3)) * 1024u, 0);
         }
     };
     auto stash_b = [&](int b, int half, const u3_v4 (&v)[2]) {
