@@ -546,7 +546,7 @@ extern "C" int ibo_cov_matrix(int device, int ktype, int D, const double *hyper,
                               int n1, const double *A1, int n2, const double *A2, int diag_rule, double noise,
                               double *K_host)
 {
-    if (!A1 || !K_host || n1 < 1) return fail(IBO_ERR_ARG, "bad argument");
+    if (!A1 || !K_host || n1 < 1 || (A2 && n2 < 1)) return fail(IBO_ERR_ARG, "bad argument");
     IBO_TRY(use_device(device));
     KParams kp;
     IBO_TRY(make_kparams(ktype, D, hyper, nhyper, sf2, &kp));

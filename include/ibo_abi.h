@@ -223,7 +223,8 @@ int ibo_gp_last_fit_ms(ibo_gp_t *gp, float *ms);
 
 /* covariance matrix only (no factorisation): Kernel.covMatrix / _computeCorrelations.
  * A2 may be NULL (square K(A1,A1) with the chosen diagonal rule) or a second
- * point set (cross-covariance K(A1,A2), n1 x n2, no diagonal rule). */
+ * point set (cross-covariance K(A1,A2), n1 x n2, no diagonal rule).  n1 >= 1, and n2 >= 1 when A2 is given
+ * (IBO_ERR_ARG otherwise). */
 int ibo_cov_matrix(int device, int ktype, int D, const double *hyper_host, int nhyper, double sf2,
                    int n1, const double *A1_host, int n2, const double *A2_host,
                    int diag_rule, double noise, double *K_host);
