@@ -3,10 +3,11 @@ Acquisition functions and their maximisers, with the reference's names and
 defaults (ego/acquisition/__init__.py):
 
     EI(GP, xi=.01)  PI(GP, xi=.01)  UCB(GP, NA, delta=0.1, scale=0.2)    .negf(x) / .f(x)
-    maximizeEI(model, bounds, useCDIRECT=True, xi=0.01, maxiter=50, maxtime=30, maxsample=10000)
-    maximizePI(model, bounds, xi=0.01, maxiter=50, maxtime=30, maxsample=10000, useCDIRECT=True)
-    maximizeUCB(model, bounds, delta=0.1, scale=0.2, useCDIRECT=True, maxiter=50, maxtime=30, maxsample=10000)
-        -> (opt, optx)
+    .gradient(X) -> (values, gradients)   .negf_grad(x) -> (negf(x), -grad f(x))   (ibo_acq_grad_batch)
+    maximizeEI(model, bounds, useCDIRECT=True, xi=0.01, maxiter=50, maxtime=30, maxsample=10000, polish=False)
+    maximizePI(model, bounds, xi=0.01, maxiter=50, maxtime=30, maxsample=10000, useCDIRECT=True, polish=False)
+    maximizeUCB(model, bounds, delta=0.1, scale=0.2, useCDIRECT=True, maxiter=50, maxtime=30, maxsample=10000, polish=False)
+        -> (opt, optx);  polish=True: a bounded L-BFGS-B finish from DIRECT's point on the exact gradient
 
 plus the batched entry point the GPU makes worthwhile:
 
@@ -28,6 +29,30 @@ from ..utils.latinhypercube import lhcSample                                    
 _ACQ = {'ei': _lib.ACQ_EI, 'pi': _lib.ACQ_PI, 'ucb': _lib.ACQ_UCB}
 
 
+def _acq_gradient(GP, X, acq, parm, ymax):
+    """values and gradients (M, D) of an acquisition at the points X with the Python classes' conventions (NR erf, clamp
+    [1e-7, 10]): one ibo_acq_grad_batch call, or -- with an augmented factor in force -- the chain rule on the host from
+    posterior_gradient, as GaussianProcess._eval forms the values there"""
+    Q = _lib.f64(np.atleast_2d(np.asarray(X, dtype=float)))
+    M, D = Q.shape
+    if GP._augdev is not None:
+        mu, s2, dmu, ds2 = GP.posterior_gradient(Q)
+        sig = np.sqrt(s2)
+        dsig = ds2 / (2.0 * sig)[:, None]
+        if acq == _lib.ACQ_UCB:
+            return mu + parm * sig, dmu + parm * dsig
+        yd = mu - ymax - parm
+        Z = yd / sig
+        if acq == _lib.ACQ_PI:
+            return CDF(Z), (PDF(Z) / sig)[:, None] * (dmu - Z[:, None] * dsig)
+        return yd * CDF(Z) + sig * PDF(Z), CDF(Z)[:, None] * dmu + PDF(Z)[:, None] * dsig
+    GP._push_prior()
+    val, grad = np.empty(M), np.empty((M, D))
+    _lib.check(_lib.lib.ibo_acq_grad_batch(GP._handle(), M, _lib.dp(Q), acq, float(parm), _lib.ERF_NR, _lib.CLAMP_PY,
+                                           float(ymax), None, None, _lib.dp(val), None, None, _lib.dp(grad)))
+    return val, grad
+
+
 class UCB(object):
     """upper confidence bound; note sqrt(scale * sBeta) with sBeta already a square
     root -- the class and the native path disagree in the reference and both are
@@ -47,6 +72,15 @@ class UCB(object):
     def f(self, x):
         return -self.negf(x)
 
+    def gradient(self, X):
+        """(values, gradients (M, D)) at the points X, the conventions of negf"""
+        return _acq_gradient(self.GP, X, _lib.ACQ_UCB, np.sqrt(self.scale * self.sBeta), np.max(self.GP.Y))
+
+    def negf_grad(self, x):
+        """(negf(x), -grad f(x)): the objective and gradient scipy.optimize.minimize(jac=True) asks for"""
+        v, g = self.gradient(x)
+        return -v[0], -g[0]
+
 
 class PI(object):
     """probability of improvement (:100-114); NR-erf CDF as the Python reference"""
@@ -63,6 +97,15 @@ class PI(object):
 
     def f(self, x):
         return -self.negf(x)
+
+    def gradient(self, X):
+        """(values, gradients (M, D)) at the points X, the conventions of negf"""
+        return _acq_gradient(self.GP, X, _lib.ACQ_PI, self.xi, self.Z - self.xi)
+
+    def negf_grad(self, x):
+        """(negf(x), -grad f(x)): the objective and gradient scipy.optimize.minimize(jac=True) asks for"""
+        v, g = self.gradient(x)
+        return -v[0], -g[0]
 
 
 class EI(object):
@@ -82,6 +125,15 @@ class EI(object):
 
     def f(self, x):
         return -self.negf(x)
+
+    def gradient(self, X):
+        """(values, gradients (M, D)) at the points X, the conventions of negf"""
+        return _acq_gradient(self.GP, X, _lib.ACQ_EI, self.xi, self.ymax)
+
+    def negf_grad(self, x):
+        """(negf(x), -grad f(x)): the objective and gradient scipy.optimize.minimize(jac=True) asks for"""
+        v, g = self.gradient(x)
+        return -v[0], -g[0]
 
     def values(self, X):
         """EI at many points at once (one GPU launch)"""
@@ -132,9 +184,46 @@ def cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc=None, xi=-1, b
 gpuDirectGP = cdirectGP          # the name earlier rounds of this package used
 
 
+POLISH_MAXITER = 30
+
+
+def _polish(model, bounds, acqfunc, parm, opt, optx):
+    """finish DIRECT's point with L-BFGS-B on the objective DIRECT maximised (libego's k* variance, libm erf, clamp
+    [1e-8, 10], the same parm; one ibo_acq_grad_batch call per evaluation), bounded to the box and at most POLISH_MAXITER
+    iterations.  The end point is re-evaluated with ibo_acq_batch and returned only if it is strictly better than DIRECT's."""
+    from scipy.optimize import minimize
+    lb = _lib.f64([b[0] for b in bounds]); ub = _lib.f64([b[1] for b in bounds])
+    D = len(lb)
+    code = _ACQ[acqfunc]
+    _, _, sf2_py, sf2_native = model.kernel._ibo_spec()
+    h = model._handle()
+    model._push_prior()
+    v, g = np.empty(1), np.empty((1, D))
+
+    def fg(x):
+        q = _lib.f64(np.clip(x, lb, ub).reshape(1, D))
+        _lib.check(_lib.lib.ibo_acq_grad_batch(h, 1, _lib.dp(q), code, float(parm), _lib.ERF_LIBM, _lib.CLAMP_NATIVE,
+                                               float('nan'), None, None, _lib.dp(v), None, None, _lib.dp(g)))
+        return -v[0], -g[0].copy()
+
+    _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(h, sf2_native))
+    try:
+        res = minimize(fg, np.clip(optx, lb, ub), jac=True, method='L-BFGS-B', bounds=list(zip(lb, ub)),
+                       options=dict(maxiter=POLISH_MAXITER, ftol=1e-15, gtol=1e-12))
+        x = _lib.f64(np.clip(res.x, lb, ub))
+        val = np.empty(1)
+        _lib.check(_lib.lib.ibo_acq_batch(h, 1, _lib.dp(x), code, float(parm), _lib.ERF_LIBM, _lib.CLAMP_NATIVE,
+                                          float('nan'), None, None, _lib.dp(val)))
+    finally:
+        _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(h, sf2_py))
+    if val[0] > opt:
+        return float(val[0]), x
+    return opt, optx
+
+
 def maximizeUCB(model, bounds, delta=0.1, scale=0.2, useCDIRECT=True, maxiter=50, maxtime=30, maxsample=10000,
-                **kwargs):
-    """maximise the GP-UCB of [Srinivas 2009] (:78-96)"""
+                polish=False, **kwargs):
+    """maximise the GP-UCB of [Srinivas 2009] (:78-96); polish=True: see _polish"""
     if not useCDIRECT:
         print('using DIRECT')
         ucb = UCB(model, len(bounds), delta=delta, scale=scale, **kwargs)
@@ -142,32 +231,41 @@ def maximizeUCB(model, bounds, delta=0.1, scale=0.2, useCDIRECT=True, maxiter=50
         opt, optx = direct(ucb.negf, bounds, maxiter=maxiter, maxtime=maxtime, maxsample=maxsample)
         return -opt, optx
     if isinstance(model, GaussianProcess):
-        return cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='ucb', delta=delta, scale=scale,
-                           **kwargs)
+        opt, optx = cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='ucb', delta=delta, scale=scale,
+                              **kwargs)
+        if polish:
+            return _polish(model, bounds, 'ucb', _ucb_parm(model, bounds, delta, scale), opt, optx)
+        return opt, optx
     raise ValueError
 
 
-def maximizePI(model, bounds, xi=0.01, maxiter=50, maxtime=30, maxsample=10000, useCDIRECT=True, **kwargs):
-    """maximise the probability of improvement [Lizotte 2008] (:117-134)"""
+def maximizePI(model, bounds, xi=0.01, maxiter=50, maxtime=30, maxsample=10000, useCDIRECT=True, polish=False, **kwargs):
+    """maximise the probability of improvement [Lizotte 2008] (:117-134); polish=True: see _polish"""
     if not useCDIRECT:
         print('using DIRECT')
         pi = PI(model, xi, **kwargs)
         opt, optx = direct(pi.negf, bounds, maxiter=maxiter, maxtime=maxtime, maxsample=maxsample)
         return -opt, optx
     if isinstance(model, GaussianProcess):
-        return cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='pi', xi=xi, **kwargs)
+        opt, optx = cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='pi', xi=xi, **kwargs)
+        if polish:
+            return _polish(model, bounds, 'pi', xi, opt, optx)
+        return opt, optx
     raise ValueError
 
 
-def maximizeEI(model, bounds, useCDIRECT=True, xi=0.01, maxiter=50, maxtime=30, maxsample=10000, **kwargs):
-    """maximise expected improvement (:174-197)"""
+def maximizeEI(model, bounds, useCDIRECT=True, xi=0.01, maxiter=50, maxtime=30, maxsample=10000, polish=False, **kwargs):
+    """maximise expected improvement (:174-197); polish=True: see _polish"""
     if not useCDIRECT:
         print('using DIRECT')
         ei = EI(model, xi, **kwargs)
         opt, optx = direct(ei.negf, bounds, maxiter=maxiter, maxtime=maxtime, maxsample=maxsample)
         return -opt, optx
     if isinstance(model, GaussianProcess):
-        return cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='ei', xi=xi, **kwargs)
+        opt, optx = cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='ei', xi=xi, **kwargs)
+        if polish:
+            return _polish(model, bounds, 'ei', xi, opt, optx)
+        return opt, optx
     raise ValueError
 
 

@@ -492,6 +492,7 @@ extern "C" int ibo_gp_destroy(ibo_gp_t *g)
     g->T.release(); g->Wp.release(); g->diag64.release(); g->alphaY.release(); g->alpha1.release();
     g->tmp.release(); g->cand.release(); g->outs.release(); g->excl.release(); g->qpart.release();
     g->mupart.release(); g->partv.release(); g->res_v.release(); g->parti.release(); g->res_i.release(); g->state.release(); g->small_ws.release();
+    g->grad_ws.release(); g->grad_cand.release(); g->grad_out.release();
     g->tile_done.release(); g->tile_ub.release(); g->part_words.release(); g->tile_rows.release(); g->tile_sel.release();
     g->done_count.release(); g->srv_ctl.release(); g->tall.release(); g->Pk2.release();
     g->pw.Rinv.release(); g->pw.A.release(); g->pw.Lh.release(); g->pw.E.release(); g->pw.Et.release(); g->pw.d64.release();

@@ -121,6 +121,7 @@ struct ibo_gp {
     DevBuf<int> tile_done; DevBuf<double> tile_ub; DevBuf<unsigned long long> part_words; DevBuf<int> tile_rows, tile_sel;   // kept state with incomplete tiles (st_pruned)
     bool st_pruned = false; int st_N0 = 0; int st_nlev = 2;   // st_N0: the model's rows when the state was formed; st_nlev: its levels of W's rows
     DevBuf<double> small_ws;        // small2.hip: k* in fragment order + partial sums of a small batch
+    DevBuf<double> grad_ws, grad_cand, grad_out;   // ibo_acq_grad_batch (grad.hip): one chunk's scratch, its candidates and its three M x D outputs
     uint64_t st_gen = 0; size_t st_off = 0; int64_t st_M = 0; int st_N = 0; double st_sf2 = 0.0; unsigned st_epoch = 0;   // st_gen: generation of the candidate array's allocation (0: no state)
     unsigned fit_epoch = 0;         // bumped by every full fit: a kept state never survives one
     int reserve = 0;                // rows of head-room the next fit leaves for ibo_gp_extend (ibo_gp_reserve)

@@ -1,6 +1,7 @@
 // abi_sweep.hip -- the evaluation side of the C ABI: candidate sweeps (one-shot and with kept per-candidate state), host batches,
 // and DIRECT on the GPU objective.
 #include "abi_internal.h"
+#include "grad.h"
 
 // 2^(j/2048), j < 2048: the table behind sweep2's exp (one per device, created on first use)
 static std::atomic<double *> g_exp_tab[16];
@@ -449,6 +450,73 @@ extern "C" int ibo_acq_batch(ibo_gp_t *g, int64_t M, const double *Q_host, int a
     IBO_TRY(use_device(g->device));
     if (!g->fitted) return fail(IBO_ERR_STATE, "evaluation before a successful fit");
     return eval_host_points(g, M, Q_host, acq, parm, erf_mode, clamp_lo, mu_host, s2_host, acq_host, ymax);
+}
+
+// ------------------------------------------------------------------------ gradients with respect to the query point (grad.hip)
+// The values (mu, s2, acq) come from eval_host_points -- the very numbers ibo_acq_batch returns; the gradients from the chunks of
+// grad.hip, which form their own mu and s2 for the clip rule and the chain rule.  Up to 64 points: the candidates are read from, and the
+// gradients written to, the handle's pinned staging (no copy launches).
+extern "C" int ibo_acq_grad_batch(ibo_gp_t *g, int64_t M, const double *Q_host, int acq, double parm, int erf_mode,
+                                  double clamp_lo, double ymax, double *mu_host, double *s2_host, double *acq_host,
+                                  double *dmu_host, double *ds2_host, double *dacq_host)
+{
+    if (!g || !Q_host) return fail(IBO_ERR_ARG, "NULL argument");
+    if (!mu_host && !s2_host && !acq_host && !dmu_host && !ds2_host && !dacq_host) return fail(IBO_ERR_ARG, "every output is NULL");
+    if (M < 1) return fail(IBO_ERR_ARG, "M=%lld", (long long)M);
+    if (acq < 0 || acq > 3) return fail(IBO_ERR_ARG, "unknown acquisition %d", acq);
+    if (erf_mode != IBO_ERF_LIBM && erf_mode != IBO_ERF_NR) return fail(IBO_ERR_ARG, "unknown erf mode %d", erf_mode);
+    if (acq == IBO_ACQ_NONE && dacq_host) return fail(IBO_ERR_ARG, "dacq_host with IBO_ACQ_NONE");
+    IBO_TRY(use_device(g->device));
+    if (!g->fitted) return fail(IBO_ERR_STATE, "gradient before a successful fit");
+    if (mu_host || s2_host || acq_host)
+        IBO_TRY(eval_host_points(g, M, Q_host, acq, parm, erf_mode, clamp_lo, mu_host, s2_host, acq_host, ymax));
+    if (!dmu_host && !ds2_host && !dacq_host) return IBO_OK;
+    const int D = g->D;
+    hipStream_t s = g->stream;
+    const GradPlan pl = grad_plan(g->N, g->Npad, g->DP, M);
+    IBO_TRY(g->grad_ws.ensure(pl.ws_doubles));
+    GradArgs a;
+    memset(&a, 0, sizeof(a));
+    a.kp = g->kp; a.N = g->N; a.Npad = g->Npad; a.DP = g->DP;
+    a.Xp = g->Xp.p; a.W = g->W.p; a.alphaY = g->alphaY.p; a.alpha1 = g->alpha1.p;
+    a.prior.nb = g->nb; a.prior.theta = g->ptheta; a.prior.means = g->pmeans.p; a.prior.beta = g->pbeta.p;
+    a.prior.lowerb = g->plowerb.p; a.prior.width = g->pwidth.p;
+    a.noise = g->noise; a.clamp_lo = clamp_lo; a.ymax = (ymax == ymax) ? ymax : g->maxY; a.parm = parm;
+    a.acq = acq; a.erf_mode = erf_mode;
+    a.TM = pl.TM; a.KC = pl.KC; a.nsplit = pl.nsplit; a.nparts = pl.nparts;
+    double *outs_host[3] = {dmu_host, ds2_host, dacq_host};
+    const bool zero_copy = M <= 64;                 // (pl.mc >= 64: one chunk)
+    if (zero_copy) {
+        IBO_TRY(ensure_pinned(g, (size_t)M * D * 4));
+        memcpy(g->pin, Q_host, sizeof(double) * M * D);
+    } else {
+        IBO_TRY(g->grad_cand.ensure((size_t)pl.mc * D));
+        IBO_TRY(g->grad_out.ensure((size_t)pl.mc * D * 3));
+    }
+    for (int64_t c0 = 0; c0 < M; c0 += pl.mc) {
+        const int m = (int)(M - c0 < pl.mc ? M - c0 : pl.mc);
+        const size_t nk = (size_t)m * g->Npad, np = (size_t)pl.nsplit * nk;
+        a.K = g->grad_ws.p; a.H = a.K + nk; a.Pt = a.H + nk; a.Pu = a.Pt + np; a.E = a.Pu + np;
+        const double *cand;
+        double *obase;
+        if (zero_copy) {
+            cand = g->pin; obase = g->pin + (size_t)M * D;
+        } else {
+            HIP_TRY(hipMemcpyAsync(g->grad_cand.p, Q_host + c0 * D, sizeof(double) * m * D, hipMemcpyHostToDevice, s));
+            cand = g->grad_cand.p; obase = g->grad_out.p;
+        }
+        double *od[3];
+        for (int k = 0; k < 3; k++) od[k] = outs_host[k] ? obase + (size_t)k * m * D : nullptr;
+        KERNEL_TRY(launch_grad(a, cand, m, od[0], od[1], od[2], s));
+        if (!zero_copy)
+            for (int k = 0; k < 3; k++)
+                if (outs_host[k]) HIP_TRY(hipMemcpyAsync(outs_host[k] + c0 * D, od[k], sizeof(double) * m * D, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (zero_copy)
+            for (int k = 0; k < 3; k++)
+                if (outs_host[k]) memcpy(outs_host[k], od[k], sizeof(double) * M * D);
+    }
+    return IBO_OK;
 }
 
 // ------------------------------------------------------------------------ DIRECT on the GPU objective

@@ -267,6 +267,45 @@ class GaussianProcess(object):
                                                     _lib.dp(s2)))
         return mu, s2
 
+    def posterior_gradient(self, X):
+        """(mu, s2, dmu, ds2) at the points X ((M, D) or (D,)): the posterior as `posteriors` gives it (the Python clamp
+        [1e-7, 10]) and its gradients with respect to the point, (M, D) each (ibo_acq_grad_batch).  ds2 is 0 where the clamp
+        is active.  An empty model gives the prior's mean and its gradient (0 without a prior), s2 = 1 and ds2 = 0; with an
+        augmented factor in force (addObservationPoint) s2 and ds2 come from it, as in `posteriors`."""
+        Q = np.asarray(X, dtype=float)
+        single = Q.ndim == 1
+        Q = _lib.f64(np.atleast_2d(Q))
+        M, D = Q.shape
+        if len(self.X) == 0:
+            mu, dmu = self._prior_gradient(Q)
+            s2, ds2 = np.ones(M), np.zeros((M, D))
+        else:
+            self._push_prior()
+            mu, s2 = np.empty(M), np.empty(M)
+            dmu, ds2 = np.empty((M, D)), np.empty((M, D))
+            _lib.check(_lib.lib.ibo_acq_grad_batch(self._handle(), M, _lib.dp(Q), _lib.ACQ_NONE, 0.0, _lib.ERF_NR, _lib.CLAMP_PY,
+                                                   float('nan'), _lib.dp(mu), _lib.dp(s2), None, _lib.dp(dmu), _lib.dp(ds2), None))
+            if self._augdev is not None:
+                mu2 = np.empty(M)
+                _lib.check(_lib.lib.ibo_acq_grad_batch(self._augdev.h, M, _lib.dp(Q), _lib.ACQ_NONE, 0.0, _lib.ERF_NR,
+                                                       _lib.CLAMP_PY, float('nan'), _lib.dp(mu2), _lib.dp(s2), None, None,
+                                                       _lib.dp(ds2), None))
+        if single:
+            return mu[0], s2[0], dmu[0], ds2[0]
+        return mu, s2, dmu, ds2
+
+    def _prior_gradient(self, Q):
+        """the mean prior and its gradient at the rows of Q (zeros without a prior)"""
+        M, D = Q.shape
+        arrs = self._prior_arrays()
+        if arrs is None:
+            return np.zeros(M), np.zeros((M, D))
+        means, beta, theta, lo, wd = arrs
+        U = (Q - lo) / wd
+        diff = U[:, None, :] - means[None, :, :]                       # (M, k, D)
+        be = beta[None, :] * np.exp(-theta * np.sum(diff ** 2, axis=2))  # (M, k)
+        return be.sum(axis=1), np.einsum('mk,mkd->md', be, diff) * (-2.0 * theta) / wd
+
     def posteriors(self, X):
         """arrays of posterior means and variances (:231-244) -- one batched GPU call"""
         if len(self.X) == 0:

@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define IBO_ABI_VERSION 7   /* 2: + ibo_gp_extend, ibo_comm_count; 3: + ibo_pref_*; 4: + ibo_dev_generation; 5: + ibo_sweep_state_info; 6: + ibo_sweep_state_levels;
-                             * 7: + ibo_gpu_time_ms, ibo_acq_sweep_exchange, ibo_direct_server_info; options "super_min_nb", "direct_resident", "direct_idle_ms", "arena_mb" -- ibo_set_option knows the keys listed below and nothing else: the experiment switches of rounds 2-4
+                             * 7: + ibo_gpu_time_ms, ibo_acq_sweep_exchange, ibo_direct_server_info, ibo_acq_grad_batch (added later, without a new version); options "super_min_nb", "direct_resident", "direct_idle_ms", "arena_mb" -- ibo_set_option knows the keys listed below and nothing else: the experiment switches of rounds 2-4
                              * (nlml_groups, cov_fast, chol_fused, small_local, zero_copy, gallery_lazy, pipe_fit, .. -- about 35 keys) were removed in
                              * round 5 and now return IBO_ERR_ARG "unknown option", as does a NULL key; ibo_nlml_grid's covariance pass is the fast one */
 
@@ -259,6 +259,28 @@ int ibo_posterior_batch(ibo_gp_t *gp, int64_t M, const double *Q_host, double cl
  */
 int ibo_acq_batch(ibo_gp_t *gp, int64_t M, const double *Q_host, int acq, double parm, int erf_mode,
                   double clamp_lo, double ymax, double *mu_host, double *s2_host, double *acq_host);
+
+/*
+ * ibo_acq_batch plus the gradients with respect to the query point: dmu_host, ds2_host, dacq_host are M x D row-major,
+ * d/dx_d of mu, of the clipped sigma^2 and of the acquisition at each point.  Any output may be NULL, not all of them.
+ * mu / s2 / acq are ibo_acq_batch's numbers bit for bit.  With acq = IBO_ACQ_NONE only posterior gradients are formed
+ * and dacq_host must be NULL.  Conventions as the sweep: k* with the handle's k* signal variance (ibo_gp_set_kstar_sf2);
+ * mu = m + k*.aY - m k*.a1 (m: the mean prior, if any); sigma^2 = 1 + noise - |W k*|^2 clipped to [clamp_lo, 10].
+ *   dmu   = dm (1 - k*.a1) + sum_i dk*_i (aY_i - m a1_i)
+ *   ds2   = -2 sum_i dk*_i u_i with u = W^T (W k*) = R^-1 k*, and exactly 0 where the clip is active (raw sigma^2 outside
+ *           the open interval (clamp_lo, 10))
+ *   EI    = Phi(z) dmu + phi(z) dsigma;  PI = phi(z) (dmu - z dsigma) / sigma;  UCB = dmu + parm dsigma
+ *           (z = (mu - ymax - parm) / sigma, dsigma = ds2 / (2 sigma); Phi, phi of the erf flavour.  This is the analytic
+ *           gradient: with IBO_ERF_NR, whose constants 0.707106 and 0.398942 are truncated, it differs from the derivative
+ *           of the returned values by about 1e-6 relative.)
+ * Cost per point: 2 N^2 flops (two triangular products) + O(N D).  Sums run in a fixed order: the same call gives the
+ * same bits.  Works for every model the handle can be fitted with (1 <= D <= 64, any N); the scratch is bounded by one
+ * chunk of candidates (192 MiB, or one tile of 64 candidates where that alone is larger: about 290 MiB at 20480 rows).
+ * IBO_ERR_STATE before a fit; IBO_ERR_ARG for M < 1, NULL Q_host, a bad acq or erf_mode, or every output NULL.
+ */
+int ibo_acq_grad_batch(ibo_gp_t *gp, int64_t M, const double *Q_host, int acq, double parm, int erf_mode,
+                       double clamp_lo, double ymax, double *mu_host, double *s2_host, double *acq_host,
+                       double *dmu_host, double *ds2_host, double *dacq_host);
 
 /*
  * Fused candidate sweep: the batched equivalent of M calls of
