@@ -10,6 +10,10 @@ hallucGP.addData(best, mu(best)).  Step (2) is one fused GPU sweep with the
 distance mask applied inside the kernel; `candidates=` swaps the 300-sample
 latin hypercube for any (M, D) array (ndarray or DeviceArray already in HBM)
 and `seed=` makes the default sampling reproducible (the reference is unseeded).
+
+thompsonGallery (an addition to the reference): the one-shot alternative by Thompson
+sampling -- each member is the arg-max of one joint posterior draw over a candidate
+set (GaussianProcess.sample_posterior), under the same distance rule.
 """
 from copy import deepcopy
 
@@ -147,4 +151,23 @@ def fastUCBGallery(GP, bounds, N, useBest=True, samples=300, useCDIRECT=True, ca
         gallery.append(pick)
         model.addData(pick, model.mu(pick))
         rnd += 1
+    return gallery
+
+
+def thompsonGallery(GP, candidates, N, seed=None, draws=None, noise=True):
+    """N points to show a user by Thompson sampling: one call of GP.sample_posterior draws `draws` (default 8 N) joint samples
+    of the posterior over the candidate rows; the draws are walked in order and each one's first maximiser (NaN never wins)
+    joins the gallery when it is farther than MIN_SEPARATION from every member.  Returns a list of candidate rows like
+    fastUCBGallery; it is shorter than N only when the draws run out first.  seed fixes the draws; noise=True draws from the
+    predictive distribution EI / PI / UCB use, noise=False from the latent function."""
+    C = np.atleast_2d(np.asarray(candidates, dtype=float))
+    draws = 8 * int(N) if draws is None else int(draws)
+    F = GP.sample_posterior(C, n=draws, seed=seed, noise=noise)
+    gallery = []
+    for f in F:
+        if len(gallery) >= N:
+            break
+        k = int(np.argmax(np.where(np.isnan(f), -np.inf, f)))
+        if _separated(C[k], gallery):
+            gallery.append(np.array(C[k]))
     return gallery

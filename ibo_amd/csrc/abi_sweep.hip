@@ -2,6 +2,7 @@
 // and DIRECT on the GPU objective.
 #include "abi_internal.h"
 #include "grad.h"
+#include "cov.h"
 
 // 2^(j/2048), j < 2048: the table behind sweep2's exp (one per device, created on first use)
 static std::atomic<double *> g_exp_tab[16];
@@ -516,6 +517,98 @@ extern "C" int ibo_acq_grad_batch(ibo_gp_t *g, int64_t M, const double *Q_host, 
             for (int k = 0; k < 3; k++)
                 if (outs_host[k]) memcpy(outs_host[k], od[k], sizeof(double) * M * D);
     }
+    return IBO_OK;
+}
+
+// ------------------------------------------------------------------------ joint posterior and draws from it (cov.hip)
+// mu: the launch sequence of ibo_posterior_batch (the same numbers, bit for bit)
+static int cov_mean(ibo_gp *g, int64_t M, const double *Q_host, double *mu_host)
+{
+    std::vector<double> s2((size_t)M);
+    return eval_host_points(g, M, Q_host, IBO_ACQ_NONE, 0.0, IBO_ERF_LIBM, 1e-7, mu_host, s2.data(), nullptr);
+}
+
+// Sigma of the M points into S (device, ld lds), diagonal rule diag - |v_a|^2; pad: rows and columns [M, round_up(M, 64)) identity.
+// Scratch: the points, V^T (Mp x Npad) and one chunk of K* (at most 256 MiB, at least 64 points); handed back on every exit path.
+static int cov_sigma(ibo_gp *g, int64_t M, const double *Q_host, double diag, int pad, double *S, size_t lds)
+{
+    const int N = g->N, Np = g->Npad, D = g->D, Mp = round_up((int)M, IBO_COV_TILE);
+    hipStream_t s = g->stream;
+    int mc = (int)((((size_t)256 << 20) / ((size_t)Np * sizeof(double))) / IBO_COV_TILE * IBO_COV_TILE);
+    mc = mc < IBO_COV_TILE ? IBO_COV_TILE : (mc > Mp ? Mp : mc);
+    ScopedBuf<double> q, kt, vt;
+    IBO_TRY(q.ensure((size_t)M * D)); IBO_TRY(kt.ensure((size_t)mc * Np)); IBO_TRY(vt.ensure((size_t)Mp * Np));
+    HIP_TRY(hipMemcpyAsync(q.p, Q_host, sizeof(double) * (size_t)M * D, hipMemcpyHostToDevice, s));
+    for (int c0 = 0; c0 < Mp; c0 += mc) {
+        const int mp = Mp - c0 < mc ? Mp - c0 : mc;
+        const int m = (int)(M - c0 < mp ? M - c0 : mp);           // >= 1: c0 <= Mp - 64 < M
+        KERNEL_TRY(launch_cov_kstar(g->kp, g->Xp.p, N, Np, g->DP, q.p + (size_t)c0 * D, m, mp, kt.p, s));
+        KERNEL_TRY(launch_cov_tri(kt.p, (size_t)Np, g->W.p, (size_t)Np, N, mp, Np, vt.p + (size_t)c0 * Np, (size_t)Np, s));
+    }
+    KERNEL_TRY(launch_cov_syrk(g->kp, q.p, vt.p, (size_t)Np, round_up(N, 32), (int)M, Mp, diag, pad, S, lds, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return IBO_OK;
+}
+
+extern "C" int ibo_posterior_cov(ibo_gp_t *g, int64_t M, const double *Q_host, int with_noise, double *mu_host, double *S_host)
+{
+    IBO_TRY(use_device(g ? g->device : 0));
+    if (!g || !Q_host || !S_host) return fail(IBO_ERR_ARG, "NULL argument");
+    if (M < 1 || M > IBO_COV_MAX_M) return fail(IBO_ERR_ARG, "M=%lld outside [1, %d]", (long long)M, IBO_COV_MAX_M);
+    if (!g->fitted) return fail(IBO_ERR_STATE, "posterior covariance before a successful fit");
+    if (mu_host) IBO_TRY(cov_mean(g, M, Q_host, mu_host));
+    hipStream_t s = g->stream;
+    ScopedBuf<double> S;
+    IBO_TRY(S.ensure((size_t)M * M));
+    HIP_TRY(hipEventRecord(g->ev0, s));
+    IBO_TRY(cov_sigma(g, M, Q_host, with_noise ? 1.0 + g->noise : 1.0, 0, S.p, (size_t)M));
+    HIP_TRY(hipMemcpyAsync(S_host, S.p, sizeof(double) * (size_t)M * M, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(g->ev1, s));
+    HIP_TRY(hipEventSynchronize(g->ev1));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, g->ev0, g->ev1));
+    gpu_time_add(g->device, ms);
+    return IBO_OK;
+}
+
+// Sigma + jitter I padded to Mp = round_up(M, 64) rows (identity pad), factored in place by ibo_spd_*'s route, then F = Z L^T on the
+// MFMA pipe.  Sigma never leaves the device.
+extern "C" int ibo_posterior_sample(ibo_gp_t *g, int64_t M, const double *Q_host, int with_noise, double jitter, int nsamp,
+                                    const double *Z_host, double *F_host, double *mu_host, int *info)
+{
+    IBO_TRY(use_device(g ? g->device : 0));
+    if (!g || !Q_host || !Z_host || !F_host) return fail(IBO_ERR_ARG, "NULL argument");
+    if (M < 1 || M > IBO_SAMPLE_MAX_M) return fail(IBO_ERR_ARG, "M=%lld outside [1, %d]", (long long)M, IBO_SAMPLE_MAX_M);
+    if (nsamp < 1 || nsamp > IBO_SAMPLE_MAX_DRAWS) return fail(IBO_ERR_ARG, "nsamp=%d outside [1, %d]", nsamp, IBO_SAMPLE_MAX_DRAWS);
+    if (!(jitter >= 0.0 && jitter < HUGE_VAL)) return fail(IBO_ERR_ARG, "jitter=%g is not a finite value >= 0", jitter);
+    if (!g->fitted) return fail(IBO_ERR_STATE, "posterior draws before a successful fit");
+    if (info) *info = 0;
+    if (mu_host) IBO_TRY(cov_mean(g, M, Q_host, mu_host));
+    hipStream_t s = g->stream;
+    const int Mp = round_up((int)M, IBO_COV_TILE), Sp = round_up(nsamp, IBO_COV_TILE);
+    ScopedBuf<double> S, d64, Z, F;
+    ScopedBuf<int> dinfo;
+    IBO_TRY(S.ensure((size_t)Mp * Mp)); IBO_TRY(d64.ensure((size_t)(Mp / 64) * 4096)); IBO_TRY(dinfo.ensure(1));
+    IBO_TRY(Z.ensure((size_t)Sp * Mp)); IBO_TRY(F.ensure((size_t)Sp * Mp));
+    HIP_TRY(hipEventRecord(g->ev0, s));
+    IBO_TRY(cov_sigma(g, M, Q_host, (with_noise ? 1.0 + g->noise : 1.0) + jitter, 1, S.p, (size_t)Mp));
+    KERNEL_TRY(launch_cholesky(S.p, Mp, d64.p, dinfo.p, s));
+    int h = 0;
+    HIP_TRY(hipMemcpyAsync(&h, dinfo.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h != 0) {
+        if (info) *info = h;
+        return fail(IBO_ERR_NOT_PD, "posterior covariance + %g I is not positive definite (pivot %d)", jitter, h);
+    }
+    HIP_TRY(hipMemsetAsync(Z.p, 0, sizeof(double) * (size_t)Sp * Mp, s));
+    HIP_TRY(hipMemcpy2DAsync(Z.p, sizeof(double) * Mp, Z_host, sizeof(double) * M, sizeof(double) * M, nsamp, hipMemcpyHostToDevice, s));
+    KERNEL_TRY(launch_cov_tri(Z.p, (size_t)Mp, S.p, (size_t)Mp, (int)M, Sp, Mp, F.p, (size_t)Mp, s));
+    HIP_TRY(hipMemcpy2DAsync(F_host, sizeof(double) * M, F.p, sizeof(double) * Mp, sizeof(double) * M, nsamp, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(g->ev1, s));
+    HIP_TRY(hipEventSynchronize(g->ev1));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, g->ev0, g->ev1));
+    gpu_time_add(g->device, ms);
     return IBO_OK;
 }
 

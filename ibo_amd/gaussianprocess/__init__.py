@@ -294,6 +294,62 @@ class GaussianProcess(object):
             return mu[0], s2[0], dmu[0], ds2[0]
         return mu, s2, dmu, ds2
 
+    def posterior_cov(self, X, noise=True):
+        """(mu (M,), Sigma (M, M)): the joint posterior at the points X ((M, D) or (D,)) (ibo_posterior_cov).  mu is what
+        `posteriors` returns; Sigma_ab = k(x_a, x_b) - v_a.v_b with v = L^-1 k*, its diagonal 1 + noise - |v_a|^2 (the variance
+        of `posteriors` before its clamp) or, with noise=False, 1 - |v_a|^2 (the latent function's).  Unclipped and exactly
+        symmetric.  With an augmented factor in force (addObservationPoint) Sigma comes from it, mu from the model.  An empty
+        model gives the prior's mean (0 without a prior) and K(X, X) with a unit diagonal."""
+        Q = _lib.f64(np.atleast_2d(np.asarray(X, dtype=float)))
+        M, D = Q.shape
+        S = np.empty((M, M))
+        if len(self.X) == 0:
+            ktype, hyper, sf2, _ = self.kernel._ibo_spec()
+            dev = _lib.default_device() if self._device is None else self._device
+            _lib.check(_lib.lib.ibo_cov_matrix(dev, ktype, D, _lib.dp(hyper), len(hyper), sf2, M, _lib.dp(Q), 0, None,
+                                               _lib.DIAG_UNIT_PLUS_NOISE, 0.0, _lib.dp(S)))
+            return self._prior_gradient(Q)[0], S
+        self._push_prior()
+        mu = np.empty(M)
+        if self._augdev is None:
+            _lib.check(_lib.lib.ibo_posterior_cov(self._handle(), M, _lib.dp(Q), int(bool(noise)), _lib.dp(mu), _lib.dp(S)))
+        else:
+            mu = self._posterior_arrays(Q, False)[0]
+            _lib.check(_lib.lib.ibo_posterior_cov(self._augdev.h, M, _lib.dp(Q), int(bool(noise)), None, _lib.dp(S)))
+        return mu, S
+
+    def sample_posterior(self, X, n=1, seed=None, noise=True):
+        """(n, M): n joint draws of the posterior at the points X ((M, D) or (D,)), mu + L_S z with S the covariance of
+        `posterior_cov` (factored on the device, ibo_posterior_sample) and z from np.random.default_rng(seed): the same seed gives
+        the same draws.  A covariance that does not factor is retried with sf2 * (1e-12, 1e-10, 1e-8, 1e-6) on its diagonal, then
+        numpy.linalg.LinAlgError.  An empty model raises ValueError."""
+        if len(self.X) == 0:
+            raise ValueError("sample_posterior needs a model with data")
+        Q = _lib.f64(np.atleast_2d(np.asarray(X, dtype=float)))
+        M = len(Q)
+        n = int(n)
+        Z = _lib.f64(np.random.default_rng(seed).standard_normal((n, M)))
+        F = np.empty((n, M))
+        self._push_prior()
+        if self._augdev is None:
+            h, mu = self._handle(), np.empty(M)
+        else:
+            h, mu = self._augdev.h, self._posterior_arrays(Q, False)[0]
+        sf2 = self.kernel._ibo_spec()[2]
+        info = ctypes.c_int(0)
+        first = self._augdev is None
+        for jitter in (0.0, sf2 * 1e-12, sf2 * 1e-10, sf2 * 1e-8, sf2 * 1e-6):
+            rc = _lib.lib.ibo_posterior_sample(h, M, _lib.dp(Q), int(bool(noise)), jitter, n, _lib.dp(Z), _lib.dp(F),
+                                               _lib.dp(mu) if first else None, ctypes.byref(info))
+            if rc == _lib.OK:
+                return mu[None, :] + F
+            if rc != _lib.ERR_NOT_PD:
+                _lib.check(rc)
+            if first:
+                mu = self._posterior_arrays(Q, False)[0]
+                first = False
+        raise LinAlgError("posterior covariance is not positive definite (info %d, jitter up to %g)" % (info.value, jitter))
+
     def _prior_gradient(self, Q):
         """the mean prior and its gradient at the rows of Q (zeros without a prior)"""
         M, D = Q.shape

@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define IBO_ABI_VERSION 7   /* 2: + ibo_gp_extend, ibo_comm_count; 3: + ibo_pref_*; 4: + ibo_dev_generation; 5: + ibo_sweep_state_info; 6: + ibo_sweep_state_levels;
-                             * 7: + ibo_gpu_time_ms, ibo_acq_sweep_exchange, ibo_direct_server_info, ibo_acq_grad_batch (added later, without a new version); options "super_min_nb", "direct_resident", "direct_idle_ms", "arena_mb" -- ibo_set_option knows the keys listed below and nothing else: the experiment switches of rounds 2-4
+                             * 7: + ibo_gpu_time_ms, ibo_acq_sweep_exchange, ibo_direct_server_info, ibo_acq_grad_batch, ibo_posterior_cov, ibo_posterior_sample (added later, without a new version); options "super_min_nb", "direct_resident", "direct_idle_ms", "arena_mb" -- ibo_set_option knows the keys listed below and nothing else: the experiment switches of rounds 2-4
                              * (nlml_groups, cov_fast, chol_fused, small_local, zero_copy, gallery_lazy, pipe_fit, .. -- about 35 keys) were removed in
                              * round 5 and now return IBO_ERR_ARG "unknown option", as does a NULL key; ibo_nlml_grid's covariance pass is the fast one */
 
@@ -281,6 +281,41 @@ int ibo_acq_batch(ibo_gp_t *gp, int64_t M, const double *Q_host, int acq, double
 int ibo_acq_grad_batch(ibo_gp_t *gp, int64_t M, const double *Q_host, int acq, double parm, int erf_mode,
                        double clamp_lo, double ymax, double *mu_host, double *s2_host, double *acq_host,
                        double *dmu_host, double *ds2_host, double *dacq_host);
+
+/*
+ * The joint posterior of M query points Q (M x D row-major): S_host (M x M row-major) receives
+ *   S_ab = k(q_a, q_b) - v_a.v_b  (a != b),   S_aa = 1 + noise - |v_a|^2 (with_noise = 1) or 1 - |v_a|^2 (with_noise = 0),
+ * v_a = W k*(q_a), W = L^-1 as the handle holds it (a preference GP: its own factor of R + C^-1), k and k* with the handle's
+ * k* signal variance (ibo_gp_set_kstar_sf2).  That is the Schur complement of the fitted matrix extended by the query rows:
+ * diag(S) with with_noise = 1 is ibo_posterior_batch's s2 before its clip, and observing q_b turns the variance at q_a into
+ * S_aa - S_ab^2 / S_bb.  S is unclipped and exactly symmetric (the lower 64 x 64 tiles are formed and mirrored).
+ * mu_host (M, may be NULL) receives ibo_posterior_batch's mean, bit for bit (its launches run first).
+ * Cost: N^2 M flops for V = W K* (W's blocks above the diagonal skipped) + N M^2 for the lower half of V^T V, on the fp64 MFMA
+ * pipe, in a fixed order: the same call gives the same bits.  Device scratch: M^2 + M Npad doubles + one chunk of K* (256 MiB
+ * at most), returned to the pool before the call returns.
+ * 1 <= M <= IBO_COV_MAX_M (S is 2^31 bytes there).  IBO_ERR_NO_DEVICE without a device (checked first); IBO_ERR_ARG for M
+ * outside the limit or a NULL gp, Q_host or S_host; IBO_ERR_STATE before a fit.
+ */
+#define IBO_COV_MAX_M 16384
+int ibo_posterior_cov(ibo_gp_t *gp, int64_t M, const double *Q_host, int with_noise,
+                      double *mu_host, double *S_host);
+
+/*
+ * nsamp zero-mean draws from the joint posterior of ibo_posterior_cov: S + jitter I is formed on the device (with the identity
+ * padding of the in-place factorisation) and factored there, S + jitter I = L_S L_S^T (the route of ibo_spd_*: panel 1 up to
+ * 2048 rows, panels of four beyond), and F_host (nsamp x M row-major) receives F[s] = L_S Z[s] for the rows Z[s] of Z_host
+ * (nsamp x M row-major).  S never reaches the host; the mean is not added (mu_host, M and optional, receives it as
+ * ibo_posterior_cov does), so a caller may take it from another handle.  Cost: ibo_posterior_cov's + M^3 / 3 for the
+ * factorisation + M^2 nsamp for the product.  Device scratch: Mp^2 + 2 nsamp_p Mp doubles (Mp, nsamp_p: rounded up to 64) on
+ * top of ibo_posterior_cov's, without its M^2.
+ * IBO_ERR_NOT_PD when the factorisation fails: *info (optional) the 1-based failing pivot, as dpotrf's info (0 otherwise).
+ * 1 <= M <= IBO_SAMPLE_MAX_M, 1 <= nsamp <= IBO_SAMPLE_MAX_DRAWS, jitter finite and >= 0: IBO_ERR_ARG otherwise, and for a
+ * NULL gp, Q_host, Z_host or F_host.  IBO_ERR_NO_DEVICE without a device (checked first); IBO_ERR_STATE before a fit.
+ */
+#define IBO_SAMPLE_MAX_M 16384
+#define IBO_SAMPLE_MAX_DRAWS 4096
+int ibo_posterior_sample(ibo_gp_t *gp, int64_t M, const double *Q_host, int with_noise, double jitter,
+                         int nsamp, const double *Z_host, double *F_host, double *mu_host, int *info);
 
 /*
  * Fused candidate sweep: the batched equivalent of M calls of
