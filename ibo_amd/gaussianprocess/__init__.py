@@ -526,13 +526,23 @@ class PrefGaussianProcess(GaussianProcess):
             _lib.check(_lib.lib.ibo_pref_newton_step(h, len(lin), lin.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _lib.dp(val),
                                                      _lib.dp(gc), _lib.dp(delta), _lib.dp(Rdelta), ctypes.byref(info)))
             step = 1.0
+            gd = g.dot(delta)
+            # S is a sum of len(w) + N non-negative terms, which NumPy adds pairwise: each value of S carries a rounding error of
+            # about log2(len(w) + N) u |S| < 16 u |S|, the difference of two values twice that.  Below 64 u |S| (twice that again) the
+            # predicted decrease |g.delta| is smaller than what the Armijo comparison can resolve and its outcome is rounding noise:
+            # halving on it would shrink the step to nothing and repeat that until maxit.  So close to the minimum (the Newton
+            # decrement -g.delta / 2 estimates S - min S) the full Newton step is taken unjudged, and the loop ends when such a
+            # step no longer lowers |g|: the gradient itself has then reached its rounding.
+            blind = -gd <= 64 * np.finfo(float).eps * max(abs(S), 1.0)
             while True:
                 Sn, gn, rn = self._S_terms(y + step * delta, Ry + step * Rdelta, v, u, w)
-                if np.isfinite(Sn) and Sn <= S + 1e-4 * step * g.dot(delta):
+                if np.isfinite(Sn) and (blind or Sn <= S + 1e-4 * step * gd):
                     break
                 step *= 0.5
                 if step < 1e-10:
                     return y
+            if blind and not np.max(np.abs(gn)) < np.max(np.abs(g)):
+                break
             y = y + step * delta
             Ry = Ry + step * Rdelta
             S, g, rho = Sn, gn, rn
@@ -632,8 +642,13 @@ class PrefGaussianProcess(GaussianProcess):
         import ctypes
         if not plain_fitted:                         # (addPreferences has done this before its Newton steps)
             _lib.check(_lib.lib.ibo_pref_begin(self._handle()))
-        lin, val = self._pair_sum_entries(n, pv, pu, w)
         info = ctypes.c_int(0)
+        if np.any(w < 0):
+            # a violated preference at small noise: pdf and cdf both sit on their floors, w = (1 + d) / (2 noise) < 0 and C need
+            # not be positive definite.  The reference inverts it all the same (LU, :488); ibo_pref_finish inverts through chol(C).
+            self._finish_indefinite(n, pv, pu, w)
+            return
+        lin, val = self._pair_sum_entries(n, pv, pu, w)
         for i in range(11):
             rc = _lib.lib.ibo_pref_finish(self._handle(), len(lin), lin.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _lib.dp(val),
                                           5.0 + i, ctypes.byref(info))
@@ -650,6 +665,47 @@ class PrefGaussianProcess(GaussianProcess):
         self._prior_pushed = False
         self._push_prior()
         self._fit_spec = None
+
+    def _inv_C_indefinite(self, n, pv, pu, w, reg):
+        """C^-1 for a C with negative weights, C = C+ + U D U^T: C+ = (5 + reg) I + the pairs with w >= 0 is positive definite and
+        inverted on the device; the k pairs with w < 0 (U's columns are e_v - e_u, D = diag(w-)) come in by Woodbury,
+        C^-1 = C+^-1 - Z (D^-1 + U^T Z)^-1 Z^T with Z = C+^-1 U, whose k x k system is solved on the host (LU: it may be indefinite)"""
+        neg = w < 0
+        Cp = np.eye(n) * (5.0 + reg)
+        v, u, wp = pv[~neg], pu[~neg], w[~neg]
+        np.add.at(Cp, (v, u), -wp); np.add.at(Cp, (u, v), -wp)
+        np.add.at(Cp, (v, v), wp); np.add.at(Cp, (u, u), wp)
+        Cpi = self._inv_spd(Cp)
+        v, u = pv[neg], pu[neg]
+        Z = Cpi[:, v] - Cpi[:, u]
+        K = Z[v, :] - Z[u, :]
+        K[np.diag_indices(len(v))] += 1.0 / w[neg]
+        return Cpi - Z.dot(np.linalg.solve(K, Z.T))
+
+    def _finish_indefinite(self, n, pv, pu, w):
+        """L = chol(R + C^-1) when some weights are negative: an identity is added to C only when R + C^-1 itself does not factor,
+        as in the reference (:488-497).  R and C^-1 cross the bus here (ibo_gp_fit_with_matrix); the usual path keeps them on the
+        device."""
+        R = np.array(self.R)
+        for i in range(11):
+            A = R + self._inv_C_indefinite(n, pv, pu, w, i)
+            try:
+                self._fit_device(A=0.5 * (A + A.T))
+                break
+            except NotPositiveDefinite:
+                print('[addPreferences] GP.C matrix is ill-conditioned, adding regularizer delta = %d' % (i + 1))
+                self.C = None
+                self._C_spec = (n, pv, pu, w, i + 1)
+        else:
+            raise NotPositiveDefinite(_lib.ERR_NOT_PD, "R + C^-1 could not be factored")
+        self._fit_spec = None
+
+    def _inv_C(self):
+        """C^-1 as the reference's linalg.inv(self.C) (:514)"""
+        spec = self._C_spec
+        if spec is not None and np.any(spec[3] < 0):
+            return self._inv_C_indefinite(*spec)
+        return self._inv_spd(self.C)
 
     def addObservationPoint(self, X):
         """add a point to observe at, without its observation (:502-519)"""
@@ -668,7 +724,7 @@ class PrefGaussianProcess(GaussianProcess):
         self.augR = K
         invC = np.zeros_like(K)
         m = self.C.shape[0]
-        invC[:m, :m] = self._inv_spd(self.C)
+        invC[:m, :m] = self._inv_C()
         self.augX = augX
         if self._augdev is None:
             self._augdev = _DeviceGP(self._dev.device)
