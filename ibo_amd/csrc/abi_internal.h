@@ -42,7 +42,6 @@ int ibo_fail(int code, const char *fmt, ...);
 
 // ---- option switches (abi_core.hip: ibo_set_option)
 extern std::atomic<int> g_super_min_nb;        // ibo_set_option("super_min_nb", nb): block columns from which a fit runs in super-panels
-extern std::atomic<int> g_direct_resident, g_direct_idle_ms;      // ibo_set_option("direct_resident", 0/1), ("direct_idle_ms", n)
 extern std::atomic<int> g_host_pipeline, g_fused2_min_nb, g_gallery_prune, g_nlml_batch, g_chol_left, g_dot_override, g_legacy_exact, g_force_path, g_nlml_groups;
 extern std::mutex g_dev_mu[16];             // serialises the per-device workspaces of ibo_nlml_grid / ibo_nlml_grad / ibo_trim
 extern std::atomic<size_t> g_pool_limit;
@@ -133,8 +132,6 @@ struct ibo_gp {
     DevBuf<unsigned> done_count;
     // fits from g_super_min_nb block columns on (launch_cholesky_super): [A ; E] in one tall buffer, the packed store of [L ; E^T-in-progress]
     DevBuf<double> tall, Pk2;
-    DevBuf<unsigned> srv_ctl;       // the resident evaluation server's control words (small2.hip: ServerCtl)
-    int srv_batches = 0; const char *srv_why = "";      // the last ibo_direct_max on this handle: batches the server evaluated; why it did not (all of them)
     // preference GP (ibo_pref_*): R^-1, the matrix being factored and its factors, vectors, sparse terms
     struct PrefWork {
         DevBuf<double> Rinv, A, Lh, E, Et, d64, vec, tmp, val;

@@ -45,7 +45,8 @@ __device__ __forceinline__ double s2_exp(double y, const double *tab)
 
 // acquisition epilogue of one candidate; coordinates are read from global memory where needed (prior,
 // exclusion balls) so that no per-lane coordinate array exists (dynamic indexing would put it in scratch)
-// SYS: the candidate's coordinates lie in host memory that a resident kernel sees change (server.hip): system-scope loads
+// SYS: the host spins on a completion flag instead of waiting for the launch to end (small2.hip: small_finish_kernel<true>):
+// coordinates and results go through system-scope accesses, which leave no L2 line to be written back before the flag
 template <bool SYS = false>
 __device__ __forceinline__ double s2_finish(const SweepArgs &a, const double *xp, double q, double muY, double mu1,
                                             int64_t li, bool valid, bool &excluded)
@@ -75,7 +76,7 @@ __device__ __forceinline__ double s2_finish(const SweepArgs &a, const double *xp
         if (!(sqrt(d2) > a.excl_radius)) excluded = true;
     }
     if (valid) {
-        if (SYS) {                                      // (a resident kernel has no launch boundary to flush its results to host memory)
+        if (SYS) {                                      // (the flag may be seen before the launch ends: no launch boundary flushes these)
             if (a.out_mu) __hip_atomic_store(a.out_mu + li, mu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             if (a.out_s2) __hip_atomic_store(a.out_s2 + li, s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             if (a.out_acq) __hip_atomic_store(a.out_acq + li, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -103,19 +104,18 @@ __device__ __forceinline__ double s2_kstar(double y, double sf2, const double *t
 // TCAND candidates of a tile -> lds_c[cand][KA (+1: odd row stride, conflict-free fragment reads)] = [c~ (D) | 1 | b_c | 0..]  (c~ = c sqrt(w)).  A candidate more than 775
 // length scales from the origin (hence > 450 from every observation: |x~| <= 316 where the dot form is in use) has k* = 0
 // exactly; it is pulled in to that radius, where k* is still 0, so that the exponent stays within what s2_exp's integer
-// arithmetic covers (|y| < 7e5).  Called by the whole workgroup; ends with a barrier.
-template <int FAM, int TCAND, int KA, int NT, bool SYS = false>
-__device__ __forceinline__ void s2_stage_candidates(const SweepArgs &a, int64_t tile0, double *lds_c, const double *cand = nullptr, int64_t Mo = -1)
+// arithmetic covers (|y| < 7e5).  cand: where the candidates are read from (nullptr: a.cand).  Called by the whole workgroup; ends with a barrier.
+template <int FAM, int TCAND, int KA, int NT>
+__device__ __forceinline__ void s2_stage_candidates(const SweepArgs &a, int64_t tile0, double *lds_c, const double *cand = nullptr)
 {
     const int tid = threadIdx.x, D = a.kp.D;
-    const int64_t Mtot = Mo >= 0 ? Mo : a.M;          // (a resident kernel's batches differ in size: the caller says)
+    const int64_t M = a.M;
     if (!cand) cand = a.cand;
     for (int e = tid; e < TCAND * KA; e += NT) {
         const int c = e / KA, col = e - c * KA;
         int64_t gi = tile0 + c;
-        if (gi > Mtot - 1) gi = Mtot - 1;
-        lds_c[c * (KA + 1) + col] = (col < D) ? (SYS ? __hip_atomic_load(cand + gi * D + col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : cand[gi * D + col]) * a.kp.sw[col]
-                                              : (col == D ? 1.0 : 0.0);
+        if (gi > M - 1) gi = M - 1;
+        lds_c[c * (KA + 1) + col] = (col < D) ? cand[gi * D + col] * a.kp.sw[col] : (col == D ? 1.0 : 0.0);
     }
     __syncthreads();
     if (tid < TCAND) {

@@ -10,8 +10,8 @@ from ibo_amd.gaussianprocess import GaussianProcess
 from ibo_amd.gaussianprocess import kernel as K
 from ibo_amd.acquisition import sweep
 
-# FUZZ_OPTS="key=value,key=value": ibo_set_option switches for the whole run (e.g. super_min_nb=32,direct_resident=1: fits from 2048 rows in
-# super-panels, DIRECT's batches on the resident server -- the same oracle, the same bars)
+# FUZZ_OPTS="key=value,key=value": ibo_set_option switches for the whole run (e.g. super_min_nb=32: fits from 2048 rows in
+# super-panels -- the same oracle, the same bars)
 if os.environ.get("FUZZ_OPTS"):
     from ibo_amd import _lib
     for kv in os.environ["FUZZ_OPTS"].split(","):
