@@ -1,6 +1,7 @@
 // abi_fit.hip -- the model side of the C ABI: fit (covariance, factorisation route, W = L^-1, alpha vectors), the block extension,
 // the preference GP's device steps, accessors, ibo_cov_matrix and the ibo_spd_* helpers.
 #include "abi_internal.h"
+#include "loo.h"
 
 int make_kparams(int ktype, int D, const double *hyper, int nhyper, double sf2, KParams *kp)
 {
@@ -525,6 +526,31 @@ extern "C" int ibo_gp_get_W(ibo_gp_t *g, double *W_host)
     if (!g || !W_host) return fail(IBO_ERR_ARG, "NULL argument");
     if (!g->fitted || g->reversed) return fail(IBO_ERR_STATE, "W not available");
     return copy_square(g, g->W.p, g->Npad, W_host);
+}
+// Leave-one-out predictions of a fitted model from what the handle holds: d_i = |column i of W|^2 = (A^-1)_ii, c = aY - m(x_i) a1.
+extern "C" int ibo_gp_loo(ibo_gp_t *g, double *mu_host, double *s2_host, double *nloo_host)
+{
+    if (!g) return fail(IBO_ERR_ARG, "gp is NULL");
+    if (!mu_host && !s2_host && !nloo_host) return fail(IBO_ERR_ARG, "every output is NULL");
+    IBO_TRY(use_device(g->device));
+    if (!g->fitted || g->reversed) return fail(IBO_ERR_STATE, "leave-one-out before a successful fit");
+    const int N = g->N, Np = g->Npad;
+    hipStream_t s = g->stream;
+    ScopedBuf<double> buf;                              // d, mu, s2 (Np each) and the sum
+    IBO_TRY(buf.ensure(3 * (size_t)Np + 1));
+    double *d = buf.p, *mu = d + Np, *s2 = mu + Np, *out = s2 + Np;
+    PriorDev pr;
+    pr.nb = g->nb; pr.theta = g->ptheta; pr.means = g->pmeans.p; pr.beta = g->pbeta.p; pr.lowerb = g->plowerb.p; pr.width = g->pwidth.p;
+    KERNEL_TRY(launch_loo_diag(g->W.p, (size_t)Np, N, d, s));
+    KERNEL_TRY(launch_loo_handle(pr, g->Xp.p, g->DP, g->D, N, g->Y.p, g->alphaY.p, g->alpha1.p, d, mu_host ? mu : nullptr, s2_host ? s2 : nullptr,
+                                 out, s));
+    double v = 0.0;
+    if (mu_host) HIP_TRY(hipMemcpyAsync(mu_host, mu, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+    if (s2_host) HIP_TRY(hipMemcpyAsync(s2_host, s2, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&v, out, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (nloo_host) *nloo_host = v + 0.5 * N * log(2.0 * M_PI);
+    return IBO_OK;
 }
 extern "C" int ibo_gp_info(ibo_gp_t *g, int *N, int *D, int *device, double *max_y)
 {

@@ -1,6 +1,7 @@
 // abi_nlml.hip -- the marginal-likelihood side of the C ABI: the batched theta-grid, one value + gradient, and ibo_trim (which owns
 // their per-device workspaces).
 #include "abi_internal.h"
+#include "loo.h"
 
 // ------------------------------------------------------------------------ marginal-likelihood grid
 struct NlmlWorkspace {
@@ -16,6 +17,7 @@ static NlmlWorkspace g_nlml_ws[16];
 static const int kSyrk3From = 1792;          // rows from which ibo_nlml_grad forms K^-1 = W^T W on the packed-operand kernel (launch_syrk3)
 struct GradWorkspace {
     DevBuf<double> dX, dY, dL, dW, dT, dKi, d64, dal, da1, tmp, dpart, dout, dpiece, tall, Pk2;     // tall, Pk2: the super-panel order's (launch_cholesky_super)
+    DevBuf<double> lpart, lout, lmu;                // ibo_loo_grad: one pass' partial sums, [gradient, value], [mu_-i, s2_-i]
     DevBuf<int> dinfo, dtasks, dsums;
     int plan_Np = 0, ntasks = 0, nsums = 0;         // launch_syrk3's lists on the device, for this Npad
     hipEvent_t t0 = nullptr, t1 = nullptr;          // the evaluation's span on the device (ibo_gpu_time_ms)
@@ -41,6 +43,7 @@ extern "C" int ibo_trim(int device)
     gw.dX.release(); gw.dY.release(); gw.dL.release(); gw.dW.release(); gw.dT.release(); gw.dKi.release(); gw.d64.release();
     gw.dal.release(); gw.da1.release(); gw.tmp.release(); gw.dpart.release(); gw.dout.release(); gw.dinfo.release();
     gw.dpiece.release(); gw.dtasks.release(); gw.dsums.release(); gw.plan_Np = 0; gw.tall.release(); gw.Pk2.release();
+    gw.lpart.release(); gw.lout.release(); gw.lmu.release();
     gw.hostX.clear(); gw.hostY.clear();              // (dX / dY went back to the pool: nothing of this data is on the device any more)
     if (gw.pin) { (void)hipHostFree(gw.pin); gw.pin = nullptr; }
     pool_trim(device);
@@ -193,38 +196,23 @@ extern "C" int ibo_nlml_grid(int device, int ktype, int N, int D, const double *
     return IBO_OK;
 }
 
-// NLML and its gradient w.r.t. the log hyper-parameters for ONE theta: marginalLikelihood(...,
-// computeGradient=True) of ego/gaussianprocess/trainhyper.py:47-75.  modes/dims describe
-// Kernel.derivative(X, h) for h < ngrad (see GradSpec).
-extern "C" int ibo_nlml_grad(int device, int ktype, int N, int D, const double *X, const double *Y,
-                             const double *hyper, int nhyper, double sf2, double noise,
-                             int ngrad, const int *modes, const int *dims, double *nlml_host, double *grad_host)
+// What ibo_nlml_grad and ibo_loo_grad share, on the device's one GradWorkspace (the caller holds its mutex): X and Y resident (compared by
+// content), the covariance matrix, the factorisation with W riding along, alpha, K^-1 = W^T W on the route the size selects -- queued on the
+// null stream behind ws.t0, nothing waited for.  scalars (optional, device): (y . alpha, sum log L_ii).  Kinv: where K^-1's lower 64 x 64 blocks are.
+static int grad_prepare(GradWorkspace &ws, const KParams &kp, int N, int D, const double *X, const double *Y, double noise, double *scalars,
+                        const double **Kinv_out)
 {
-    if (!X || !Y || !hyper || !modes || !dims || !nlml_host || !grad_host || N < 1) return fail(IBO_ERR_ARG, "bad argument");
-    if (ngrad < 1 || ngrad > IBO_GRAD_MAX) return fail(IBO_ERR_ARG, "ngrad=%d unsupported (1..%d)", ngrad, IBO_GRAD_MAX);
-    IBO_TRY(use_device(device));
-    std::lock_guard<std::mutex> lk(g_dev_mu[device & 15]);      // (its workspace too)
-    KParams kp;
-    IBO_TRY(make_kparams(ktype, D, hyper, nhyper, sf2, &kp));
-    GradSpec gs;
-    gs.nh = ngrad;
-    for (int h = 0; h < ngrad; h++) {
-        if (modes[h] < 0 || modes[h] > 4 || dims[h] < 0 || dims[h] >= D) return fail(IBO_ERR_ARG, "bad derivative spec");
-        gs.mode[h] = modes[h]; gs.dim[h] = dims[h];
-    }
     const int Np = round_up(N, 64);
     const size_t nn = (size_t)Np * Np;
-    const int nblk = ((N + 15) / 16) * ((N + 15) / 16);
     // workspace kept between calls (BFGS calls this dozens of times; five N^2 buffers allocated and freed per
     // call cost as much as the arithmetic); ibo_trim() releases it
-    GradWorkspace &ws = g_grad_ws[device & 15];
     DevBuf<double> &dX = ws.dX, &dY = ws.dY, &dL = ws.dL, &dW = ws.dW, &dT = ws.dT, &dKi = ws.dKi, &d64 = ws.d64,
-                   &dal = ws.dal, &da1 = ws.da1, &tmp = ws.tmp, &dpart = ws.dpart, &dout = ws.dout;
+                   &dal = ws.dal, &da1 = ws.da1, &tmp = ws.tmp;
     DevBuf<int> &dinfo = ws.dinfo;
     IBO_TRY(dX.ensure((size_t)N * D)); IBO_TRY(dY.ensure(Np)); IBO_TRY(dL.ensure(nn)); IBO_TRY(dW.ensure(nn));
     IBO_TRY(dT.ensure(nn)); IBO_TRY(dKi.ensure(nn)); IBO_TRY(d64.ensure((size_t)(Np / 64) * 4096));
     IBO_TRY(dal.ensure(Np)); IBO_TRY(da1.ensure(Np)); IBO_TRY(tmp.ensure(2 * (size_t)Np + 2 * (size_t)(Np / 64) * Np + 64));
-    IBO_TRY(dpart.ensure((size_t)ngrad * nblk)); IBO_TRY(dout.ensure(ngrad + 2)); IBO_TRY(dinfo.ensure(1));
+    IBO_TRY(dinfo.ensure(1));
     hipStream_t s = nullptr;
     if (ws.hostX.size() != (size_t)N * D || memcmp(ws.hostX.data(), X, sizeof(double) * N * D) != 0) {
         ws.hostX.clear();                            // (not valid while the copy is in flight or if it fails)
@@ -268,7 +256,7 @@ extern "C" int ibo_nlml_grad(int device, int ktype, int N, int D, const double *
     KERNEL_TRY(launch_alpha(dW.p, N, Np, dY.p, tmp.p, dal.p, da1.p, s));
     // K^-1 = W^T W: with the ride-along, W^T is what the factorisation left in dKi -- no transpose; the result goes to dT, free by now
     const double *Kinv = fused ? dT.p : dKi.p;
-    KERNEL_TRY(launch_nlml_scalars(dL.p, Np, N, dY.p, dal.p, dout.p + ngrad, s));        // (y . alpha, sum log L_ii): L has been read for the last time
+    if (scalars) KERNEL_TRY(launch_nlml_scalars(dL.p, Np, N, dY.p, dal.p, scalars, s));        // (y . alpha, sum log L_ii): L has been read for the last time
     if (fused && Np >= kSyrk3From) {
         // from 1792 rows the product runs on the packed-operand kernel (128 x 128 tiles, A fragments straight from L2), its long K ranges in pieces
         // of 256 columns below 2560 rows, 512 below 4096, 1024 from there (measured: 0.692 -> 0.668 ms per evaluation at N = 1792, 0.809 -> 0.766 at
@@ -286,6 +274,38 @@ extern "C" int ibo_nlml_grad(int device, int ktype, int N, int D, const double *
         KERNEL_TRY(launch_syrk3(dKi.p, dL.p, dT.p, Np, ws.dtasks.p, ws.ntasks, ws.dsums.p, ws.nsums, ws.dpiece.p, s));
     } else if (fused) KERNEL_TRY(launch_wtw(dW.p, dKi.p, dT.p, Np, s, 1, 1));
     else KERNEL_TRY(launch_wtw(dW.p, dT.p, dKi.p, Np, s, 1));
+    *Kinv_out = Kinv;
+    return IBO_OK;
+}
+
+// NLML and its gradient w.r.t. the log hyper-parameters for ONE theta: marginalLikelihood(...,
+// computeGradient=True) of ego/gaussianprocess/trainhyper.py:47-75.  modes/dims describe
+// Kernel.derivative(X, h) for h < ngrad (see GradSpec).
+extern "C" int ibo_nlml_grad(int device, int ktype, int N, int D, const double *X, const double *Y,
+                             const double *hyper, int nhyper, double sf2, double noise,
+                             int ngrad, const int *modes, const int *dims, double *nlml_host, double *grad_host)
+{
+    if (!X || !Y || !hyper || !modes || !dims || !nlml_host || !grad_host || N < 1) return fail(IBO_ERR_ARG, "bad argument");
+    if (ngrad < 1 || ngrad > IBO_GRAD_MAX) return fail(IBO_ERR_ARG, "ngrad=%d unsupported (1..%d)", ngrad, IBO_GRAD_MAX);
+    IBO_TRY(use_device(device));
+    std::lock_guard<std::mutex> lk(g_dev_mu[device & 15]);      // (its workspace too)
+    KParams kp;
+    IBO_TRY(make_kparams(ktype, D, hyper, nhyper, sf2, &kp));
+    GradSpec gs;
+    gs.nh = ngrad;
+    for (int h = 0; h < ngrad; h++) {
+        if (modes[h] < 0 || modes[h] > 4 || dims[h] < 0 || dims[h] >= D) return fail(IBO_ERR_ARG, "bad derivative spec");
+        gs.mode[h] = modes[h]; gs.dim[h] = dims[h];
+    }
+    const int Np = round_up(N, 64);
+    const int nblk = ((N + 15) / 16) * ((N + 15) / 16);
+    GradWorkspace &ws = g_grad_ws[device & 15];
+    DevBuf<double> &dX = ws.dX, &dal = ws.dal, &dpart = ws.dpart, &dout = ws.dout;
+    DevBuf<int> &dinfo = ws.dinfo;
+    IBO_TRY(dpart.ensure((size_t)ngrad * nblk)); IBO_TRY(dout.ensure(ngrad + 2));
+    hipStream_t s = nullptr;
+    const double *Kinv = nullptr;
+    IBO_TRY(grad_prepare(ws, kp, N, D, X, Y, noise, dout.p + ngrad, &Kinv));
     KERNEL_TRY(launch_nlml_grad(kp, gs, N, dX.p, D, Kinv, Np, dal.p, dpart.p, dout.p, s));
     HIP_TRY(hipEventRecord(ws.t1, s));
     HIP_TRY(hipMemcpyAsync(ws.pin, dout.p, sizeof(double) * (ngrad + 2), hipMemcpyDeviceToHost, s));
@@ -301,3 +321,47 @@ extern "C" int ibo_nlml_grad(int device, int ktype, int N, int D, const double *
     return IBO_OK;
 }
 
+
+// The leave-one-out objective (Rasmussen & Williams 5.4.2, to be minimised like the NLML), its gradient w.r.t. the log hyper-parameters and the
+// leave-one-out predictions for ONE theta: ibo_nlml_grad's sequence up to K^-1 on its workspace, then loo.hip.
+extern "C" int ibo_loo_grad(int device, int ktype, int N, int D, const double *X, const double *Y,
+                            const double *hyper, int nhyper, double sf2, double noise,
+                            int ngrad, const int *modes, const int *dims, double *nloo_host, double *grad_host, double *mu_host, double *s2_host)
+{
+    if (!X || !Y || !hyper || !nloo_host || N < 1) return fail(IBO_ERR_ARG, "bad argument");
+    if (grad_host && (!modes || !dims)) return fail(IBO_ERR_ARG, "bad argument");
+    if (grad_host && (ngrad < 1 || ngrad > IBO_GRAD_MAX)) return fail(IBO_ERR_ARG, "ngrad=%d unsupported (1..%d)", ngrad, IBO_GRAD_MAX);
+    IBO_TRY(use_device(device));
+    std::lock_guard<std::mutex> lk(g_dev_mu[device & 15]);      // (ibo_nlml_grad's workspace)
+    KParams kp;
+    IBO_TRY(make_kparams(ktype, D, hyper, nhyper, sf2, &kp));
+    GradSpec gs;
+    gs.nh = grad_host ? ngrad : 0;
+    for (int h = 0; h < gs.nh; h++) {
+        if (modes[h] < 0 || modes[h] > 4 || dims[h] < 0 || dims[h] >= D) return fail(IBO_ERR_ARG, "bad derivative spec");
+        gs.mode[h] = modes[h]; gs.dim[h] = dims[h];
+    }
+    const int Np = round_up(N, 64);
+    GradWorkspace &ws = g_grad_ws[device & 15];
+    IBO_TRY(ws.lout.ensure(IBO_GRAD_MAX + 1)); IBO_TRY(ws.lmu.ensure(2 * (size_t)Np));
+    if (gs.nh) IBO_TRY(ws.lpart.ensure(loo_contract_scratch(Np)));
+    hipStream_t s = nullptr;
+    const double *Kinv = nullptr;
+    IBO_TRY(grad_prepare(ws, kp, N, D, X, Y, noise, nullptr, &Kinv));
+    double *dmu = ws.lmu.p, *ds2 = ws.lmu.p + Np;
+    KERNEL_TRY(launch_loo_value(Kinv, (size_t)Np, N, ws.dY.p, ws.dal.p, mu_host ? dmu : nullptr, s2_host ? ds2 : nullptr, ws.lout.p + IBO_GRAD_MAX, s));
+    if (gs.nh) KERNEL_TRY(launch_loo_contract(kp, gs, N, Np, ws.dX.p, D, Kinv, ws.dal.p, ws.lpart.p, ws.lout.p, s));
+    HIP_TRY(hipEventRecord(ws.t1, s));
+    HIP_TRY(hipMemcpyAsync(ws.pin, ws.lout.p, sizeof(double) * (IBO_GRAD_MAX + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ws.pin + IBO_GRAD_MAX + 2, ws.dinfo.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    int h = 0;
+    memcpy(&h, ws.pin + IBO_GRAD_MAX + 2, sizeof(int));
+    { float ms = 0.f; if (hipEventElapsedTime(&ms, ws.t0, ws.t1) == hipSuccess) gpu_time_add(device, ms); }
+    if (h != 0) return fail(IBO_ERR_NOT_PD, "covariance matrix is not positive definite (pivot %d)", h);
+    if (mu_host) HIP_TRY(hipMemcpy(mu_host, dmu, sizeof(double) * N, hipMemcpyDeviceToHost));
+    if (s2_host) HIP_TRY(hipMemcpy(s2_host, ds2, sizeof(double) * N, hipMemcpyDeviceToHost));
+    for (int i = 0; i < gs.nh; i++) grad_host[i] = ws.pin[i];
+    *nloo_host = ws.pin[IBO_GRAD_MAX] + 0.5 * N * log(2.0 * M_PI);
+    return IBO_OK;
+}

@@ -318,6 +318,31 @@ class GaussianProcess(object):
             _lib.check(_lib.lib.ibo_posterior_cov(self._augdev.h, M, _lib.dp(Q), int(bool(noise)), None, _lib.dp(S)))
         return mu, S
 
+    def _loo(self, want_pred, want_score):
+        if len(self.X) == 0:
+            raise ValueError("leave-one-out predictions need at least one observation")
+        self._push_prior()
+        N = len(self.X)
+        mu = np.empty(N) if want_pred else None
+        s2 = np.empty(N) if want_pred else None
+        v = ctypes.c_double()
+        _lib.check(_lib.lib.ibo_gp_loo(self._handle(), _lib.dp(mu) if want_pred else None, _lib.dp(s2) if want_pred else None,
+                                       ctypes.byref(v) if want_score else None))
+        return mu, s2, v.value
+
+    def loo(self):
+        """(mu, s2): the leave-one-out predictions of the fitted model at its own points (ibo_gp_loo) -- mu[i], s2[i] are what
+        `posterior(X[i])` of the model fitted WITHOUT observation i gives, before its clamp to [1e-7, 10] (s2 includes the
+        noise).  O(N^2) from the factor the handle holds: mu_-i = Y_i - c_i / d_i, s2_-i = 1 / d_i with d = diag(A^-1) and
+        c = A^-1 (Y - m(x_i)), A the matrix the model factored."""
+        mu, s2, _ = self._loo(True, False)
+        return mu, s2
+
+    def loo_score(self):
+        """the leave-one-out objective sum_i [log(s2_-i) / 2 + (Y_i - mu_-i)^2 / (2 s2_-i) + log(2 pi) / 2] (the negative log
+        predictive probability of Rasmussen & Williams 5.4.2): smaller is better, like trainhyper.nlml"""
+        return self._loo(False, True)[2]
+
     def sample_posterior(self, X, n=1, seed=None, noise=True):
         """(n, M): n joint draws of the posterior at the points X ((M, D) or (D,)), mu + L_S z with S the covariance of
         `posterior_cov` (factored on the device, ibo_posterior_sample) and z from np.random.default_rng(seed): the same seed gives
@@ -706,6 +731,12 @@ class PrefGaussianProcess(GaussianProcess):
         if spec is not None and np.any(spec[3] < 0):
             return self._inv_C_indefinite(*spec)
         return self._inv_spd(self.C)
+
+    def loo(self):
+        raise NotImplementedError("the preference GP's targets are latent MAP values, not observations: no leave-one-out")
+
+    def loo_score(self):
+        raise NotImplementedError("the preference GP's targets are latent MAP values, not observations: no leave-one-out")
 
     def addObservationPoint(self, X):
         """add a point to observe at, without its observation (:502-519)"""

@@ -4,11 +4,14 @@ Marginal likelihood of the GP hyper-parameters (ego/gaussianprocess/trainhyper.p
     marginalLikelihood(kernel, X, Y, nhyper, computeGradient=True, useCholesky=True, noise=1e-3)
     nlml(loghyper, Kernel, X, Y)     dnlml(loghyper, Kernel, X, Y)     nlmlMulti(...)
     nlml_grid(KernelClass, thetas, X, Y, noise=1e-3)      <- new: a whole theta grid in one call
+    looLikelihood(kernel, X, Y, nhyper, computeGradient=True, noise=1e-3, predictions=False)      <- new: the leave-one-out objective
+    nloo(loghyper, Kernel, X, Y, noise=1e-3)     dnloo(loghyper, Kernel, X, Y, noise=1e-3)
 
 The value (K assembly, Cholesky, L^-1 Y, log det) is computed on the GPU by
 ibo_nlml_grid; value + gradient for one theta by ibo_nlml_grad (K^-1 = W^T W from the device
 factorisation, then one fused kernel contracts K^-1 - alpha alpha^T with every dK/dtheta_i,
-recomputed from X on the fly).
+recomputed from X on the fly).  The leave-one-out objective (Rasmussen & Williams 5.4.2), its gradient and the leave-one-out
+predictions come from ibo_loo_grad: the same sequence up to K^-1, then T = K^-1 dK/dtheta_i on the MFMA unit.
 """
 import numpy as np
 from numpy.linalg import LinAlgError
@@ -118,3 +121,71 @@ def nlmlMulti(loghyper, kernel, X, Y, *args):
 
 def dnlml(loghyper, kernel, X, Y):
     return _value_and_grad(loghyper, kernel, X, Y)[1]
+
+
+# ---------------------------------------------------------------------------------------- leave-one-out cross-validation
+def looLikelihood(kernel, X, Y, nhyper, computeGradient=True, noise=1e-3, predictions=False):
+    """the leave-one-out objective  sum_i [log(s2_-i) / 2 + (Y_i - mu_-i)^2 / (2 s2_-i) + log(2 pi) / 2]  of K = covMatrix + noise I
+    (to be minimised, like marginalLikelihood) and, with computeGradient, its partial derivatives w.r.t. each log hyper-parameter:
+    `value` or `(value, grad)`.  predictions=True appends (mu_-i, s2_-i), the leave-one-out predictions at this theta, as a
+    last element.  LinAlgError when K is not positive definite."""
+    import ctypes
+    assert len(X) == len(Y)
+    Xa = _lib.rows(X); Ya = _lib.f64(Y)
+    N, D = Xa.shape
+    ktype, hyper, sf2, _ = kernel._ibo_spec()
+    modes = dims = None
+    g = None
+    if computeGradient:
+        spec = kernel._ibo_grad_spec(D)[:nhyper]
+        if len(spec) < nhyper:
+            raise ValueError("kernel has %d hyperparameters, %d gradients requested" % (len(spec), nhyper))
+        modes = (ctypes.c_int * nhyper)(*[m for m, _ in spec])
+        dims = (ctypes.c_int * nhyper)(*[d for _, d in spec])
+        g = np.empty(nhyper)
+    mu = np.empty(N) if predictions else None
+    s2 = np.empty(N) if predictions else None
+    v = ctypes.c_double()
+    try:
+        _lib.check(_lib.lib.ibo_loo_grad(_lib.default_device(), ktype, N, D, _lib.dp(Xa), _lib.dp(Ya), _lib.dp(hyper), len(hyper), sf2,
+                                         float(noise), nhyper if computeGradient else 0, modes, dims, ctypes.byref(v),
+                                         _lib.dp(g) if computeGradient else None, _lib.dp(mu) if predictions else None,
+                                         _lib.dp(s2) if predictions else None))
+    except _lib.NotPositiveDefinite:
+        raise LinAlgError("covariance matrix is not positive definite for hyperparameters %s" % (kernel.hyperparams,))
+    out = (v.value, g) if computeGradient else (v.value,)
+    if predictions:
+        out = out + ((mu, s2),)
+    return out if len(out) > 1 else out[0]
+
+
+_last_loo = {"key": None, "value": None, "grad": None}      # (as _last: f(x) and f'(x) at one x cost one device call)
+
+
+def _loo_value_and_grad(loghyper, kernel, X, Y, noise=1e-3):
+    loghyper = np.asarray(loghyper, dtype=float)
+    import hashlib
+    dig = hashlib.blake2b(_lib.rows(X).tobytes(), digest_size=16)
+    dig.update(_lib.f64(Y).tobytes())
+    key = (loghyper.tobytes(), kernel, dig.digest(), float(noise))
+    if _last_loo["key"] != key:
+        k = kernel(np.exp(loghyper))
+        _last_loo["key"] = None
+        _last_loo["value"], _last_loo["grad"] = looLikelihood(k, X, Y, len(loghyper), computeGradient=True, noise=noise)
+        _last_loo["key"] = key
+    return _last_loo["value"], _last_loo["grad"]
+
+
+def nloo(loghyper, kernel, X, Y, noise=1e-3):
+    """the leave-one-out objective as a function of LOG hyper-parameters, for fmin_bfgs; 100 when not PD (as nlml)"""
+    try:
+        v = _loo_value_and_grad(loghyper, kernel, X, Y, noise)[0]
+    except LinAlgError as e:
+        print(e)
+        v = 100
+        print('returning nloo = 100')
+    return v
+
+
+def dnloo(loghyper, kernel, X, Y, noise=1e-3):
+    return _loo_value_and_grad(loghyper, kernel, X, Y, noise)[1]

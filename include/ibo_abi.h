@@ -39,7 +39,8 @@ extern "C" {
                              * (nlml_groups, cov_fast, chol_fused, small_local, zero_copy, gallery_lazy, pipe_fit, .. -- about 35 keys) were removed in
                              * round 5 and now return IBO_ERR_ARG "unknown option", as does a NULL key; ibo_nlml_grid's covariance pass is the fast one;
                              * 8: - ibo_direct_server_info and the options "direct_resident", "direct_idle_ms" (ibo_direct_max's resident evaluation server, measured
-                             * slower than the launches and removed: both keys are unknown options now) */
+                             * slower than the launches and removed: both keys are unknown options now); + ibo_gp_loo, ibo_loo_grad (leave-one-out predictions and the LOO-CV
+                             * objective with its gradient: additions within 8, nothing else changed) */
 
 /* status codes */
 #define IBO_OK              0
@@ -218,6 +219,17 @@ int ibo_gp_get_R(ibo_gp_t *gp, double *R_host);
 int ibo_gp_get_L(ibo_gp_t *gp, double *L_host);
 /* W = L^-1 (N x N, lower triangular), and R^-1 = W^T W if wanted by a caller */
 int ibo_gp_get_W(ibo_gp_t *gp, double *W_host);
+/*
+ * Leave-one-out predictions of the fitted model at its own points, from the factor the handle holds (O(N^2), one pass over W): with A the
+ * matrix the handle factored (R with diagonal 1 + noise, or what ibo_gp_fit_with_matrix was given), d_i = (A^-1)_ii = |column i of W|^2 and
+ * c = aY - m(x_i) a1 (m: the mean prior, if any; the reference subtracts the query's prior from every target):
+ *     mu_host[i] = Y_i - c_i / d_i        s2_host[i] = 1 / d_i        *nloo_host = sum_i [-log(d_i) / 2 + c_i^2 / (2 d_i)] + N log(2 pi) / 2
+ * i.e. the posterior at x_i of the model fitted WITHOUT observation i (the variance includes the noise, as ibo_posterior_batch's does) and the
+ * negative leave-one-out log predictive probability.  UNCLIPPED: ibo_posterior_batch clips its variance to [clamp_lo, 10] (Python: [1e-7, 10]),
+ * this does not.  Any output may be NULL, not all of them (IBO_ERR_ARG); IBO_ERR_STATE before a successful fit.  Works after ibo_gp_extend.
+ * Fixed-order sums: the same call gives the same bits.
+ */
+int ibo_gp_loo(ibo_gp_t *gp, double *mu_host, double *s2_host, double *nloo_host);
 int ibo_gp_info(ibo_gp_t *gp, int *N, int *D, int *device, double *max_y);
 /* milliseconds of the last fit, device-side (hipEvent) */
 int ibo_gp_last_fit_ms(ibo_gp_t *gp, float *ms);
@@ -450,6 +462,23 @@ int ibo_trim(int device);
 int ibo_nlml_grad(int device, int ktype, int N, int D, const double *X_host, const double *Y_host,
                   const double *hyper_host, int nhyper, double sf2, double noise,
                   int ngrad, const int *modes, const int *dims, double *nlml_host, double *grad_host);
+
+/*
+ * The leave-one-out objective of K = covMatrix + noise I for one theta, to be minimised like the NLML (Rasmussen & Williams 5.4.2): with
+ * B = K^-1, d_i = B_ii, alpha = B y
+ *     nloo = sum_i [-log(d_i) / 2 + alpha_i^2 / (2 d_i)] + N log(2 pi) / 2        mu_host[i] = y_i - alpha_i / d_i        s2_host[i] = 1 / d_i
+ * and, when grad_host is given, d nloo / d log theta_h = -sum_i [alpha_i r_i - (1 + alpha_i^2 / d_i) s_i / 2] / d_i for h < ngrad, where
+ * T = B dK_h, r = T alpha, s_i = sum_b T_ib B_ib and dK_h = Kernel.derivative(X, h) as modes / dims describe it (ibo_nlml_grad's).  Contract,
+ * limits and error codes are ibo_nlml_grad's (up to 23168 rows; IBO_ERR_NOT_PD leaves the outputs untouched), except that grad_host may be
+ * NULL (value only: ngrad, modes, dims ignored) and 1 <= ngrad <= 65 otherwise; mu_host / s2_host are optional.  It runs ibo_nlml_grad's
+ * sequence up to K^-1 on that entry's workspace and resident X / Y (calls of the two may interleave freely; neither changes the other's
+ * bits), then 2 ngrad N^3 flops on the fp64 MFMA unit, four derivatives per pass, dK_h generated on the fly.  Fixed-order sums, no atomics.
+ */
+int ibo_loo_grad(int device, int ktype, int N, int D, const double *X_host, const double *Y_host,
+                 const double *hyper_host, int nhyper, double sf2, double noise,
+                 int ngrad, const int *modes, const int *dims,
+                 double *nloo_host, double *grad_host /* ngrad, or NULL: value only */,
+                 double *mu_host /* N or NULL */, double *s2_host /* N or NULL */);
 
 /* ---------------------------------------------------------------- multi-GPU arg-max exchange (RCCL) */
 #define IBO_COMM_ID_BYTES 128
