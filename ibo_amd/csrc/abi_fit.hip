@@ -28,19 +28,18 @@ int make_kparams(int ktype, int D, const double *hyper, int nhyper, double sf2, 
     return IBO_OK;
 }
 
-// |x~|^2 bounds the absolute error of y = a_k + b_c + x~.c~ by ~|x~|^2 * 2^-52
+// |x~|^2 bounds the absolute error of y = a_k + b_c + x~.c~ by ~|x~|^2 * 2^-52 (IBO_DOT_GUARD, ibo_common.h)
 static int dot_form_ok(const KParams &kp, const double *X, int N, int D)
 {
     if (D > IBO_DDOT) return 0;                      // 33 .. 64 dimensions: difference-form kernels only
     double mx = 0.0;
     for (int i = 0; i < N; i++) {
-        double n2 = 0.0;
-        for (int d = 0; d < D; d++) { double v = X[(size_t)i * D + d] * kp.sw[d]; n2 += v * v; }
+        const double n2 = ibo_scaled_norm2(kp.sw, X + (size_t)i * D, D);
         if (n2 > mx) mx = n2;
     }
     const char *e = getenv("IBO_DOT_FORM");
     if (e) return atoi(e);
-    return mx <= 1e5;
+    return mx <= IBO_DOT_GUARD;
 }
 
 
@@ -242,11 +241,8 @@ extern "C" int ibo_gp_extend(ibo_gp_t *g, int n, const double *Xnew, const doubl
     HIP_TRY(hipEventElapsedTime(&g->fit_ms, g->fit0, g->fit1));
     gpu_time_add(g->device, g->fit_ms);
     if (g->dot_form) {                              // |x~|^2 of the new points still admits the dot form?
-        for (int i = 0; i < n && g->dot_form; i++) {
-            double n2 = 0.0;
-            for (int d = 0; d < D; d++) { const double v = Xnew[(size_t)i * D + d] * g->kp_fit.sw[d]; n2 += v * v; }
-            if (n2 > 1e5) g->dot_form = 0;
-        }
+        for (int i = 0; i < n && g->dot_form; i++)
+            if (ibo_scaled_norm2(g->kp_fit.sw, Xnew + (size_t)i * D, D) > IBO_DOT_GUARD) g->dot_form = 0;
     }
     // the kept sweep state's stale tiles carry means formed with the OLD alpha vectors, and the lazy refresh's drift margin only
     // covers the appended rows' (W y)_i: a caller that changed an earlier target along the way (GaussianProcess.Y is a public

@@ -100,7 +100,7 @@ extern "C" int ibo_nlml_grid(int device, int ktype, int N, int D, const double *
     for (int t = 0; t < n_theta; t++)
         IBO_TRY(make_kparams(ktype, D, thetas + (size_t)t * nhyper, nhyper, sf2s ? sf2s[t] : 1.0, &kps[t]));
     // the covariance pass forms the exponent on the MFMA unit (cov_grid_mfma_kernel) where every scaled point of every theta-point stays
-    // within the dot form's accuracy guard: |x~|^2 <= sum_d w_d max_k x_kd^2 <= 1e5 (ibo_set_option("dot_form", 0) keeps the difference form)
+    // within the dot form's accuracy guard: |x~|^2 <= sum_d w_d max_k x_kd^2 <= IBO_DOT_GUARD_NLML (ibo_set_option("dot_form", 0) keeps the difference form)
     int dot_ok = g_dot_override.load() != 0 && D <= IBO_DDOT;
     if (dot_ok) {
         std::vector<double> xm(D, 0.0);
@@ -109,7 +109,7 @@ extern "C" int ibo_nlml_grid(int device, int ktype, int N, int D, const double *
         for (int t = 0; t < n_theta && dot_ok; t++) {
             double b = 0.0;
             for (int d = 0; d < D; d++) b += kps[t].w[d] * xm[d];
-            if (!(b <= 1e5)) dot_ok = 0;
+            if (!(b <= IBO_DOT_GUARD_NLML)) dot_ok = 0;
         }
     }
     IBO_TRY(ws.dkp.ensure(n_theta));

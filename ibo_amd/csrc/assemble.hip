@@ -253,7 +253,7 @@ __global__ __launch_bounds__(256) void cov_grid_kernel(const KParams *__restrict
 // its 4.3 GB of stores).  Same tiles and numbering as cov_grid_kernel (64 rows x 128 columns, four waves: wave w takes rows 16 w .. of all
 // eight column blocks, so a row's 1 KiB still leaves the workgroup together); the augmented rows are built in LDS with an odd stride
 // (conflict-free fragment reads); exp_fast / sqrt_fast as before.  |y|'s absolute error is ~|x~|^2 2^-52, hence the caller's guard
-// (|x~|^2 <= 1e5 for every row and every theta-point of the call: launch_cov_matrix_batched's `dot_ok`), beyond which the difference form runs.
+// (|x~|^2 <= IBO_DOT_GUARD_NLML = 1e5 for every row and every theta-point of the call: launch_cov_matrix_batched's `dot_ok`), beyond which the difference form runs.
 // The 64 x 64 diagonal blocks are written whole, as before; inside them K_ij and K_ji may differ in the last bit (the two a's enter the
 // sum in the other order) -- the factorisation reads the lower triangle only.
 template <int KA4>

@@ -10,6 +10,28 @@
 #define IBO_DDOT 32            // ... and the largest for which the dot-form kernels (sweep2.hip, small2.hip: exponent GEMM of up to
                                // nine k4-steps) are instantiated; beyond, the difference-form kernels of sweep.hip take every batch
 
+// The dot form y = a_k + b_c + x~.c~ (x~ = x sqrt(w)) carries an ABSOLUTE error of about |x~|^2 2^-52 in the exponent, whatever the distance
+// between the two points; a model whose scaled observations lie farther from the origin takes the difference-form kernels.
+//   IBO_DOT_GUARD       max_k |x~_k|^2 of a model's observations that still admits the dot-form sweeps (dot_form_ok and ibo_gp_extend in
+//                       abi_fit.hip).  The posterior mean is the sensitive output: its error is about (exponent error) x sum_i |k*_i alpha_i|,
+//                       absolute and growing with the model.  At 1e5 -- the value until the suite left the unit cube -- a 1100-row model at
+//                       the edge missed the 1e-9 absolute bar on the mean (1.2e-9 to 3e-9 on the device, 0.9 to 1.0 of the bar in the
+//                       float64 restatement of tests/shift_reference.py); 2e4 leaves that model a factor of four, the variance and the
+//                       acquisition values a factor of a hundred under their 1e-6.
+//   IBO_DOT_GUARD_NLML  the same for ibo_nlml_grid's covariance pass, on the per-dimension bound sum_d w_d max_k x_kd^2 over every theta-point of
+//                       the call (abi_nlml.hip).  At its edge the likelihood value moves by up to 2e-8 relative (1e-10 in the unit cube),
+//                       which no optimiser notices: left where it was.
+#define IBO_DOT_GUARD 2e4
+#define IBO_DOT_GUARD_NLML 1e5
+
+// |x~|^2 of one point under a kernel's scaling (host side: the guards above)
+static inline double ibo_scaled_norm2(const double *sw, const double *x, int D)
+{
+    double n2 = 0.0;
+    for (int d = 0; d < D; d++) { const double v = x[d] * sw[d]; n2 += v * v; }
+    return n2;
+}
+
 // covariance families after normalising the reference's four kernel types to
 // "weighted squared distance z = sum_d w_d (x_d - c_d)^2, then a scalar map":
 //   SE  (ARD: w_d = 1/theta_d^2, ISO: w_d = 1/theta^2)  k = sf2 exp(-z/2)

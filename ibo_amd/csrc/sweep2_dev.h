@@ -102,7 +102,7 @@ __device__ __forceinline__ double s2_kstar(double y, double sf2, const double *t
 }
 
 // TCAND candidates of a tile -> lds_c[cand][KA (+1: odd row stride, conflict-free fragment reads)] = [c~ (D) | 1 | b_c | 0..]  (c~ = c sqrt(w)).  A candidate more than 775
-// length scales from the origin (hence > 450 from every observation: |x~| <= 316 where the dot form is in use) has k* = 0
+// length scales from the origin (hence > 630 from every observation: |x~| <= 142 where the dot form is in use, IBO_DOT_GUARD) has k* = 0
 // exactly; it is pulled in to that radius, where k* is still 0, so that the exponent stays within what s2_exp's integer
 // arithmetic covers (|y| < 7e5).  cand: where the candidates are read from (nullptr: a.cand).  Called by the whole workgroup; ends with a barrier.
 template <int FAM, int TCAND, int KA, int NT>

@@ -102,8 +102,8 @@ __global__ __launch_bounds__(S2_NW * 64) void sweep2_kernel(SweepArgs a)
     if (tid < TCAND) {
         double n2 = 0.0;
         for (int d = 0; d < D; d++) { const double v = lds_c[tid * (KA + 1) + d]; n2 = fma(v, v, n2); }
-        // A candidate more than 775 length scales from the origin (hence > 450 from every observation: |x~| <= 316
-        // where the dot form is in use) has k* = 0 exactly; it is pulled in to that radius, where k* is still 0, so
+        // A candidate more than 775 length scales from the origin (hence > 630 from every observation: |x~| <= 142
+        // where the dot form is in use, IBO_DOT_GUARD) has k* = 0 exactly; it is pulled in to that radius, where k* is still 0, so
         // that the exponent stays within what s2_exp's integer arithmetic covers (|y| < 7e5).
         if (n2 > 6e5) {
             const double sc = sqrt(6e5 / n2);

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Randomised parity sweep (GPU box): fit + posterior + EI over random (N, D, kernel, M) against the oracle.
-python3 tools/fuzz_gpu.py [n_cases] [seed]"""
+python3 tools/fuzz_gpu.py [n_cases] [seed]
+FUZZ_SHIFT=1: observations and candidates on the 2^-12 grid, moved by one integer per case drawn from {0, +-3, just below the dot
+form's guard, just above it, +-4096} (tests/shift_reference.py); both sides get the shifted data.  Off by default: the seeds of the
+summaries in profiles/ reproduce."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
@@ -16,6 +19,24 @@ if os.environ.get("FUZZ_OPTS"):
     from ibo_amd import _lib
     for kv in os.environ["FUZZ_OPTS"].split(","):
         k, v = kv.split("="); _lib.check(_lib.lib.ibo_set_option(k.encode(), int(v)))
+SHIFT = os.environ.get("FUZZ_SHIFT", "0") != "0"
+if SHIFT:
+    import shift_reference as sr
+
+
+def draw_shift(rs, X0, sw):
+    """one of 0, +-3, an integer that lands max |x~|^2 just inside / just beyond the guard (either sign), +-4096"""
+    which = rs.randint(7)
+    sign = 1 if rs.randint(2) else -1
+    if which == 0: return 0
+    if which in (1, 2): return 3 * sign
+    if which in (5, 6): return 4096 * sign
+    try:
+        return sr.shift_for(X0, sw, *(sr.INSIDE if which == 3 else sr.OUTSIDE), sign=sign)
+    except AssertionError:                               # length scales so short that no integer lands in the band
+        return 0
+
+
 ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 rs = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 special_N = [1, 2, 15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 257, 511, 512, 513, 1023, 1025, 1471, 2047, 2049]
@@ -33,13 +54,22 @@ for case in range(ncases):
     elif kind == "iso": hyp = th[:1]; ours = K.GaussianKernel_iso(hyp)
     elif kind == "m3": hyp = np.r_[th[0], 1.0]; ours = K.MaternKernel3(hyp)
     else: hyp = np.r_[th[0], 1.0]; ours = K.MaternKernel5(hyp)
+    cand = None
+    shift = 0
+    if SHIFT:
+        X0 = np.floor(X * sr.GRID) / sr.GRID
+        Y = np.sin(3 * X0.sum(1)) + .01 * rs.randn(N)
+        shift = draw_shift(rs, X0, sr.scale_of(kind, list(hyp), D))
+        X = X0 + shift
+        cand = np.floor(rs.rand(M, D) * sr.GRID) / sr.GRID + shift
     ogp = orc.GP(orc.Kern(kind, hyp), X, Y, noise=noise)
     try:
         np.linalg.cholesky(ogp.factor_matrix())
     except np.linalg.LinAlgError:
         continue
     gp = GaussianProcess(ours, X, Y, noise=noise)
-    cand = rs.rand(M, D)
+    if cand is None:
+        cand = rs.rand(M, D)
     Mo = min(M, 300)                                    # the oracle's share (it is O(N^2) per point, scalar)
     r = sweep(gp, cand, acq='ei', xi=.01, native=True, outputs=("mu", "s2", "acq"))
     o = orc.sweep_native(ogp, cand[:Mo], orc.ACQ_EI, .01)
@@ -49,7 +79,8 @@ for case in range(ncases):
     ok_idx = int(np.argmax(r["acq"])) == r["best_idx"]
     worst = max(worst, em, es, ea)
     flag = "" if (max(em, es, ea) < 1e-6 and ok_idx) else "   <-- FAIL"
-    print("N=%5d D=%2d %-3s M=%6d noise=%g  rel err mu %.1e s2 %.1e ei %.1e argmax %s%s" % (N, D, kind, M, noise, em, es, ea, ok_idx, flag), flush=True)
+    print("N=%5d D=%2d %-3s M=%6d noise=%g%s  rel err mu %.1e s2 %.1e ei %.1e argmax %s%s" %
+          (N, D, kind, M, noise, "  shift %d %s" % (shift, r["kernel"]) if SHIFT else "", em, es, ea, ok_idx, flag), flush=True)
 print("worst relative error %.2e over %d cases, %.1f s" % (worst, ncases, time.time() - t0))
 
 # --- DIRECT: maximizeEI / PI / UCB on the GPU objective against the oracle's sequential run -----------------
