@@ -535,10 +535,8 @@ extern "C" int ibo_gp_loo(ibo_gp_t *g, double *mu_host, double *s2_host, double 
     ScopedBuf<double> buf;                              // d, mu, s2 (Np each) and the sum
     IBO_TRY(buf.ensure(3 * (size_t)Np + 1));
     double *d = buf.p, *mu = d + Np, *s2 = mu + Np, *out = s2 + Np;
-    PriorDev pr;
-    pr.nb = g->nb; pr.theta = g->ptheta; pr.means = g->pmeans.p; pr.beta = g->pbeta.p; pr.lowerb = g->plowerb.p; pr.width = g->pwidth.p;
     KERNEL_TRY(launch_loo_diag(g->W.p, (size_t)Np, N, d, s));
-    KERNEL_TRY(launch_loo_handle(pr, g->Xp.p, g->DP, g->D, N, g->Y.p, g->alphaY.p, g->alpha1.p, d, mu_host ? mu : nullptr, s2_host ? s2 : nullptr,
+    KERNEL_TRY(launch_loo_handle(prior_of(g), g->Xp.p, g->DP, g->D, N, g->Y.p, g->alphaY.p, g->alpha1.p, d, mu_host ? mu : nullptr, s2_host ? s2 : nullptr,
                                  out, s));
     double v = 0.0;
     if (mu_host) HIP_TRY(hipMemcpyAsync(mu_host, mu, sizeof(double) * N, hipMemcpyDeviceToHost, s));

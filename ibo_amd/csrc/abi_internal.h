@@ -146,6 +146,13 @@ struct ibo_gp {
 };
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+// the handle's mean prior as the kernels take it (sweeps, gradients, leave-one-out)
+static inline PriorDev prior_of(const ibo_gp *g)
+{
+    PriorDev p;
+    p.nb = g->nb; p.theta = g->ptheta; p.means = g->pmeans.p; p.beta = g->pbeta.p; p.lowerb = g->plowerb.p; p.width = g->pwidth.p;
+    return p;
+}
 // Which order factors an Np-row matrix: the single-level right-looking order with pipelined block columns and W = L^-1 riding along
 // (launch_cholesky_fused) below g_fused2_min_nb block columns, the two-level order (panels of four, K = 256 updates, recursive-doubling
 // inversion) from there on: 104 block columns (6656 rows) by default -- with the eight-wave pipelined column and two steps per pass the

@@ -26,197 +26,265 @@ int exp_table(int device, const double **out)
 }
 
 // ------------------------------------------------------------------------ sweep
-static int run_sweep(ibo_gp *g, int64_t M, const double *cand_dev, int acq, double parm, int erf_mode,
-                     double clamp_lo, double ymax, int n_excl, const double *excl_host, double excl_radius,
-                     int64_t index_base, double *mu_dev, double *s2_dev, double *acq_dev,
-                     double *best_val, int64_t *best_idx, bool incremental = false, bool timed = true, bool signal = false,
-                     const double *cand_host = nullptr, bool device_result = false)
+// What one sweep is asked for: the arguments of ibo_acq_sweep, and what the library's own callers add to them.  Lives on the caller's stack.
+struct SweepRequest {
+    int64_t M = 0;
+    const double *cand_dev = nullptr;            // M x D, where the kernels read them (device memory, or pinned host memory)
+    const double *cand_host = nullptr;           // the same candidates where the HOST can read them (pinned staging), or NULL
+    int acq = IBO_ACQ_NONE, erf_mode = IBO_ERF_LIBM;
+    double parm = 0.0, clamp_lo = 0.0, ymax = NAN;       // ymax NaN: the model's largest observation
+    int n_excl = 0; const double *excl_host = nullptr; double excl_radius = 0.0;
+    int64_t index_base = 0;
+    double *mu_dev = nullptr, *s2_dev = nullptr, *acq_dev = nullptr;     // per-candidate outputs, optional
+    double *best_val = nullptr; int64_t *best_idx = nullptr;             // the arg-max, on the host (both NULL: no read-back, no synchronisation)
+    bool incremental = false;                    // keep the candidates' state on the handle (ibo_acq_sweep_incremental)
+    bool timed = true;                           // kernel-time events around the launches (small2.hip's only: the others always record them)
+    bool signal = false;                         // the caller will spin on the handle's host-visible word instead of an event, where the route can write it
+    bool device_result = false;                  // (value, index) stay in res_v / res_i for the exchange
+};
+
+// the part of the kernel arguments that comes from the handle alone
+static void fill_model_args(const ibo_gp *g, SweepArgs &a)
 {
-    if (!g->fitted) return fail(IBO_ERR_STATE, "sweep before a successful fit");
-    if (M < 1 || !cand_dev) return fail(IBO_ERR_ARG, "empty candidate set");
-    if (acq < 0 || acq > 3) return fail(IBO_ERR_ARG, "unknown acquisition %d", acq);
-    hipStream_t s = g->stream;
-    SweepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.kp = g->kp; a.N = g->N; a.Npad = g->Npad; a.DP = g->DP; a.M = M;
+    a.kp = g->kp; a.N = g->N; a.Npad = g->Npad; a.DP = g->DP;
     a.Xs = g->Xs.p; a.ak = g->ak.p; a.XA = g->XA.p; a.log_sf2 = log(g->kp.sf2); a.dot_form = (g_dot_override >= 0 && g->D <= IBO_DDOT) ? g_dot_override.load() : g->dot_form;
     a.Xp = g->Xp.p; a.W = g->W.p; a.Wp = g->Wp.p; a.alphaY = g->alphaY.p; a.alpha1 = g->alpha1.p;
-    a.cand = cand_dev; a.cand_host = cand_host;
-    a.prior.nb = g->nb; a.prior.theta = g->ptheta; a.prior.means = g->pmeans.p; a.prior.beta = g->pbeta.p;
-    a.prior.lowerb = g->plowerb.p; a.prior.width = g->pwidth.p;
-    a.noise = g->noise; a.clamp_lo = clamp_lo; a.ymax = (ymax == ymax) ? ymax : g->maxY; a.parm = parm;
-    a.acq = acq; a.erf_mode = erf_mode;
-    a.n_excl = 0; a.excl_radius = excl_radius;
-    if (n_excl > 0) {
-        if (!excl_host) return fail(IBO_ERR_ARG, "excl_host is NULL");
-        IBO_TRY(g->excl.ensure((size_t)n_excl * g->D));
-        HIP_TRY(hipMemcpyAsync(g->excl.p, excl_host, sizeof(double) * n_excl * g->D, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        a.n_excl = n_excl; a.excl = g->excl.p;
-    }
-    a.index_base = index_base;
-    a.out_mu = mu_dev; a.out_s2 = s2_dev; a.out_acq = acq_dev;
-    int64_t ntiles = (M + 63) / 64;
-    IBO_TRY(g->partv.ensure(2 * ntiles)); IBO_TRY(g->parti.ensure(2 * ntiles));     // sweep2 has 32-candidate tiles
-    IBO_TRY(g->res_v.ensure(1)); IBO_TRY(g->res_i.ensure(1));
-    a.part_val = g->partv.p; a.part_idx = g->parti.p;
-    const bool want_best = best_val || best_idx || device_result;      // device_result: (value, index) stay in res_v / res_i for the exchange
-    a.result_val = want_best ? g->res_v.p : nullptr; a.result_idx = want_best ? g->res_i.p : nullptr;
+    a.prior = prior_of(g);
+    a.noise = g->noise;
+}
+
+// Which kernel serves a sweep of M candidates on a model of Npad padded rows.  dot_form: whether the dot form holds for this sweep;
+// force_path: ibo_set_option("sweep_path") -- 0: by size, 1: GEMV, 3: panel-split, anything else: the large-batch kernels.
+// No handle, no HIP call, no allocation: the thresholds below are all there is to it.
+enum SweepRoute { ROUTE_SMALL2, ROUTE_SPLIT, ROUTE_GEMV, ROUTE_SWEEP2, ROUTE_TILE };
+static int choose_route(int64_t M, int Npad, int dot_form, int force_path, SweepRoute *route)
+{
+    const int64_t ntiles = (M + 63) / 64;
     // batches up to 4096 candidates where the dot form holds: three short kernels spread over the chip (small2.hip;
     // from ~8192 candidates on the panel-split kernel's tiles fill the chip by themselves and it is the faster one).
     // They beat the GEMV kernel down to a single candidate (N = 2048: 22 us against 87; N = 1024: 16 against 38), which
     // is left with the models they do not take (no dot form, rows beyond sweep2's LDS budget).
-    const bool small2_ok = g_force_path == 0 && M <= 4096 && a.dot_form && sweep2_fits(a.Npad);
+    const bool small2_ok = force_path == 0 && M <= 4096 && dot_form && sweep2_fits(Npad);
     // (the GEMV kernel holds k* of a candidate in LDS: beyond 20416 rows a few candidates go to the panel-split kernel)
-    bool gemv = (g_force_path == 1) || (g_force_path == 0 && M <= 16 && !small2_ok && sweep_gemv_fits(a.Npad));
-    if (gemv && !sweep_gemv_fits(a.Npad))
-        return fail(IBO_ERR_ARG, "the GEMV sweep kernel holds at most 20416 rows in its 160 KiB of LDS (model: %d padded rows)", a.Npad);
+    const bool gemv = (force_path == 1) || (force_path == 0 && M <= 16 && !small2_ok && sweep_gemv_fits(Npad));
+    if (gemv && !sweep_gemv_fits(Npad))
+        return fail(IBO_ERR_ARG, "the GEMV sweep kernel holds at most 20416 rows in its 160 KiB of LDS (model: %d padded rows)", Npad);
     // small batches: spread the IBO_SPLIT_PANEL-row panels over the grid too (one tile per 64 candidates alone
     // would leave most of the 256 CUs idle); above ~128 tiles the plain kernel fills the chip
     // (4097 .. 8192 candidates are at most 256 tiles of the large-batch kernel -- one round of the chip, 134 us at N = 1024 and
     // 495 us at N = 2048 whatever their number, where the panel-split kernel takes 142 .. 221 and 478 .. 842 us)
-    const bool sweep2_ok = a.dot_form && sweep2_fits(a.Npad);
-    bool split = !gemv && (g_force_path == 3 || (g_force_path == 0 && ntiles * 2 <= 256 && !(sweep2_ok && M > 4096)));
-    const bool small2 = split && small2_ok;
-    if (small2) {
-        IBO_TRY(exp_table(g->device, &a.exp_tab));
-        IBO_TRY(g->small_ws.ensure(small_sweep_workspace(g->Npad, M)));
-        if (signal && !want_best) {                  // the caller will spin on a host-visible word the last kernel writes
-            if (!g->done_flag) {                     // (a recycled handle brings its flag along)
-                HIP_TRY(hipHostMalloc((void **)&g->done_flag, 64, hipHostMallocDefault));
-                *g->done_flag = 0;
-            }
-            if (!g->done_count.p) {
-                IBO_TRY(g->done_count.ensure(1));
-                HIP_TRY(hipMemsetAsync(g->done_count.p, 0, sizeof(unsigned), s));
-            }
-            a.done_flag = g->done_flag; a.done_seq = ++g->done_seq; a.done_count = g->done_count.p;
-            g->signal_pending = true;
+    const bool sweep2_ok = dot_form && sweep2_fits(Npad);
+    const bool split = !gemv && (force_path == 3 || (force_path == 0 && ntiles * 2 <= 256 && !(sweep2_ok && M > 4096)));
+    *route = (split && small2_ok) ? ROUTE_SMALL2 : split ? ROUTE_SPLIT : gemv ? ROUTE_GEMV : sweep2_ok ? ROUTE_SWEEP2 : ROUTE_TILE;
+    return IBO_OK;
+}
+
+// The diagnostic build's per-tile stamps (make stamps; tools/stamp_sweep.py, tools/stamp_sweep2.py) travel in mupart, `words` 64-bit words
+// in all; after the launch they go to the file IBO_STAMP_FILE names.  The product's build has neither.
+#ifdef IBO_STAMPS
+static int stamps_attach(ibo_gp *g, SweepArgs &a, size_t words)
+{
+    IBO_TRY(g->mupart.ensure(words + 16));
+    a.mupart = g->mupart.p;
+    return IBO_OK;
+}
+static int stamps_dump(ibo_gp *g, size_t words)
+{
+    if (!getenv("IBO_STAMP_FILE")) return IBO_OK;
+    std::vector<unsigned long long> h(words);
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    HIP_TRY(hipMemcpy(h.data(), g->mupart.p, h.size() * 8, hipMemcpyDeviceToHost));
+    FILE *f = fopen(getenv("IBO_STAMP_FILE"), "wb");
+    if (f) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
+    return IBO_OK;
+}
+#else
+static inline int stamps_attach(ibo_gp *, SweepArgs &, size_t) { return IBO_OK; }
+static inline int stamps_dump(ibo_gp *, size_t) { return IBO_OK; }
+#endif
+
+// ---- one function per route: its buffers, its launch, the name ibo_last_sweep_kernel_ms reports
+static int sweep_small2(ibo_gp *g, SweepArgs &a, const SweepRequest &r)
+{
+    hipStream_t s = g->stream;
+    IBO_TRY(exp_table(g->device, &a.exp_tab));
+    IBO_TRY(g->small_ws.ensure(small_sweep_workspace(g->Npad, a.M)));
+    if (r.signal && !a.result_val) {             // (no arg-max to read back) the caller will spin on a host-visible word the last kernel writes
+        if (!g->done_flag) {                     // (a recycled handle brings its flag along)
+            HIP_TRY(hipHostMalloc((void **)&g->done_flag, 64, hipHostMallocDefault));
+            *g->done_flag = 0;
         }
-        KERNEL_TRY(launch_sweep_small(a, g->small_ws.p, s, timed ? g->ev0 : nullptr, timed ? g->ev1 : nullptr));
-        g->sweep_kernel = "wk_small_kernel";
-    } else if (split) {
-        IBO_TRY(g->qpart.ensure((size_t)((g->Npad + IBO_SPLIT_PANEL - 1) / IBO_SPLIT_PANEL) * M)); IBO_TRY(g->mupart.ensure(2 * (size_t)M));
-        a.qpart = g->qpart.p; a.mupart = g->mupart.p;
-        KERNEL_TRY(launch_sweep_mfma(a, s, g->ev0, g->ev1));
-        g->sweep_kernel = "sweep_mfma_kernel<split>";
-    } else if (gemv) {
-        IBO_TRY(g->qpart.ensure((size_t)(g->Npad / 64) * M)); IBO_TRY(g->mupart.ensure(2 * (size_t)M));
-        a.qpart = g->qpart.p; a.mupart = g->mupart.p;
-        KERNEL_TRY(launch_sweep_gemv(a, s, g->ev0, g->ev1));
-        g->sweep_kernel = "sweep_gemv_kernel";
-    } else if (sweep2_ok) {
-        IBO_TRY(exp_table(g->device, &a.exp_tab));
-        if (incremental) {
-            // the state of this candidate array is kept on the handle; if the model has only grown by a few rows
-            // (ibo_gp_extend) since it was formed, those rows are folded in -- O(N) per candidate, not O(N^2)
-            // (keyed on the array's GENERATION, not its address: see ibo_dev_alloc.  An array the library did not allocate
-            // has none, and is swept in full every time)
-            size_t off = 0;
-            const uint64_t gen = alloc_generation(g->device, cand_dev, sizeof(double) * (size_t)M * g->D, &off);
-            const bool usable = gen != 0 && g->st_gen == gen && g->st_off == off && g->st_M == M && g->st_epoch == g->fit_epoch && g->st_sf2 == g->kp.sf2 &&
-                                g->st_N >= 1 && g->st_N <= g->N && g->N - g->st_N <= 8 && (!g->st_pruned || g->N - g->st_N0 <= 16) && g->state.cap >= 5 * (size_t)M &&
-                                sweep2_rank1_fits(a.Npad, a.kp.D);
-            IBO_TRY(g->state.ensure(5 * (size_t)M));     // [q_a, aY.k*, a1.k*, zsum, q_b]: q = (q_a + q_b) + zsum
-            a.qpart = g->state.p;
-            a.state5 = 1;
-            // EI and UCB grow with the variance, and the variance computed from PART of W's rows bounds it from above: where only
-            // the arg-max is wanted, the second half of W's rows (three quarters of the work) runs only for tiles whose bound can
-            // still reach the best complete value (sweep2.hip: launch_sweep2_pruned).  PI and the plain mean, per-candidate
-            // outputs, or a model the part kernels do not take: every tile complete, as before.
-            // (UCB = mu + parm sigma grows with sigma only for parm >= 0: a caller's negative coefficient -- a lower confidence bound --
-            // takes the complete-every-tile route)
-            const bool monotone = (acq == IBO_ACQ_EI || (acq == IBO_ACQ_UCB && parm >= 0.0)) && !mu_dev && !s2_dev && !acq_dev;
-            const int64_t nt32 = (M + IBO_S2_TCAND - 1) / IBO_S2_TCAND;
-            a.part_rows = usable ? g->st_N0 : g->N;
-            a.part_slack = 1e-13 * (1.0 + fabs(a.ymax) + fabs(a.parm));
-            a.rank_hi = g->N; a.wy = g->tmp.p;               // (g->tmp[0 .. Npad) is W y after every fit, extension and ibo_gp_set_y)
-            // Drift margin of the lazy refresh: an appended row i moves a stale candidate's mean by nu_i (W y)_i, nu = W k*.  With
-            // R = sf2_fit P + (1 + noise - sf2_fit) I (P: the correlation matrix, unit diagonal -- the reference's diagonal rule) and
-            // k* = sf2_k p*, R >= sf2_fit P whenever sf2_fit <= 1 + noise, hence |nu_i|^2 <= q = k*^T R^-1 k* <= sf2_k^2 / sf2_fit
-            // (p*^T P^-1 p* <= 1 for a valid kernel).  1 for the squared exponentials, magnitude^2-dependent for the SV / Matern
-            // kernels and under ibo_gp_set_kstar_sf2.  A model fitted with sf2_fit > 1 + noise has no such bound: never lazy.
-            const bool nu_bounded = g->kp_fit.sf2 > 0.0 && g->kp_fit.sf2 <= 1.0 + g->noise;
-            a.nu_max = nu_bounded ? (g->kp.sf2 / sqrt(g->kp_fit.sf2)) * (1.0 + 1e-9) : INFINITY;
-            if (usable && g->st_pruned) {
-                // a two-part state: its tiles fold the appended rows in lazily (launch_sweep2_refresh); a caller that needs every
-                // candidate's own numbers (outputs, PI, the plain mean), the A/B switch, or a mean prior (whose second vector W 1
-                // moves the means of stale tiles by more than any margin allows) has every tile refreshed and completed instead
-                a.tile_done = g->tile_done.p; a.tile_ub = g->tile_ub.p; a.part_best = g->part_words.p; a.part_thresh = g->part_words.p + 1;
-                a.tile_rows = g->tile_rows.p; a.tile_sel = g->tile_sel.p; a.part_nlev = g->st_nlev;
-                a.part_lazy = monotone && g_gallery_prune == 1 && g->nb == 0 && nu_bounded;
-            }
-            if (usable) {
-                KERNEL_TRY(launch_sweep2_refresh(a, g->st_N, g->N - 1, s, g->ev0, g->ev1));
-                g->sweep_kernel = g->N > g->st_N ? "sweep2_rank1_kernel" : "acq_finish_kernel";
-            } else if (g_gallery_prune && monotone && sweep2_part_fits(a.Npad, a.kp.D)) {
-                IBO_TRY(g->tile_done.ensure((size_t)nt32)); IBO_TRY(g->tile_ub.ensure((size_t)nt32)); IBO_TRY(g->part_words.ensure(2));
-                IBO_TRY(g->tile_rows.ensure((size_t)nt32)); IBO_TRY(g->tile_sel.ensure(2 * (size_t)nt32 + 16));     // flags | compact list | counters
-                HIP_TRY(hipMemsetAsync(g->tile_done.p, 0, sizeof(int) * (size_t)nt32, s));
-                HIP_TRY(hipMemsetAsync(g->tile_rows.p, 0, sizeof(int) * (size_t)nt32, s));
-                a.tile_rows = g->tile_rows.p; a.tile_sel = g->tile_sel.p;
-                HIP_TRY(hipMemsetAsync(g->state.p + 3 * (size_t)M, 0, sizeof(double) * 2 * (size_t)M, s));
-                a.tile_done = g->tile_done.p; a.tile_ub = g->tile_ub.p; a.part_best = g->part_words.p; a.part_thresh = g->part_words.p + 1;
-                a.part_nlev = g->st_nlev = sweep2_part_nlev(a.Npad);
-                KERNEL_TRY(launch_sweep2_pruned(a, g_gallery_prune == 1, s, g->ev0, g->ev1));
-                g->st_pruned = true;
-                g->sweep_kernel = "sweep2_kernel<part>";
-            } else {
-                HIP_TRY(hipMemsetAsync(g->state.p + 3 * (size_t)M, 0, sizeof(double) * 2 * (size_t)M, s));
-                KERNEL_TRY(launch_sweep2(a, s, g->ev0, g->ev1));
-                g->st_pruned = false;
-                g->sweep_kernel = "sweep2_kernel";
-            }
-            if (!usable) g->st_N0 = g->N;
-            g->st_gen = gen; g->st_off = off; g->st_M = M; g->st_N = g->N; g->st_sf2 = g->kp.sf2; g->st_epoch = g->fit_epoch;
-        } else {
-            IBO_TRY(g->qpart.ensure(3 * (size_t)M));    // (q, aY.k*, a1.k*) per candidate, finished by acq_finish_kernel
-            a.qpart = g->qpart.p;
-#ifdef IBO_STAMPS
-            const size_t nt32s = (size_t)((M + IBO_S2_TCAND - 1) / IBO_S2_TCAND);
-            IBO_TRY(g->mupart.ensure(nt32s * 8 + 16));
-            a.mupart = g->mupart.p;
-#endif
-            KERNEL_TRY(launch_sweep2(a, s, g->ev0, g->ev1));
-            g->sweep_kernel = "sweep2_kernel";
-#ifdef IBO_STAMPS
-            if (getenv("IBO_STAMP_FILE")) {
-                std::vector<unsigned long long> h(nt32s * 8);
-                HIP_TRY(hipStreamSynchronize(s));
-                HIP_TRY(hipMemcpy(h.data(), g->mupart.p, h.size() * 8, hipMemcpyDeviceToHost));
-                FILE *f = fopen(getenv("IBO_STAMP_FILE"), "wb");
-                if (f) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-            }
-#endif
+        if (!g->done_count.p) {
+            IBO_TRY(g->done_count.ensure(1));
+            HIP_TRY(hipMemsetAsync(g->done_count.p, 0, sizeof(unsigned), s));
         }
-    } else {
-#ifdef IBO_STAMPS
-        IBO_TRY(g->mupart.ensure((size_t)ntiles * 16 + 16));
-        a.mupart = g->mupart.p;
-#endif
-        a.dot_form = 0;                              // the first-generation tile kernel is kept in its difference form only
-        KERNEL_TRY(launch_sweep_mfma(a, s, g->ev0, g->ev1));
-        g->sweep_kernel = "sweep_mfma_kernel";
-#ifdef IBO_STAMPS
-        if (getenv("IBO_STAMP_FILE")) {
-            std::vector<unsigned long long> h((size_t)ntiles * 16);
-            HIP_TRY(hipStreamSynchronize(s));
-            HIP_TRY(hipMemcpy(h.data(), g->mupart.p, h.size() * 8, hipMemcpyDeviceToHost));
-            FILE *f = fopen(getenv("IBO_STAMP_FILE"), "wb");
-            if (f) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-        }
-#endif
+        a.done_flag = g->done_flag; a.done_seq = ++g->done_seq; a.done_count = g->done_count.p;
+        g->signal_pending = true;
     }
-    if (!best_val && !best_idx) return IBO_OK;        // internal callers that only want the per-point outputs (or the result on the device)
+    KERNEL_TRY(launch_sweep_small(a, g->small_ws.p, s, r.timed ? g->ev0 : nullptr, r.timed ? g->ev1 : nullptr));
+    g->sweep_kernel = "wk_small_kernel";
+    return IBO_OK;
+}
+
+static int sweep_split_or_gemv(ibo_gp *g, SweepArgs &a, bool gemv)
+{
+    const size_t chunks = gemv ? (size_t)(g->Npad / 64) : (size_t)((g->Npad + IBO_SPLIT_PANEL - 1) / IBO_SPLIT_PANEL);
+    IBO_TRY(g->qpart.ensure(chunks * a.M)); IBO_TRY(g->mupart.ensure(2 * (size_t)a.M));
+    a.qpart = g->qpart.p; a.mupart = g->mupart.p;
+    if (gemv) KERNEL_TRY(launch_sweep_gemv(a, g->stream, g->ev0, g->ev1));
+    else KERNEL_TRY(launch_sweep_mfma(a, g->stream, g->ev0, g->ev1));
+    g->sweep_kernel = gemv ? "sweep_gemv_kernel" : "sweep_mfma_kernel<split>";
+    return IBO_OK;
+}
+
+static int sweep_sweep2(ibo_gp *g, SweepArgs &a)
+{
+    const size_t words = (size_t)((a.M + IBO_S2_TCAND - 1) / IBO_S2_TCAND) * 8;
+    IBO_TRY(exp_table(g->device, &a.exp_tab));
+    IBO_TRY(g->qpart.ensure(3 * (size_t)a.M));    // (q, aY.k*, a1.k*) per candidate, finished by acq_finish_kernel
+    a.qpart = g->qpart.p;
+    IBO_TRY(stamps_attach(g, a, words));
+    KERNEL_TRY(launch_sweep2(a, g->stream, g->ev0, g->ev1));
+    g->sweep_kernel = "sweep2_kernel";
+    return stamps_dump(g, words);
+}
+
+static int sweep_tile(ibo_gp *g, SweepArgs &a)
+{
+    const size_t words = (size_t)((a.M + 63) / 64) * 16;
+    IBO_TRY(stamps_attach(g, a, words));
+    a.dot_form = 0;                              // the first-generation tile kernel is kept in its difference form only
+    KERNEL_TRY(launch_sweep_mfma(a, g->stream, g->ev0, g->ev1));
+    g->sweep_kernel = "sweep_mfma_kernel";
+    return stamps_dump(g, words);
+}
+
+// The sweep2 route of ibo_acq_sweep_incremental: the state of this candidate array is kept on the handle; if the model has only grown by a
+// few rows (ibo_gp_extend) since it was formed, those rows are folded in -- O(N) per candidate, not O(N^2)
+// (keyed on the array's GENERATION, not its address: see ibo_dev_alloc.  An array the library did not allocate
+// has none, and is swept in full every time)
+static int sweep_sweep2_kept(ibo_gp *g, SweepArgs &a, const SweepRequest &r)
+{
+    hipStream_t s = g->stream;
+    const int64_t M = a.M;
+    IBO_TRY(exp_table(g->device, &a.exp_tab));
+    size_t off = 0;
+    const uint64_t gen = alloc_generation(g->device, r.cand_dev, sizeof(double) * (size_t)M * g->D, &off);
+    const bool usable = gen != 0 && g->st_gen == gen && g->st_off == off && g->st_M == M && g->st_epoch == g->fit_epoch && g->st_sf2 == g->kp.sf2 &&
+                        g->st_N >= 1 && g->st_N <= g->N && g->N - g->st_N <= 8 && (!g->st_pruned || g->N - g->st_N0 <= 16) && g->state.cap >= 5 * (size_t)M &&
+                        sweep2_rank1_fits(a.Npad, a.kp.D);
+    IBO_TRY(g->state.ensure(5 * (size_t)M));     // [q_a, aY.k*, a1.k*, zsum, q_b]: q = (q_a + q_b) + zsum
+    a.qpart = g->state.p;
+    a.state5 = 1;
+    // EI and UCB grow with the variance, and the variance computed from PART of W's rows bounds it from above: where only
+    // the arg-max is wanted, the second half of W's rows (three quarters of the work) runs only for tiles whose bound can
+    // still reach the best complete value (sweep2.hip: launch_sweep2_pruned).  PI and the plain mean, per-candidate
+    // outputs, or a model the part kernels do not take: every tile complete, as before.
+    // (UCB = mu + parm sigma grows with sigma only for parm >= 0: a caller's negative coefficient -- a lower confidence bound --
+    // takes the complete-every-tile route)
+    const bool monotone = (r.acq == IBO_ACQ_EI || (r.acq == IBO_ACQ_UCB && r.parm >= 0.0)) && !r.mu_dev && !r.s2_dev && !r.acq_dev;
+    const int64_t nt32 = (M + IBO_S2_TCAND - 1) / IBO_S2_TCAND;
+    a.part_rows = usable ? g->st_N0 : g->N;
+    a.part_slack = 1e-13 * (1.0 + fabs(a.ymax) + fabs(a.parm));
+    a.rank_hi = g->N; a.wy = g->tmp.p;               // (g->tmp[0 .. Npad) is W y after every fit, extension and ibo_gp_set_y)
+    // Drift margin of the lazy refresh: an appended row i moves a stale candidate's mean by nu_i (W y)_i, nu = W k*.  With
+    // R = sf2_fit P + (1 + noise - sf2_fit) I (P: the correlation matrix, unit diagonal -- the reference's diagonal rule) and
+    // k* = sf2_k p*, R >= sf2_fit P whenever sf2_fit <= 1 + noise, hence |nu_i|^2 <= q = k*^T R^-1 k* <= sf2_k^2 / sf2_fit
+    // (p*^T P^-1 p* <= 1 for a valid kernel).  1 for the squared exponentials, magnitude^2-dependent for the SV / Matern
+    // kernels and under ibo_gp_set_kstar_sf2.  A model fitted with sf2_fit > 1 + noise has no such bound: never lazy.
+    const bool nu_bounded = g->kp_fit.sf2 > 0.0 && g->kp_fit.sf2 <= 1.0 + g->noise;
+    a.nu_max = nu_bounded ? (g->kp.sf2 / sqrt(g->kp_fit.sf2)) * (1.0 + 1e-9) : INFINITY;
+    if (usable && g->st_pruned) {
+        // a two-part state: its tiles fold the appended rows in lazily (launch_sweep2_refresh); a caller that needs every
+        // candidate's own numbers (outputs, PI, the plain mean), the A/B switch, or a mean prior (whose second vector W 1
+        // moves the means of stale tiles by more than any margin allows) has every tile refreshed and completed instead
+        a.tile_done = g->tile_done.p; a.tile_ub = g->tile_ub.p; a.part_best = g->part_words.p; a.part_thresh = g->part_words.p + 1;
+        a.tile_rows = g->tile_rows.p; a.tile_sel = g->tile_sel.p; a.part_nlev = g->st_nlev;
+        a.part_lazy = monotone && g_gallery_prune == 1 && g->nb == 0 && nu_bounded;
+    }
+    if (usable) {
+        KERNEL_TRY(launch_sweep2_refresh(a, g->st_N, g->N - 1, s, g->ev0, g->ev1));
+        g->sweep_kernel = g->N > g->st_N ? "sweep2_rank1_kernel" : "acq_finish_kernel";
+    } else if (g_gallery_prune && monotone && sweep2_part_fits(a.Npad, a.kp.D)) {
+        IBO_TRY(g->tile_done.ensure((size_t)nt32)); IBO_TRY(g->tile_ub.ensure((size_t)nt32)); IBO_TRY(g->part_words.ensure(2));
+        IBO_TRY(g->tile_rows.ensure((size_t)nt32)); IBO_TRY(g->tile_sel.ensure(2 * (size_t)nt32 + 16));     // flags | compact list | counters
+        HIP_TRY(hipMemsetAsync(g->tile_done.p, 0, sizeof(int) * (size_t)nt32, s));
+        HIP_TRY(hipMemsetAsync(g->tile_rows.p, 0, sizeof(int) * (size_t)nt32, s));
+        a.tile_rows = g->tile_rows.p; a.tile_sel = g->tile_sel.p;
+        HIP_TRY(hipMemsetAsync(g->state.p + 3 * (size_t)M, 0, sizeof(double) * 2 * (size_t)M, s));
+        a.tile_done = g->tile_done.p; a.tile_ub = g->tile_ub.p; a.part_best = g->part_words.p; a.part_thresh = g->part_words.p + 1;
+        a.part_nlev = g->st_nlev = sweep2_part_nlev(a.Npad);
+        KERNEL_TRY(launch_sweep2_pruned(a, g_gallery_prune == 1, s, g->ev0, g->ev1));
+        g->st_pruned = true;
+        g->sweep_kernel = "sweep2_kernel<part>";
+    } else {
+        HIP_TRY(hipMemsetAsync(g->state.p + 3 * (size_t)M, 0, sizeof(double) * 2 * (size_t)M, s));
+        KERNEL_TRY(launch_sweep2(a, s, g->ev0, g->ev1));
+        g->st_pruned = false;
+        g->sweep_kernel = "sweep2_kernel";
+    }
+    if (!usable) g->st_N0 = g->N;
+    g->st_gen = gen; g->st_off = off; g->st_M = M; g->st_N = g->N; g->st_sf2 = g->kp.sf2; g->st_epoch = g->fit_epoch;
+    return IBO_OK;
+}
+
+static int run_sweep(ibo_gp *g, const SweepRequest &r)
+{
+    if (!g->fitted) return fail(IBO_ERR_STATE, "sweep before a successful fit");
+    if (r.M < 1 || !r.cand_dev) return fail(IBO_ERR_ARG, "empty candidate set");
+    if (r.acq < 0 || r.acq > 3) return fail(IBO_ERR_ARG, "unknown acquisition %d", r.acq);
+    hipStream_t s = g->stream;
+    SweepArgs a;
+    memset(&a, 0, sizeof(a));
+    fill_model_args(g, a);
+    a.M = r.M; a.cand = r.cand_dev; a.cand_host = r.cand_host;
+    a.clamp_lo = r.clamp_lo; a.ymax = (r.ymax == r.ymax) ? r.ymax : g->maxY; a.parm = r.parm;
+    a.acq = r.acq; a.erf_mode = r.erf_mode;
+    a.n_excl = 0; a.excl_radius = r.excl_radius;
+    if (r.n_excl > 0) {
+        if (!r.excl_host) return fail(IBO_ERR_ARG, "excl_host is NULL");
+        IBO_TRY(g->excl.ensure((size_t)r.n_excl * g->D));
+        HIP_TRY(hipMemcpyAsync(g->excl.p, r.excl_host, sizeof(double) * r.n_excl * g->D, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        a.n_excl = r.n_excl; a.excl = g->excl.p;
+    }
+    a.index_base = r.index_base;
+    a.out_mu = r.mu_dev; a.out_s2 = r.s2_dev; a.out_acq = r.acq_dev;
+    const int64_t ntiles = (r.M + 63) / 64;
+    IBO_TRY(g->partv.ensure(2 * ntiles)); IBO_TRY(g->parti.ensure(2 * ntiles));     // sweep2 has 32-candidate tiles
+    IBO_TRY(g->res_v.ensure(1)); IBO_TRY(g->res_i.ensure(1));
+    a.part_val = g->partv.p; a.part_idx = g->parti.p;
+    const bool want_best = r.best_val || r.best_idx || r.device_result;
+    a.result_val = want_best ? g->res_v.p : nullptr; a.result_idx = want_best ? g->res_i.p : nullptr;
+    SweepRoute route;
+    IBO_TRY(choose_route(r.M, a.Npad, a.dot_form, g_force_path, &route));
+    switch (route) {
+    case ROUTE_SMALL2: IBO_TRY(sweep_small2(g, a, r)); break;
+    case ROUTE_SPLIT: IBO_TRY(sweep_split_or_gemv(g, a, false)); break;
+    case ROUTE_GEMV: IBO_TRY(sweep_split_or_gemv(g, a, true)); break;
+    case ROUTE_SWEEP2: IBO_TRY(r.incremental ? sweep_sweep2_kept(g, a, r) : sweep_sweep2(g, a)); break;
+    case ROUTE_TILE: IBO_TRY(sweep_tile(g, a)); break;
+    }
+    if (!r.best_val && !r.best_idx) return IBO_OK;        // internal callers that only want the per-point outputs (or the result on the device)
     double hv; int64_t hi;
     HIP_TRY(hipMemcpyAsync(&hv, g->res_v.p, sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&hi, g->res_i.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(hipEventElapsedTime(&g->sweep_ms, g->ev0, g->ev1));
     gpu_time_add(g->device, g->sweep_ms);
-    if (best_val) *best_val = hv;
-    if (best_idx) *best_idx = hi;
+    if (r.best_val) *r.best_val = hv;
+    if (r.best_idx) *r.best_idx = hi;
     return IBO_OK;
+}
+
+// the leading arguments of ibo_acq_sweep, which three entry points carry in ibo_abi.h's order, as a request
+static SweepRequest abi_request(int64_t M, const double *cand_dev, int acq, double parm, int erf_mode, double clamp_lo, double ymax,
+                                int n_excl, const double *excl_host, double excl_radius, int64_t index_base)
+{
+    SweepRequest r;
+    r.M = M; r.cand_dev = cand_dev; r.acq = acq; r.parm = parm; r.erf_mode = erf_mode; r.clamp_lo = clamp_lo; r.ymax = ymax;
+    r.n_excl = n_excl; r.excl_host = excl_host; r.excl_radius = excl_radius; r.index_base = index_base;
+    return r;
 }
 
 extern "C" int ibo_acq_sweep(ibo_gp_t *g, int64_t M, const double *cand_dev, int acq, double parm, int erf_mode,
@@ -226,8 +294,9 @@ extern "C" int ibo_acq_sweep(ibo_gp_t *g, int64_t M, const double *cand_dev, int
 {
     if (!g) return fail(IBO_ERR_ARG, "gp is NULL");
     IBO_TRY(use_device(g->device));
-    return run_sweep(g, M, cand_dev, acq, parm, erf_mode, clamp_lo, ymax, n_excl, excl_host, excl_radius,
-                     index_base, mu_dev, s2_dev, acq_dev, best_val, best_idx);
+    SweepRequest r = abi_request(M, cand_dev, acq, parm, erf_mode, clamp_lo, ymax, n_excl, excl_host, excl_radius, index_base);
+    r.mu_dev = mu_dev; r.s2_dev = s2_dev; r.acq_dev = acq_dev; r.best_val = best_val; r.best_idx = best_idx;
+    return run_sweep(g, r);
 }
 
 extern "C" int ibo_acq_sweep_incremental(ibo_gp_t *g, int64_t M, const double *cand_dev, int acq, double parm, int erf_mode,
@@ -237,8 +306,10 @@ extern "C" int ibo_acq_sweep_incremental(ibo_gp_t *g, int64_t M, const double *c
 {
     if (!g) return fail(IBO_ERR_ARG, "gp is NULL");
     IBO_TRY(use_device(g->device));
-    return run_sweep(g, M, cand_dev, acq, parm, erf_mode, clamp_lo, ymax, n_excl, excl_host, excl_radius,
-                     index_base, mu_dev, s2_dev, acq_dev, best_val, best_idx, true);
+    SweepRequest r = abi_request(M, cand_dev, acq, parm, erf_mode, clamp_lo, ymax, n_excl, excl_host, excl_radius, index_base);
+    r.mu_dev = mu_dev; r.s2_dev = s2_dev; r.acq_dev = acq_dev; r.best_val = best_val; r.best_idx = best_idx;
+    r.incremental = true;
+    return run_sweep(g, r);
 }
 
 // The sharded sweep's step in one call (the loop of ego/acquisition/gallery.py:93-134 cut over ranks): this rank's block is
@@ -252,8 +323,9 @@ extern "C" int ibo_acq_sweep_exchange(ibo_gp_t *g, ibo_comm_t *c, int incrementa
 {
     if (!g || !c) return fail(IBO_ERR_ARG, "NULL argument");
     IBO_TRY(use_device(g->device));
-    IBO_TRY(run_sweep(g, M, cand_dev, acq, parm, erf_mode, clamp_lo, ymax, n_excl, excl_host, excl_radius, index_base, nullptr, nullptr, nullptr,
-                      nullptr, nullptr, incremental != 0, true, false, nullptr, true));
+    SweepRequest r = abi_request(M, cand_dev, acq, parm, erf_mode, clamp_lo, ymax, n_excl, excl_host, excl_radius, index_base);
+    r.incremental = incremental != 0; r.device_result = true;
+    IBO_TRY(run_sweep(g, r));
     IBO_TRY(ibo_comm_exchange_dev(c, g->stream, g->res_v.p, g->res_i.p, cand_dev, g->D, index_base, local_val, local_idx, best_val, best_idx,
                                   best_x, best_rank));
     HIP_TRY(hipEventElapsedTime(&g->sweep_ms, g->ev0, g->ev1));      // (the exchange has synchronised the stream)
@@ -313,6 +385,33 @@ extern "C" int ibo_last_sweep_kernel_ms(ibo_gp_t *g, float *ms, const char **ker
     return IBO_OK;
 }
 
+// Host batches hand their results over as one block: (mu, s2, acq) restricted to the wanted ones, contiguous in that order, m values each.
+struct Packed3 { double *p[3]; int n; };         // p[k]: where output k of such a block lies (NULL: not wanted); n: how many are
+static Packed3 pack3(double *base, size_t m, const double *mu, const double *s2, const double *acq)
+{
+    Packed3 w = {{nullptr, nullptr, nullptr}, 0};
+    const double *want[3] = {mu, s2, acq};
+    for (int k = 0; k < 3; k++)
+        if (want[k]) w.p[k] = base + m * w.n++;
+    return w;
+}
+// a block in host memory -> the caller's arrays
+static void unpack3(const double *base, size_t m, double *mu, double *s2, double *acq)
+{
+    const Packed3 w = pack3(const_cast<double *>(base), m, mu, s2, acq);
+    double *dst[3] = {mu, s2, acq};
+    for (int k = 0; k < 3; k++)
+        if (dst[k]) memcpy(dst[k], w.p[k], sizeof(double) * m);
+}
+// the request of a host batch: per-candidate outputs into such a block at `base`, no arg-max
+static SweepRequest batch_request(int64_t m, const double *cand_dev, int acq, double parm, int erf_mode, double clamp_lo, double ymax, const Packed3 &out)
+{
+    SweepRequest r;
+    r.M = m; r.cand_dev = cand_dev; r.acq = acq; r.parm = parm; r.erf_mode = erf_mode; r.clamp_lo = clamp_lo; r.ymax = ymax;
+    r.mu_dev = out.p[0]; r.s2_dev = out.p[1]; r.acq_dev = out.p[2];
+    return r;
+}
+
 // Large host-in / host-out batches (GP.posteriors(X) on 10^5..10^7 NumPy rows): chunks of 2^17 points go through
 // two sets of pinned + device buffers; the upload of chunk c+1 and the download of chunk c-1 run on their own
 // streams while chunk c is in the sweep kernel, so the call costs about the kernel time, not kernel + PCIe +
@@ -331,7 +430,6 @@ static int eval_host_points_pipelined(ibo_gp *g, int64_t M, const double *Q_host
             HIP_TRY(hipEventCreateWithFlags(&g->pe_out[b], hipEventDisableTiming));
         }
     }
-    const int nout = (mu_host ? 1 : 0) + (s2_host ? 1 : 0) + (acq_host ? 1 : 0);
     IBO_TRY(g->cand.ensure((size_t)(2 * CH) * D));
     IBO_TRY(g->outs.ensure((size_t)(2 * CH) * 3));
     IBO_TRY(ensure_pinned(g, (size_t)(2 * CH) * (D + 3)));
@@ -344,10 +442,7 @@ static int eval_host_points_pipelined(ibo_gp *g, int64_t M, const double *Q_host
         const int b = (int)(c & 1);
         const int64_t m = (c + 1 < nch) ? CH : M - c * CH;
         HIP_TRY(hipEventSynchronize(g->pe_out[b]));
-        int k = 0;
-        if (mu_host) memcpy(mu_host + c * CH, pin_out[b] + m * k++, sizeof(double) * m);
-        if (s2_host) memcpy(s2_host + c * CH, pin_out[b] + m * k++, sizeof(double) * m);
-        if (acq_host) memcpy(acq_host + c * CH, pin_out[b] + m * k++, sizeof(double) * m);
+        unpack3(pin_out[b], (size_t)m, mu_host ? mu_host + c * CH : nullptr, s2_host ? s2_host + c * CH : nullptr, acq_host ? acq_host + c * CH : nullptr);
         return IBO_OK;
     };
     for (int64_t c = 0; c < nch; c++) {
@@ -358,15 +453,11 @@ static int eval_host_points_pipelined(ibo_gp *g, int64_t M, const double *Q_host
         HIP_TRY(hipMemcpyAsync(dev_in[b], pin_in[b], sizeof(double) * m * D, hipMemcpyHostToDevice, g->h2d_stream));
         HIP_TRY(hipEventRecord(g->pe_in[b], g->h2d_stream));
         HIP_TRY(hipStreamWaitEvent(g->stream, g->pe_in[b], 0));
-        int k = 0;
-        double *dmu = mu_host ? dev_out[b] + m * k++ : nullptr;
-        double *ds2 = s2_host ? dev_out[b] + m * k++ : nullptr;
-        double *dacq = acq_host ? dev_out[b] + m * k++ : nullptr;
-        IBO_TRY(run_sweep(g, m, dev_in[b], acq, parm, erf_mode, clamp_lo, ymax, 0, nullptr, 0.0, 0, dmu, ds2, dacq,
-                          nullptr, nullptr));
+        const Packed3 out = pack3(dev_out[b], (size_t)m, mu_host, s2_host, acq_host);
+        IBO_TRY(run_sweep(g, batch_request(m, dev_in[b], acq, parm, erf_mode, clamp_lo, ymax, out)));
         HIP_TRY(hipEventRecord(g->pe_k[b], g->stream));
         HIP_TRY(hipStreamWaitEvent(g->d2h_stream, g->pe_k[b], 0));
-        HIP_TRY(hipMemcpyAsync(pin_out[b], dev_out[b], sizeof(double) * m * nout, hipMemcpyDeviceToHost, g->d2h_stream));
+        HIP_TRY(hipMemcpyAsync(pin_out[b], dev_out[b], sizeof(double) * m * out.n, hipMemcpyDeviceToHost, g->d2h_stream));
         HIP_TRY(hipEventRecord(g->pe_out[b], g->d2h_stream));
     }
     if (nch >= 2) IBO_TRY(drain(nch - 2));
@@ -391,17 +482,12 @@ static int eval_host_points(ibo_gp *g, int64_t M, const double *Q_host, int acq,
     // kernels read the few KB of candidates from it and store the results into it (two ~10 us launches per batch).
     const bool zero_copy = M <= 8192;
     if (!zero_copy) HIP_TRY(hipMemcpyAsync(g->cand.p, pin_in, sizeof(double) * M * g->D, hipMemcpyHostToDevice, s));
-    // outputs are contiguous in the order (mu, s2, acq) restricted to the wanted ones
-    int nout = 0;
-    double *obase = zero_copy ? pin_out : g->outs.p;
-    double *dmu = nullptr, *ds2 = nullptr, *dacq = nullptr;
-    if (mu_host) dmu = obase + (size_t)M * nout++;
-    if (s2_host) ds2 = obase + (size_t)M * nout++;
-    if (acq_host) dacq = obase + (size_t)M * nout++;
+    const Packed3 out = pack3(zero_copy ? pin_out : g->outs.p, (size_t)M, mu_host, s2_host, acq_host);
+    SweepRequest r = batch_request(M, zero_copy ? pin_in : g->cand.p, acq, parm, erf_mode, clamp_lo, ymax, out);
+    if (zero_copy) { r.cand_host = pin_in; r.signal = true; r.timed = false; }      // small batches: no kernel-time events either
     g->signal_pending = false;
-    IBO_TRY(run_sweep(g, M, zero_copy ? pin_in : g->cand.p, acq, parm, erf_mode, clamp_lo, ymax, 0, nullptr, 0.0, 0, dmu, ds2, dacq,
-                      nullptr, nullptr, false, !zero_copy, zero_copy, zero_copy ? pin_in : nullptr));    // small batches: no kernel-time events either
-    if (!zero_copy) HIP_TRY(hipMemcpyAsync(pin_out, g->outs.p, sizeof(double) * M * nout, hipMemcpyDeviceToHost, s));
+    IBO_TRY(run_sweep(g, r));
+    if (!zero_copy) HIP_TRY(hipMemcpyAsync(pin_out, g->outs.p, sizeof(double) * M * out.n, hipMemcpyDeviceToHost, s));
     if (zero_copy) {
         // a batch of this size is back in tens of microseconds: spin for a moment before handing the thread to the runtime's
         // blocking wait (whose wake-up alone costs about as much as the batch) -- on the word small2.hip's last kernel stores
@@ -423,10 +509,7 @@ static int eval_host_points(ibo_gp *g, int64_t M, const double *Q_host, int acq,
             if ((w1.tv_sec - w0.tv_sec) * 1e6 + (w1.tv_nsec - w0.tv_nsec) * 1e-3 > 300.0) { HIP_TRY(hipStreamSynchronize(s)); break; }
         }
     } else HIP_TRY(hipStreamSynchronize(s));
-    nout = 0;
-    if (mu_host) memcpy(mu_host, pin_out + (size_t)M * nout++, sizeof(double) * M);
-    if (s2_host) memcpy(s2_host, pin_out + (size_t)M * nout++, sizeof(double) * M);
-    if (acq_host) memcpy(acq_host, pin_out + (size_t)M * nout++, sizeof(double) * M);
+    unpack3(pin_out, (size_t)M, mu_host, s2_host, acq_host);
     return IBO_OK;
 }
 
@@ -480,8 +563,7 @@ extern "C" int ibo_acq_grad_batch(ibo_gp_t *g, int64_t M, const double *Q_host, 
     memset(&a, 0, sizeof(a));
     a.kp = g->kp; a.N = g->N; a.Npad = g->Npad; a.DP = g->DP;
     a.Xp = g->Xp.p; a.W = g->W.p; a.alphaY = g->alphaY.p; a.alpha1 = g->alpha1.p;
-    a.prior.nb = g->nb; a.prior.theta = g->ptheta; a.prior.means = g->pmeans.p; a.prior.beta = g->pbeta.p;
-    a.prior.lowerb = g->plowerb.p; a.prior.width = g->pwidth.p;
+    a.prior = prior_of(g);
     a.noise = g->noise; a.clamp_lo = clamp_lo; a.ymax = (ymax == ymax) ? ymax : g->maxY; a.parm = parm;
     a.acq = acq; a.erf_mode = erf_mode;
     a.TM = pl.TM; a.KC = pl.KC; a.nsplit = pl.nsplit; a.nparts = pl.nparts;

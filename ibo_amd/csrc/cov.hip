@@ -75,10 +75,7 @@ __global__ void __launch_bounds__(256) cov_kstar_kernel(KParams kp, const double
     if (j >= Npad) return;
     double k = 0.0;
     if (c < m && j < N) {
-        const double *xr = Xp + (size_t)j * DP;
-        double z = 0.0;
-        for (int d = 0; d < D; d++) { const double u = xs[d] - xr[d]; z = fma(kp.w[d] * u, u, z); }
-        k = cov_from_z_rt(kp.family, z, kp.sf2);
+        k = cov_from_z_rt(kp.family, wsqdist_dev(kp.w, xs, Xp + (size_t)j * DP, D), kp.sf2);
     }
     Kt[(size_t)c * Npad + j] = k;
 }
@@ -142,10 +139,7 @@ __global__ void __launch_bounds__(256) cov_syrk_kernel(KParams kp, const double 
                 } else if (a == b) {
                     v = diag - acc[i][j][e];
                 } else {
-                    const double *qa = Q + (size_t)a * D, *qb = Q + (size_t)b * D;
-                    double z = 0.0;
-                    for (int d = 0; d < D; d++) { const double u = qa[d] - qb[d]; z = fma(kp.w[d] * u, u, z); }
-                    v = cov_from_z_rt(kp.family, z, kp.sf2) - acc[i][j][e];
+                    v = cov_from_z_rt(kp.family, wsqdist_dev(kp.w, Q + (size_t)a * D, Q + (size_t)b * D, D), kp.sf2) - acc[i][j][e];
                 }
                 S[(size_t)a * lds + b] = v;
                 if (a != b) S[(size_t)b * lds + a] = v;

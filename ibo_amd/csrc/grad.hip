@@ -25,8 +25,7 @@ __global__ void __launch_bounds__(256) grad_kstar_kernel(GradArgs a, const doubl
     double k = 0.0, h = 0.0;
     if (i < a.N) {
         const double *xr = a.Xp + (size_t)i * a.DP;
-        double z = 0.0;
-        for (int d = 0; d < D; d++) { const double t = xs[d] - xr[d]; z = fma(a.kp.w[d] * t, t, z); }
+        const double z = wsqdist_dev(a.kp.w, xs, xr, D);
         const double sf2 = a.kp.sf2;
         if (a.kp.family == FAM_SE) {
             k = sf2 * exp(-0.5 * z);
@@ -130,22 +129,6 @@ __device__ __forceinline__ double grad_u_at(const GradArgs &a, int mc, int c, in
     return v;
 }
 
-// RBF-network prior mean at x (the sum of s2_finish, in its order)
-__device__ __forceinline__ double grad_prior_m(const GradArgs &a, const double *x)
-{
-    const int D = a.kp.D;
-    double m = 0.0;
-    for (int j = 0; j < a.prior.nb; j++) {
-        double d = 0.0;
-        for (int e = 0; e < D; e++) {
-            const double t = (x[e] - a.prior.lowerb[e]) / a.prior.width[e] - a.prior.means[(size_t)j * D + e];
-            d += t * t;
-        }
-        m += a.prior.beta[j] * exp(-a.prior.theta * d);
-    }
-    return m;
-}
-
 // Partial sums of one row part [i0, i1) for one candidate.  Thread (g, d): d = tid % DP, g = tid / DP; rows i0 + g, i0 + g + G, ...
 // Out: E[(c * nparts + p) * ES + ..] = [aY.k*, a1.k*, |t|^2, S_mu[DP], S_u[DP]], ES = 3 + 2 DP
 __global__ void __launch_bounds__(256) grad_epi_part_kernel(GradArgs a, const double *cand, int mc)
@@ -157,7 +140,7 @@ __global__ void __launch_bounds__(256) grad_epi_part_kernel(GradArgs a, const do
     const int tid = threadIdx.x, p = blockIdx.x, c = blockIdx.y, D = a.kp.D, DP = a.DP, G = 256 / DP;
     if (tid < D) xs[tid] = cand[(size_t)c * D + tid];
     __syncthreads();
-    if (tid == 0) mprior = a.prior.nb > 0 ? grad_prior_m(a, xs) : 0.0;
+    if (tid == 0) mprior = prior_mean_dev(a.prior, D, [&](int j) { return xs[j]; });
     __syncthreads();
     const double m = mprior;
     const int d = tid % DP, g = tid / DP;
@@ -194,17 +177,6 @@ __global__ void __launch_bounds__(256) grad_epi_part_kernel(GradArgs a, const do
     }
 }
 
-__device__ __forceinline__ void grad_cdf_pdf(int erf_mode, double z, double *cdf, double *pdf)
-{
-    if (erf_mode == 0) {
-        *cdf = 0.5 * (1.0 + erf(z / sqrt(2.0)));
-        *pdf = exp(-(z * z / 2.0)) / sqrt(2.0 * M_PI);
-    } else {
-        *cdf = 0.5 * (1.0 + erf_nr_dev(z * 0.707106));
-        *pdf = exp(-(z * z / 2.0)) * 0.398942;
-    }
-}
-
 // one candidate per 64-lane workgroup, lane = dimension
 __global__ void __launch_bounds__(64) grad_finish_kernel(GradArgs a, const double *cand, int mc, double *dmu, double *ds2, double *dacq)
 {
@@ -220,20 +192,8 @@ __global__ void __launch_bounds__(64) grad_finish_kernel(GradArgs a, const doubl
         if (d < DP) { smu += e[3 + d]; su += e[3 + DP + d]; }
     }
     if (d >= D) return;
-    double m = 0.0, dm = 0.0;
-    if (a.prior.nb > 0) {
-        const double x = xs[d], ud = (x - a.prior.lowerb[d]) / a.prior.width[d];
-        for (int j = 0; j < a.prior.nb; j++) {
-            double r = 0.0;
-            for (int e = 0; e < D; e++) {
-                const double t = (xs[e] - a.prior.lowerb[e]) / a.prior.width[e] - a.prior.means[(size_t)j * D + e];
-                r += t * t;
-            }
-            const double be = a.prior.beta[j] * exp(-a.prior.theta * r);
-            m += be;
-            dm += be * (-2.0 * a.prior.theta) * (ud - a.prior.means[(size_t)j * D + d]) / a.prior.width[d];
-        }
-    }
+    double dm = 0.0;
+    const double m = prior_mean_dev(a.prior, D, [&](int e) { return xs[e]; }, d, &dm);
     const double w = a.kp.w[d];
     const double mu = a.prior.nb > 0 ? m + sY - m * s1 : sY;
     const double gmu = dm * (1.0 - s1) + w * smu;
@@ -251,7 +211,7 @@ __global__ void __launch_bounds__(64) grad_finish_kernel(GradArgs a, const doubl
         else {
             const double z = (mu - a.ymax - a.parm) / sig;
             double cdf, pdf;
-            grad_cdf_pdf(a.erf_mode, z, &cdf, &pdf);
+            gauss_cdf_pdf_dev(a.erf_mode, z, &cdf, &pdf);
             g = a.acq == 1 ? pdf * (gmu - z * gsig) / sig : cdf * gmu + pdf * gsig;
         }
         dacq[o] = g;

@@ -21,8 +21,13 @@
 //   IBO_DOT_GUARD_NLML  the same for ibo_nlml_grid's covariance pass, on the per-dimension bound sum_d w_d max_k x_kd^2 over every theta-point of
 //                       the call (abi_nlml.hip).  At its edge the likelihood value moves by up to 2e-8 relative (1e-10 in the unit cube),
 //                       which no optimiser notices: left where it was.
+//   IBO_DOT_PULL_IN     |c~|^2 beyond which a CANDIDATE of a dot-form sweep is pulled in to that radius (s2_stage_candidates in sweep2_dev.h).
+//                       775 length scales from the origin is at least 630 from any admitted observation (|x~| <= 142 under IBO_DOT_GUARD),
+//                       where k* = 0 exactly for every family: the value does not change, and the exponent stays within what s2_exp's
+//                       integer arithmetic covers (|y| < 7e5).
 #define IBO_DOT_GUARD 2e4
 #define IBO_DOT_GUARD_NLML 1e5
+#define IBO_DOT_PULL_IN 6e5
 
 // |x~|^2 of one point under a kernel's scaling (host side: the guards above)
 static inline double ibo_scaled_norm2(const double *sw, const double *x, int D)
@@ -47,6 +52,15 @@ struct KParams {
     double w[IBO_DMAX];         // zero beyond D
     double sw[IBO_DMAX];        // sqrt(w): coordinates are pre-scaled for the sweep's k* generation
 };
+
+// z of two unscaled points: the difference first, then one FMA per dimension in ascending order (cov.hip, grad.hip).  The sweeps' k*
+// generation scales first or takes the dot form -- other roundings, kept where they are.
+__device__ __forceinline__ double wsqdist_dev(const double *w, const double *a, const double *b, int D)
+{
+    double z = 0.0;
+    for (int d = 0; d < D; d++) { const double u = a[d] - b[d]; z = fma(w[d] * u, u, z); }
+    return z;
+}
 
 template <int FAM>
 __device__ __forceinline__ double cov_from_z(double z, double sf2)
@@ -147,6 +161,28 @@ struct PriorDev {
     const double *width;    // D
 };
 
+// The RBF-network prior mean m(x) = sum_i beta_i exp(-theta |u - c_i|^2), u = (x - lowerb) / width, basis functions in ascending order: the
+// ONE sum behind every mean the library returns (sweep epilogue, gradient, leave-one-out).  X(j): coordinate j of the point (a lambda, so
+// that the system-scope loads of finish_candidate<true> go through the same body).  dm (grad_finish_kernel): also receives dm / dx_dd, every
+// term formed from the very beta_i exp(..) that enters the mean.
+template <typename XF>
+__device__ __forceinline__ double prior_mean_dev(const PriorDev &p, int D, XF X, int dd = 0, double *dm = nullptr)
+{
+    double m = 0.0, g = 0.0;
+    for (int i = 0; i < p.nb; i++) {
+        double d = 0.0;
+        for (int j = 0; j < D; j++) {
+            const double t = (X(j) - p.lowerb[j]) / p.width[j] - p.means[(size_t)i * D + j];
+            d += t * t;
+        }
+        const double be = p.beta[i] * exp(-p.theta * d);
+        m += be;
+        if (dm) g += be * (-2.0 * p.theta) * ((X(dd) - p.lowerb[dd]) / p.width[dd] - p.means[(size_t)i * D + dd]) / p.width[dd];
+    }
+    if (dm) *dm = g;
+    return m;
+}
+
 // acquisition value (positive) from (mu, sigma); mirrors
 // cpp/optimizeGP.cpp:194-236 (libm) and ego/acquisition/__init__.py:68-71,107-110,150-164
 // with CDF/PDF of ego/gaussianprocess/__init__.py:55-77 (NR).
@@ -166,6 +202,18 @@ __device__ __forceinline__ double erf_nr_dev(double z)
     return z >= 0.0 ? ans : -ans;
 }
 
+// Gaussian cdf and pdf at z in either erf flavour (NR: with the reference's truncated 1 / sqrt 2 and 1 / sqrt(2 pi))
+__device__ __forceinline__ void gauss_cdf_pdf_dev(int erf_mode, double z, double *cdf, double *pdf)
+{
+    if (erf_mode == 0) {
+        *cdf = 0.5 * (1.0 + erf(z / sqrt(2.0)));
+        *pdf = exp(-(z * z / 2.0)) / sqrt(2.0 * M_PI);
+    } else {
+        *cdf = 0.5 * (1.0 + erf_nr_dev(z * 0.707106));
+        *pdf = exp(-(z * z / 2.0)) * 0.398942;
+    }
+}
+
 __device__ __forceinline__ double acq_value_dev(int acq, int erf_mode, double mu, double sigma,
                                                 double ymax, double parm)
 {
@@ -173,13 +221,7 @@ __device__ __forceinline__ double acq_value_dev(int acq, int erf_mode, double mu
     double ydiff = mu - ymax - parm;
     double Z = ydiff / sigma;
     double cdf, pdf;
-    if (erf_mode == 0) {
-        cdf = 0.5 * (1.0 + erf(Z / sqrt(2.0)));
-        pdf = exp(-(Z * Z / 2.0)) / sqrt(2.0 * M_PI);
-    } else {
-        cdf = 0.5 * (1.0 + erf_nr_dev(Z * 0.707106));
-        pdf = exp(-(Z * Z / 2.0)) * 0.398942;
-    }
+    gauss_cdf_pdf_dev(erf_mode, Z, &cdf, &pdf);
     if (acq == 1) return cdf;
     return ydiff * cdf + sigma * pdf;
 }
@@ -232,13 +274,51 @@ struct SweepArgs {
     // the launch at hand, the model's rows now, W y (the drift margin's source), and whether tiles may be left stale at all
     int *tile_rows; int *tile_sel; const double *wy; int rank_hi; int part_lazy;
     int part_level, part_nlev;                 // this launch's level (>= 1: only tiles whose tile_done is part_level - 1 run), and how many levels there are
-    double nu_max;                             // bound on |(W k*)_i| for any candidate: sf2_k / sqrt(sf2_fit) (abi.hip: run_sweep); the drift margin's factor
+    double nu_max;                             // bound on |(W k*)_i| for any candidate: sf2_k / sqrt(sf2_fit) (abi_sweep.hip: sweep_sweep2_kept); the drift margin's factor
     unsigned long long *part_best;             // acq_bound_kernel: running maximum over the COMPLETE tiles, same encoding
     // small2.hip: when set, the last workgroup of the last kernel stores done_seq there (host-visible memory) after all
     // results are out -- the host spins on that word instead of going through an event
     unsigned long long *done_flag; unsigned long long done_seq; unsigned *done_count;
     const double *cand_host;                   // the same candidates where the HOST can read them (pinned staging), or NULL
 };
+
+// The acquisition epilogue of one candidate, for every sweep kernel: prior mean, variance clamp, EI / PI / UCB, exclusion balls, optional
+// outputs; returns the value.  Coordinates are read from global memory where needed (prior, exclusion balls) so that no per-lane
+// coordinate array exists (dynamic indexing would put it in scratch).
+// SYS: the host spins on a completion flag instead of waiting for the launch to end (small2.hip: small_finish_kernel<true>):
+// coordinates and results go through system-scope accesses, which leave no L2 line to be written back before the flag
+// (a.kp.D where it is used and the prior behind its own test, not a local copy: sweep_mfma_kernel's register allocation is at its limit, and
+// with a local D its 32- and 64-dimensional difference-form instances take 8 more bytes of scratch per lane)
+template <bool SYS = false>
+__device__ __forceinline__ double finish_candidate(const SweepArgs &a, const double *xp, double q, double muY, double mu1,
+                                                   int64_t li, bool valid, bool &excluded)
+{
+    auto X = [&](int j) { return SYS ? __hip_atomic_load(xp + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : xp[j]; };
+    const double m = (a.prior.nb > 0) ? prior_mean_dev(a.prior, a.kp.D, X) : 0.0;
+    const double mu = (a.prior.nb > 0) ? (m + muY - m * mu1) : muY;
+    double s2 = 1.0 + a.noise - q;
+    if (s2 < a.clamp_lo) s2 = a.clamp_lo;
+    else if (s2 > 10.0) s2 = 10.0;
+    const double val = (a.acq == 3) ? mu : acq_value_dev(a.acq, a.erf_mode, mu, sqrt(s2), a.ymax, a.parm);
+    excluded = false;
+    for (int e = 0; e < a.n_excl; e++) {
+        double d2 = 0.0;
+        for (int j = 0; j < a.kp.D; j++) { double t = X(j) - a.excl[(size_t)e * a.kp.D + j]; d2 += t * t; }
+        if (!(sqrt(d2) > a.excl_radius)) excluded = true;
+    }
+    if (valid) {
+        if (SYS) {                                      // (the flag may be seen before the launch ends: no launch boundary flushes these)
+            if (a.out_mu) __hip_atomic_store(a.out_mu + li, mu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (a.out_s2) __hip_atomic_store(a.out_s2 + li, s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (a.out_acq) __hip_atomic_store(a.out_acq + li, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        } else {
+            if (a.out_mu) a.out_mu[li] = mu;
+            if (a.out_s2) a.out_s2[li] = s2;
+            if (a.out_acq) a.out_acq[li] = val;
+        }
+    }
+    return val;
+}
 
 int launch_sweep_mfma(const SweepArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 int launch_sweep_gemv(const SweepArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1);

@@ -31,21 +31,6 @@ __device__ __forceinline__ double lo_block_sum(double v, double *red)
     return red[0];
 }
 
-// RBF-network prior mean at x (grad.hip: grad_prior_m)
-__device__ __forceinline__ double lo_prior_m(const PriorDev &p, const double *x, int D)
-{
-    double m = 0.0;
-    for (int j = 0; j < p.nb; j++) {
-        double d = 0.0;
-        for (int e = 0; e < D; e++) {
-            const double t = (x[e] - p.lowerb[e]) / p.width[e] - p.means[(size_t)j * D + e];
-            d += t * t;
-        }
-        m += p.beta[j] * exp(-p.theta * d);
-    }
-    return m;
-}
-
 __global__ void __launch_bounds__(64) loo_diag_kernel(const double *__restrict__ W, size_t ldw, int N, double *__restrict__ d)
 {
     const int k0 = blockIdx.x * 64, i = k0 + threadIdx.x;
@@ -76,7 +61,7 @@ __global__ void __launch_bounds__(256) loo_point_kernel(PriorDev prior, const do
     double acc = 0.0;
     for (int i = threadIdx.x; i < N; i += 256) {
         double c = aY[i];
-        if (prior.nb > 0) c = fma(-lo_prior_m(prior, Xp + (size_t)i * DP, D), a1[i], c);
+        if (prior.nb > 0) c = fma(-prior_mean_dev(prior, D, [&](int j) { return Xp[(size_t)i * DP + j]; }), a1[i], c);
         const double di = dsrc[(size_t)i * dstride];
         if (mu) mu[i] = Y[i] - c / di;
         if (s2) s2[i] = 1.0 / di;

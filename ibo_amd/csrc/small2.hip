@@ -348,7 +348,7 @@ __device__ __forceinline__ bool small_finish_body(const SweepArgs &a, const doub
 #pragma unroll
     for (int u = 0; u < SM_FIN_P; u++) { q += lds_q[u][lane]; my += lds_y[u][lane]; m1 += lds_1[u][lane]; }
     bool excl;
-    double val = s2_finish<SYSOUT>(a, a.cand + ci * a.kp.D, q, my, m1, li, valid, excl);
+    double val = finish_candidate<SYSOUT>(a, a.cand + ci * a.kp.D, q, my, m1, li, valid, excl);
     int64_t idx = a.index_base + li;
     if (!valid || excl || !(val == val)) { val = -INFINITY; idx = INT64_MAX; }
     for (int o = 32; o > 0; o >>= 1) {

@@ -25,45 +25,6 @@
 
 #define TC 64          // candidates per workgroup
 
-__device__ __forceinline__ double prior_mu_dev(const PriorDev &p, int D, const double *x)
-{
-    double m = 0.0;
-    for (int i = 0; i < p.nb; i++) {
-        double d = 0.0;
-        for (int j = 0; j < D; j++) {
-            double t = (x[j] - p.lowerb[j]) / p.width[j] - p.means[(size_t)i * D + j];
-            d += t * t;
-        }
-        m += p.beta[i] * exp(-p.theta * d);
-    }
-    return m;
-}
-
-// finish one candidate: returns the acquisition value, writes optional outputs
-__device__ __forceinline__ double finish_candidate(const SweepArgs &a, const double *x, double q, double muY,
-                                                   double mu1, int64_t gidx, bool valid, bool &excluded)
-{
-    double m = 0.0;
-    if (a.prior.nb > 0) m = prior_mu_dev(a.prior, a.kp.D, x);
-    double mu = (a.prior.nb > 0) ? (m + muY - m * mu1) : muY;
-    double s2 = 1.0 + a.noise - q;
-    if (s2 < a.clamp_lo) s2 = a.clamp_lo;
-    else if (s2 > 10.0) s2 = 10.0;
-    double val = (a.acq == 3) ? mu : acq_value_dev(a.acq, a.erf_mode, mu, sqrt(s2), a.ymax, a.parm);
-    excluded = false;
-    for (int e = 0; e < a.n_excl; e++) {
-        double d2 = 0.0;
-        for (int j = 0; j < a.kp.D; j++) { double t = x[j] - a.excl[(size_t)e * a.kp.D + j]; d2 += t * t; }
-        if (!(sqrt(d2) > a.excl_radius)) excluded = true;
-    }
-    if (valid) {
-        if (a.out_mu) a.out_mu[gidx] = mu;
-        if (a.out_s2) a.out_s2[gidx] = s2;
-        if (a.out_acq) a.out_acq[gidx] = val;
-    }
-    return val;
-}
-
 __device__ __forceinline__ void wave_argmax(double &v, int64_t &i)
 {
     for (int o = 32; o > 0; o >>= 1) {
@@ -540,7 +501,7 @@ static int launch_mfma_fam(const SweepArgs &a, int64_t ntiles, hipStream_t s)
         return launch_mfma_split<FAM, false>(a, ntiles, s);
     }
     // large batches reach this kernel only in the difference form: data that admit the dot form go to sweep2.hip
-    // (abi.hip: run_sweep clears dot_form on this route, also when a test forces it)
+    // (abi_sweep.hip: sweep_tile clears dot_form on this route, also when a test forces it)
     return launch_mfma_var<FAM, false>(a, ntiles, s);
 }
 
@@ -568,7 +529,7 @@ bool sweep_gemv_fits(int Npad) { return sizeof(double) * ((size_t)Npad + 12) <= 
 
 int launch_sweep_gemv(const SweepArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
-    if (!sweep_gemv_fits(a.Npad)) return (int)hipErrorInvalidConfiguration;     // (run_sweep reports it before anything is launched)
+    if (!sweep_gemv_fits(a.Npad)) return (int)hipErrorInvalidConfiguration;     // (abi_sweep.hip: choose_route reports it before anything is launched)
     int nrc = a.Npad / 64;
     dim3 grid(nrc, (unsigned)a.M);
     if (sizeof(double) * a.Npad > 64 * 1024) {     // up to 160 KiB of LDS per workgroup on gfx950

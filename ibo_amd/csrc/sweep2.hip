@@ -35,7 +35,7 @@
 
 // second half of the sweep: mean prior, variance clamp, EI / PI / UCB, optional per-candidate outputs, exclusion
 // balls, and a (max value, lowest index) partial per 256 candidates -- all from sweep2_kernel's three numbers per
-// candidate.  Summation order and formulas are those of s2_finish (shared with sweep.hip's epilogue).
+// candidate.  Summation order and formulas are those of finish_candidate (shared with sweep.hip's epilogue).
 __global__ __launch_bounds__(256) void acq_finish_kernel(SweepArgs a)
 {
     __shared__ double sv[4];
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void acq_finish_kernel(SweepArgs a)
     const int64_t gi = valid ? li : a.M - 1;
     bool excl;
     const double q = a.state5 ? (a.qpart[gi] + a.qpart[4 * a.M + gi]) + a.qpart[3 * a.M + gi] : a.qpart[gi];
-    double val = s2_finish(a, a.cand + gi * a.kp.D, q, a.qpart[a.M + gi], a.qpart[2 * a.M + gi], li, valid, excl);
+    double val = finish_candidate(a, a.cand + gi * a.kp.D, q, a.qpart[a.M + gi], a.qpart[2 * a.M + gi], li, valid, excl);
     int64_t idx = a.index_base + li;
     if (!valid || excl || !(val == val)) { val = -INFINITY; idx = INT64_MAX; }
     for (int o = 32; o > 0; o >>= 1) {
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void acq_bound_kernel(SweepArgs a)
         for (int i = a.part_rows; i < a.rank_hi; i++) margin += fabs(a.wy[i]);
         margin = margin > 0.0 ? margin * a.nu_max : 0.0;        // (rows with (W y)_i = 0 exactly move nothing, whatever nu is)
     }
-    double val = s2_finish(a, a.cand + gi * a.kp.D, q, a.qpart[a.M + gi] + margin, a.qpart[2 * a.M + gi], li, valid, excl);
+    double val = finish_candidate(a, a.cand + gi * a.kp.D, q, a.qpart[a.M + gi] + margin, a.qpart[2 * a.M + gi], li, valid, excl);
     if (!valid || excl || !(val == val)) val = -INFINITY;
     for (int o = 16; o > 0; o >>= 1) val = fmax(val, __shfl_xor(val, o));          // the 32 candidates of a tile: half a wave
     if ((threadIdx.x & 31) == 0 && valid) {

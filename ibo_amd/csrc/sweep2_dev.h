@@ -1,6 +1,6 @@
 // sweep2_dev.h -- device helpers shared by the second-generation sweep kernels (sweep2.hip: large batches and the
 // gallery's rank-1 refresh; small2.hip: DIRECT's batches): buffer-resource loads, the table-based exp, the k*
-// value of one exponent, the acquisition epilogue and the per-tile candidate staging.
+// value of one exponent and the per-tile candidate staging (the acquisition epilogue, finish_candidate, is in ibo_common.h).
 #pragma once
 #include "ibo_common.h"
 
@@ -43,53 +43,6 @@ __device__ __forceinline__ double s2_exp(double y, const double *tab)
     return __builtin_amdgcn_ldexp(T * p, ti >> 11);
 }
 
-// acquisition epilogue of one candidate; coordinates are read from global memory where needed (prior,
-// exclusion balls) so that no per-lane coordinate array exists (dynamic indexing would put it in scratch)
-// SYS: the host spins on a completion flag instead of waiting for the launch to end (small2.hip: small_finish_kernel<true>):
-// coordinates and results go through system-scope accesses, which leave no L2 line to be written back before the flag
-template <bool SYS = false>
-__device__ __forceinline__ double s2_finish(const SweepArgs &a, const double *xp, double q, double muY, double mu1,
-                                            int64_t li, bool valid, bool &excluded)
-{
-    const int D = a.kp.D;
-    auto X = [&](int j) { return SYS ? __hip_atomic_load(xp + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : xp[j]; };
-    double m = 0.0;
-    if (a.prior.nb > 0) {
-        for (int i = 0; i < a.prior.nb; i++) {
-            double d = 0.0;
-            for (int j = 0; j < D; j++) {
-                double t = (X(j) - a.prior.lowerb[j]) / a.prior.width[j] - a.prior.means[(size_t)i * D + j];
-                d += t * t;
-            }
-            m += a.prior.beta[i] * exp(-a.prior.theta * d);
-        }
-    }
-    const double mu = (a.prior.nb > 0) ? (m + muY - m * mu1) : muY;
-    double s2 = 1.0 + a.noise - q;
-    if (s2 < a.clamp_lo) s2 = a.clamp_lo;
-    else if (s2 > 10.0) s2 = 10.0;
-    const double val = (a.acq == 3) ? mu : acq_value_dev(a.acq, a.erf_mode, mu, sqrt(s2), a.ymax, a.parm);
-    excluded = false;
-    for (int e = 0; e < a.n_excl; e++) {
-        double d2 = 0.0;
-        for (int j = 0; j < D; j++) { double t = X(j) - a.excl[(size_t)e * D + j]; d2 += t * t; }
-        if (!(sqrt(d2) > a.excl_radius)) excluded = true;
-    }
-    if (valid) {
-        if (SYS) {                                      // (the flag may be seen before the launch ends: no launch boundary flushes these)
-            if (a.out_mu) __hip_atomic_store(a.out_mu + li, mu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            if (a.out_s2) __hip_atomic_store(a.out_s2 + li, s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            if (a.out_acq) __hip_atomic_store(a.out_acq + li, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        } else {
-            if (a.out_mu) a.out_mu[li] = mu;
-            if (a.out_s2) a.out_s2[li] = s2;
-            if (a.out_acq) a.out_acq[li] = val;
-        }
-    }
-    return val;
-}
-
-
 // k* from the exponent y = a_k + b_c + x~.c~ (b_c carries log sf2 for the squared exponential)
 template <int FAM>
 __device__ __forceinline__ double s2_kstar(double y, double sf2, const double *tab)
@@ -101,10 +54,9 @@ __device__ __forceinline__ double s2_kstar(double y, double sf2, const double *t
     return sf2 * poly * s2_exp(-rr, tab);
 }
 
-// TCAND candidates of a tile -> lds_c[cand][KA (+1: odd row stride, conflict-free fragment reads)] = [c~ (D) | 1 | b_c | 0..]  (c~ = c sqrt(w)).  A candidate more than 775
-// length scales from the origin (hence > 630 from every observation: |x~| <= 142 where the dot form is in use, IBO_DOT_GUARD) has k* = 0
-// exactly; it is pulled in to that radius, where k* is still 0, so that the exponent stays within what s2_exp's integer
-// arithmetic covers (|y| < 7e5).  cand: where the candidates are read from (nullptr: a.cand).  Called by the whole workgroup; ends with a barrier.
+// TCAND candidates of a tile -> lds_c[cand][KA (+1: odd row stride, conflict-free fragment reads)] = [c~ (D) | 1 | b_c | 0..]  (c~ = c sqrt(w)).  A candidate
+// beyond IBO_DOT_PULL_IN is pulled in to that radius, where k* is still 0 exactly (ibo_common.h).  The ONE staging of the dot form: sweep2_kernel,
+// sweep2_rank1_kernel and small2.hip's kernels all call it; its two barriers also cover whatever the caller stored to LDS before the call.  cand: where the candidates are read from (nullptr: a.cand).  Called by the whole workgroup; ends with a barrier.
 template <int FAM, int TCAND, int KA, int NT>
 __device__ __forceinline__ void s2_stage_candidates(const SweepArgs &a, int64_t tile0, double *lds_c, const double *cand = nullptr)
 {
@@ -121,10 +73,10 @@ __device__ __forceinline__ void s2_stage_candidates(const SweepArgs &a, int64_t 
     if (tid < TCAND) {
         double n2 = 0.0;
         for (int d = 0; d < D; d++) { const double v = lds_c[tid * (KA + 1) + d]; n2 = fma(v, v, n2); }
-        if (n2 > 6e5) {
-            const double sc = sqrt(6e5 / n2);
+        if (n2 > IBO_DOT_PULL_IN) {
+            const double sc = sqrt(IBO_DOT_PULL_IN / n2);
             for (int d = 0; d < D; d++) lds_c[tid * (KA + 1) + d] *= sc;
-            n2 = 6e5;
+            n2 = IBO_DOT_PULL_IN;
         }
         lds_c[tid * (KA + 1) + D + 1] = fma(-0.5, n2, FAM == FAM_SE ? a.log_sf2 : 0.0);
     }

@@ -75,13 +75,12 @@ __global__ __launch_bounds__(S2_NW * 64) void sweep2_kernel(SweepArgs a)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int64_t tile0 = (int64_t)tb * TCAND;
-    const int D = a.kp.D;
 #ifdef IBO_STAMPS   // diagnostic build (tools/stamp_sweep2.py): a tile's entry / prologue done / panels done / exit, and where it ran
     unsigned long long st2[4];
     st2[0] = __builtin_amdgcn_s_memrealtime();
 #endif
 
-    // ---- candidates of this tile: c~ = c sqrt(w), then the two extra columns 1 and b_c
+    // ---- the exp table and the alpha vectors, then the candidates of this tile (the staging's barriers cover all three)
     const int NA128 = (a.Npad + 127) & ~127;
     lds_tab[tid] = a.exp_tab[tid];
     lds_tab[tid + 1024] = a.exp_tab[tid + 1024];
@@ -92,27 +91,7 @@ __global__ __launch_bounds__(S2_NW * 64) void sweep2_kernel(SweepArgs a)
             lds_alpha[AW + e] = a.alpha1[e];
         }
     }
-    for (int e = tid; e < TCAND * KA; e += S2_NW * 64) {
-        const int c = e / KA, col = e - c * KA;
-        int64_t gi = tile0 + c;
-        if (gi > a.M - 1) gi = a.M - 1;
-        lds_c[c * (KA + 1) + col] = (col < D) ? a.cand[gi * D + col] * a.kp.sw[col] : (col == D ? 1.0 : 0.0);
-    }
-    __syncthreads();
-    if (tid < TCAND) {
-        double n2 = 0.0;
-        for (int d = 0; d < D; d++) { const double v = lds_c[tid * (KA + 1) + d]; n2 = fma(v, v, n2); }
-        // A candidate more than 775 length scales from the origin (hence > 630 from every observation: |x~| <= 142
-        // where the dot form is in use, IBO_DOT_GUARD) has k* = 0 exactly; it is pulled in to that radius, where k* is still 0, so
-        // that the exponent stays within what s2_exp's integer arithmetic covers (|y| < 7e5).
-        if (n2 > 6e5) {
-            const double sc = sqrt(6e5 / n2);
-            for (int d = 0; d < D; d++) lds_c[tid * (KA + 1) + d] *= sc;
-            n2 = 6e5;
-        }
-        lds_c[tid * (KA + 1) + D + 1] = fma(-0.5, n2, FAM == FAM_SE ? a.log_sf2 : 0.0);
-    }
-    __syncthreads();
+    s2_stage_candidates<FAM, TCAND, KA, S2_NW * 64>(a, tile0, lds_c);
     // this wave generates the 16 x 16 tile (row-tile rt, candidate block gcb) of every stage
     const int rt = wave >> 1, gcb = wave & 1;
     // its B-fragments of the exponent GEMM, c~aug[candidate 16 gcb + (lane&15)][4 s + (lane>>4)], are re-read from
@@ -395,7 +374,7 @@ __global__ __launch_bounds__(S2_NW * 64) void sweep2_rank1_kernel(SweepArgs a)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned tb = (a.tile_rows && a.part_all == 2) ? (unsigned)a.tile_sel[blockIdx.x] : blockIdx.x;      // (a compact list of tiles, as in sweep2_kernel)
     const int64_t tile0 = (int64_t)tb * TCAND;
-    const int D = a.kp.D, Npad = a.Npad;
+    const int Npad = a.Npad;
     const int NA128 = (Npad + 127) & ~127;
     // one row (a.rank1_row; < 0: the means only), or -- a kept state whose tiles are refreshed lazily (a.tile_rows) -- every appended
     // row this tile has not folded in yet, in order: the squares enter zsum in row order whenever the tile catches up, so its bits
@@ -412,24 +391,7 @@ __global__ __launch_bounds__(S2_NW * 64) void sweep2_rank1_kernel(SweepArgs a)
         lds_vec[e] = a.alphaY[e];
         lds_vec[NA128 + e] = a.alpha1[e];
     }
-    for (int e = tid; e < TCAND * KA; e += S2_NW * 64) {
-        const int c = e / KA, col = e - c * KA;
-        int64_t gi = tile0 + c;
-        if (gi > a.M - 1) gi = a.M - 1;
-        lds_c[c * (KA + 1) + col] = (col < D) ? a.cand[gi * D + col] * a.kp.sw[col] : (col == D ? 1.0 : 0.0);
-    }
-    __syncthreads();
-    if (tid < TCAND) {                               // as sweep2_kernel: radius guard, then b_c
-        double n2 = 0.0;
-        for (int d = 0; d < D; d++) { const double v = lds_c[tid * (KA + 1) + d]; n2 = fma(v, v, n2); }
-        if (n2 > 6e5) {
-            const double sc = sqrt(6e5 / n2);
-            for (int d = 0; d < D; d++) lds_c[tid * (KA + 1) + d] *= sc;
-            n2 = 6e5;
-        }
-        lds_c[tid * (KA + 1) + D + 1] = fma(-0.5, n2, FAM == FAM_SE ? a.log_sf2 : 0.0);
-    }
-    __syncthreads();
+    s2_stage_candidates<FAM, TCAND, KA, S2_NW * 64>(a, tile0, lds_c);      // (as sweep2_kernel: radius guard, then b_c)
     const int rt = wave >> 1, gcb = wave & 1;
     const double *cfrag = &lds_c[(16 * gcb + (lane & 15)) * (KA + 1) + (lane >> 4)];
     const __amdgpu_buffer_rsrc_t rXA = s2_rsrc(a.XA, (size_t)(NA128 / 16) * KA4 * 64 * sizeof(double));

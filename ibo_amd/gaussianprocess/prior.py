@@ -2,7 +2,7 @@
 Mean priors for the GP (ego/gaussianprocess/prior.py).
 
 RBFNMeanPrior.mu is part of the acqmaxGP ABI and is evaluated on the GPU inside the
-sweep epilogue (csrc/sweep.hip prior_mu_dev); `train` fits the network offline:
+sweep epilogue (csrc/ibo_common.h prior_mean_dev); `train` fits the network offline:
 k-means for the centres on the host (a few hundred points), the kernel matrix of the
 training set and the regularised solves on the device.
 """

@@ -28,7 +28,7 @@ import grad_reference as gr
 GRID = 4096.0                       # coordinates are multiples of 2^-12
 GUARD = 2e4                         # IBO_DOT_GUARD (csrc/ibo_common.h; dot_form_ok and ibo_gp_extend in csrc/abi_fit.hip): max |x~|^2 that admits the dot-form sweeps
 NLML_GUARD = 1e5                    # IBO_DOT_GUARD_NLML (ibo_nlml_grid, csrc/abi_nlml.hip): the per-dimension bound that admits the dot-form covariance pass
-PULL_IN = 6e5                       # s2_stage_candidates (csrc/sweep2_dev.h, two more copies in sweep2_kernels.h): |c~|^2 beyond which a candidate is pulled in
+PULL_IN = 6e5                       # IBO_DOT_PULL_IN (csrc/ibo_common.h; s2_stage_candidates in csrc/sweep2_dev.h): |c~|^2 beyond which a candidate is pulled in
 INSIDE = (0.80 * GUARD, 0.98 * GUARD)        # where the cases "inside the guard" put max |x~|^2
 OUTSIDE = (1.02 * GUARD, 1.3 * GUARD)        # ... and the cases beyond it
 MU_RTOL, MU_ATOL = 1e-6, 1e-9       # the suite's bar on the posterior mean (tests/test_gpu_parity.py)

@@ -478,6 +478,30 @@ def test_small_batch_kernels_against_oracle_and_the_other_kernels(ibo, oracle):
         opt(b"sweep_path", 0)
 
 
+def test_route_table_on_both_sides_of_every_threshold(ibo):
+    """which kernel serves a one-shot sweep under sweep_path = 0 (csrc/abi_sweep.hip: choose_route), read back through
+    ibo_last_sweep_kernel_ms on both sides of every batch-size threshold, on a model of 193 rows in 3 dimensions"""
+    from ibo_amd import _lib
+    from ibo_amd.gaussianprocess import GaussianProcess
+    from ibo_amd.gaussianprocess import kernel as K
+    from ibo_amd.acquisition import sweep
+    opt = lambda k, v: _lib.check(_lib.lib.ibo_set_option(k, v))
+    X, Y = synth(193, 193, 3)
+    GP = GaussianProcess(K.GaussianKernel_ard([.3, .35, .4]), X, Y, noise=.1)
+    cand = np.random.RandomState(193).rand(8193, 3)
+    table = ((-1, 16, "wk_small_kernel"), (-1, 4096, "wk_small_kernel"), (-1, 4097, "sweep2_kernel"),
+             (0, 16, "sweep_gemv_kernel"), (0, 17, "sweep_mfma_kernel<split>"), (0, 8192, "sweep_mfma_kernel<split>"),
+             (0, 8193, "sweep_mfma_kernel"))
+    try:
+        opt(b"sweep_path", 0)
+        for dot, M, kernel in table:
+            opt(b"dot_form", dot)
+            assert sweep(GP, cand[:M])["kernel"] == kernel, (dot, M)
+    finally:
+        opt(b"dot_form", -1)
+        opt(b"sweep_path", 0)
+
+
 def test_incremental_sweep_state_equals_full_sweeps(ibo):
     """sweep(incremental=True) on a fixed candidate array while the model grows by addData (the gallery's rounds):
     every round's per-candidate mu / s2 / EI and arg-max equal a full sweep of a freshly fitted model -- values at

@@ -3,7 +3,7 @@ Inputs away from the unit cube on every kernel route ("inputs away fr
 
 Every other model of the suite has its observations in [0, 1)^D.  Here the data sit tens to a million units from the origin, on
 both sides of the three dot-form guards (max |x~|^2 <= 2e4: csrc/abi_fit.hip dot_form_ok and ibo_gp_extend; 1e5: csrc/abi_nlml.hip) and
-beyond the candidate pull-in (|c~|^2 > 6e5: csrc/sweep2_dev.h s2_stage_candidates and its two copies in sweep2_kernels.h).
+beyond the candidate pull-in (|c~|^2 > 6e5: IBO_DOT_PULL_IN in csrc/ibo_common.h, applied by s2_stage_candidates in csrc/sweep2_dev.h).
 
 The reference is the oracle at the UNSHIFTED data: on the 2^-12 grid moved by an integer it returns the same bits at the shifted
 data (tests/shift_reference.py, tests/test_shift_reference.py), so the bars are test_gpu_parity.py's, unchanged: mu at rtol 1e-6,
