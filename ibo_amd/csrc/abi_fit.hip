@@ -1,7 +1,10 @@
-// abi_fit.hip -- the model side of the C ABI: fit (covariance, factorisation route, W = L^-1, alpha vectors), the block extension,
-// the preference GP's device steps, accessors, ibo_cov_matrix and the ibo_spd_* helpers.
+// abi_fit.hip -- the model side of the C ABI: fit (covariance, factorisation route, W = L^-1, alpha vectors), the block extension, the
+// removal of rows, the preference GP's device steps, accessors, ibo_cov_matrix and the ibo_spd_* helpers.
 #include "abi_internal.h"
 #include "loo.h"
+#include "downdate.h"
+
+#include <algorithm>
 
 int make_kparams(int ktype, int D, const double *hyper, int nhyper, double sf2, KParams *kp)
 {
@@ -252,6 +255,69 @@ extern "C" int ibo_gp_extend(ibo_gp_t *g, int n, const double *Xnew, const doubl
     g->N = N1; g->maxY = my;
     g->Yhost.assign(Yall, Yall + N1);
     g->L_upper_dirty = true;
+    g->fitted = true;
+    return IBO_OK;
+}
+
+// Take observations out of a fitted model without refactoring: per row the rank-one update of the trailing factor and of its inverse
+// (downdate.hip), O(N^2), in DESCENDING index order so the earlier indices stay valid.  Out of place: L' into T (scratch after a fit; the two
+// then trade places, as fit_factor trades T and Wp), W' into one pool buffer that is handed back before the call returns.  Npad does not
+// change: a removal gives a row of head-room back to ibo_gp_extend.
+extern "C" int ibo_gp_remove(ibo_gp_t *g, int n, const int *rows_host, const double *Y_rest, int *info)
+{
+    if (!g || !rows_host || !Y_rest || n < 1) return fail(IBO_ERR_ARG, "bad argument");
+    if (!g->fitted || !g->plain_fit || g->reversed) return fail(IBO_ERR_STATE, "rows cannot be removed from this model in place");
+    if (n >= g->N) return fail(IBO_ERR_ARG, "cannot remove %d of %d rows", n, g->N);
+    std::vector<int> rows(rows_host, rows_host + n);
+    std::sort(rows.begin(), rows.end(), [](int a, int b) { return a > b; });
+    for (int k = 0; k < n; k++) {
+        if (rows[k] < 0 || rows[k] >= g->N) return fail(IBO_ERR_ARG, "row %d out of range (model: %d rows)", rows[k], g->N);
+        if (k > 0 && rows[k] == rows[k - 1]) return fail(IBO_ERR_ARG, "row %d given twice", rows[k]);
+    }
+    IBO_TRY(use_device(g->device));
+    hipStream_t s = g->stream;
+    const int Np = g->Npad, DP = g->DP, D = g->D, N0 = g->N, N1 = N0 - n;
+    if (info) *info = 0;
+    ScopedBuf<double> wbuf;
+    IBO_TRY(wbuf.ensure((size_t)Np * Np));
+    IBO_TRY(g->tmp.ensure(downdate_scratch(Np)));       // (inside what stage_data sized for launch_alpha)
+    std::vector<double> yp(Np, 0.0);
+    double my = Y_rest[0];
+    for (int i = 0; i < N1; i++) { yp[i] = Y_rest[i]; if (Y_rest[i] > my) my = Y_rest[i]; }      // stage_data's scan
+    HIP_TRY(hipMemsetAsync(g->info.p, 0, sizeof(int), s));
+    HIP_TRY(hipEventRecord(g->fit0, s));
+    // from here on the handle's rows are being rewritten: any early return must leave it marked unfitted (the caller then refits)
+    g->fitted = false;
+    g->st_gen = 0;                                      // a kept sweep state never survives a removal
+    g->R_valid = false;                                 // ensure_R re-forms R on request
+    const double *Lsrc = g->L.p, *Wsrc = g->W.p;
+    double *Ldst = g->T.p, *Wdst = wbuf.p;
+    for (int k = 0; k < n; k++) {
+        const int N = N0 - k, i = rows[k];
+        KERNEL_TRY(launch_downdate_scalars(Wsrc, N, Np, i, g->tmp.p, g->info.p, s));
+        KERNEL_TRY(launch_downdate_L(Lsrc, N, Np, i, g->tmp.p, Ldst, s));
+        KERNEL_TRY(launch_downdate_W(Wsrc, N, Np, i, g->tmp.p, Wdst, s));
+        KERNEL_TRY(launch_downdate_X(g->Xp.p, N, Np, DP, i, g->Xs.p, s));                         // Xs: rewritten by launch_scale_x below
+        HIP_TRY(hipMemcpyAsync(g->Xp.p, g->Xs.p, sizeof(double) * (size_t)Np * DP, hipMemcpyDeviceToDevice, s));
+        const double *l = Lsrc, *w = Wsrc;
+        Lsrc = Ldst; Ldst = const_cast<double *>(l);
+        Wsrc = Wdst; Wdst = const_cast<double *>(w);
+    }
+    if (Lsrc != g->L.p) std::swap(g->L, g->T);          // an odd number of steps: the factor is in what was T
+    KERNEL_TRY(launch_pack_w(Wsrc, N1, Np, 0, g->W.p, g->Wp.p, s));                               // W (from the pool buffer, or in place) and its fragment copy
+    HIP_TRY(hipMemcpyAsync(g->Y.p, yp.data(), yp.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    KERNEL_TRY(launch_scale_x(g->kp_fit, g->Xp.p, Np, DP, g->Xs.p, g->ak.p, s));
+    KERNEL_TRY(launch_pack_xa(g->Xs.p, g->ak.p, N1, Np, DP, D, g->XA.p, s));
+    KERNEL_TRY(launch_alpha(g->W.p, N1, Np, g->Y.p, g->tmp.p, g->alphaY.p, g->alpha1.p, s));
+    HIP_TRY(hipEventRecord(g->fit1, s));
+    g->N = N1;                                          // (what the device holds now, whatever the info word says)
+    IBO_TRY(check_info(g, info));                       // synchronises: yp and the pool buffer may go
+    HIP_TRY(hipEventElapsedTime(&g->fit_ms, g->fit0, g->fit1));
+    gpu_time_add(g->device, g->fit_ms);
+    g->maxY = my;
+    g->Yhost.assign(Y_rest, Y_rest + N1);
+    g->L_upper_dirty = true;
+    g->fit_epoch++;
     g->fitted = true;
     return IBO_OK;
 }

@@ -3,7 +3,7 @@ Gaussian-process models with the reference's API (ego/gaussianprocess/__init__.p
 on the MI355X backend.
 
     GaussianProcess(kernel, X=None, Y=None, prior=None, noise=.1, gnoise=1e-4, G=None)
-        .addData(X, Y)  .posterior(x, getvar=True)  .posteriors(X)  .mu(x)  .negmu(x)
+        .addData(X, Y)  .removeData(indices)  .posterior(x, getvar=True)  .posteriors(X)  .mu(x)  .negmu(x)
         .getYfromX(qx)  .done(x)   attributes X, Y, R, L, noise, kernel, prior, ...
     PrefGaussianProcess(kernel, prefs=None, **kw)
         .addPreferences(prefs)  .addObservationPoint(x)   attributes preferences, C
@@ -448,6 +448,60 @@ class GaussianProcess(object):
         self._cache = {}
         return True
 
+    # A removal through ibo_gp_remove costs one O(N^2) step per row, a refit one O(N^3) factorisation: more rows than this in one call are
+    # refitted.  UNMEASURED: the ratio of a fit (0.27 ms) to addData's 0.12 ms step at N = 1024, D = 4, rounded down, stands in until
+    # tools/time_remove.py has been run.
+    REMOVE_MAX = 2
+
+    def removeData(self, indices, _route=None):
+        """take observations out of the model: `indices` is a row number or a sequence of distinct row numbers (negative ones count
+        from the end).  X and Y lose the rows; the fitted model is reduced on the device without refactoring (ibo_gp_remove: the rank-one
+        update of the trailing factor and of W = L^-1, O(N^2) per row) while at most REMOVE_MAX rows go and kernel and noise are those of
+        the fit, else the remaining data are refitted.  IndexError for a row that does not exist, ValueError for a row named twice or
+        when no row would be left: the model is unchanged then.  _route ("device" / "refit") forces one route (tests)."""
+        import operator
+        N = len(self.X)
+        rows = []
+        for v in np.atleast_1d(np.asarray(indices, dtype=object)).ravel():
+            k = operator.index(v)
+            if not -N <= k < N:
+                raise IndexError("row %d of a model with %d observations" % (k, N))
+            rows.append(k + N if k < 0 else k)
+        if len(rows) == 0:
+            raise ValueError("no row given")
+        if len(set(rows)) != len(rows):
+            raise ValueError("a row is named twice")
+        if len(rows) >= N:
+            raise ValueError("removing every observation leaves no model")
+        keep = np.setdiff1d(np.arange(N), rows)
+        oldX, oldY = self.X, self.Y
+        self.X, self.Y = oldX[keep], oldY[keep]
+        try:
+            if _route == "refit" or not self._remove_device(rows, forced=_route == "device"):
+                self._fit_device()
+        except Exception:
+            # as addData: a failed factorisation leaves the model as it was -- the old data are factored again before the error is passed on
+            self.X, self.Y = oldX, oldY
+            self._fit_device()
+            raise
+
+    def _remove_device(self, rows, forced=False):
+        """removal on the device; False when the handle has to be refitted with the remaining data instead"""
+        if self._dev is None or (len(rows) > self.REMOVE_MAX and not forced):
+            return False
+        spec = self.kernel._ibo_spec()
+        if getattr(self, "_fit_spec", None) != (spec[0], tuple(spec[1]), spec[2], float(self.noise)):
+            return False                             # kernel or noise changed since the fit
+        info = ctypes.c_int(0)
+        rc_rows = (ctypes.c_int * len(rows))(*rows)
+        Yc = _lib.f64(self.Y)
+        rc = _lib.lib.ibo_gp_remove(self._handle(), len(rows), rc_rows, _lib.dp(Yc), ctypes.byref(info))
+        if rc in (_lib.ERR_STATE, _lib.ERR_NOT_PD):  # not a plain fit, or a step was refused: the remaining data are factored afresh
+            return False
+        _lib.check(rc)
+        self._cache = {}
+        return True
+
     def getYfromX(self, qx):
         for x, y in zip(self.X, self.Y):
             if np.all(qx == x):
@@ -737,6 +791,9 @@ class PrefGaussianProcess(GaussianProcess):
 
     def loo_score(self):
         raise NotImplementedError("the preference GP's targets are latent MAP values, not observations: no leave-one-out")
+
+    def removeData(self, indices, _route=None):
+        raise NotImplementedError("the preference GP's factor is that of R + C^-1 and its targets are a MAP: removing a point changes C")
 
     def addObservationPoint(self, X):
         """add a point to observe at, without its observation (:502-519)"""

@@ -40,7 +40,8 @@ extern "C" {
                              * round 5 and now return IBO_ERR_ARG "unknown option", as does a NULL key; ibo_nlml_grid's covariance pass is the fast one;
                              * 8: - ibo_direct_server_info and the options "direct_resident", "direct_idle_ms" (ibo_direct_max's resident evaluation server, measured
                              * slower than the launches and removed: both keys are unknown options now); + ibo_gp_loo, ibo_loo_grad (leave-one-out predictions and the LOO-CV
-                             * objective with its gradient: additions within 8, nothing else changed) */
+                             * objective with its gradient: additions within 8, nothing else changed); + ibo_gp_remove (observations taken out of a fitted model in
+                             * O(N^2): added within 8, nothing else changed) */
 
 /* status codes */
 #define IBO_OK              0
@@ -177,6 +178,20 @@ int ibo_gp_extend(ibo_gp_t *gp, int n, const double *Xnew_host, const double *Y_
  * that many observations can be appended by ibo_gp_extend before a refit is due (a gallery of n points on a model
  * whose size is a multiple of 64 would otherwise refit, and sweep in full, in its very first round) */
 int ibo_gp_reserve(ibo_gp_t *gp, int rows);
+
+/*
+ * Take n observations out of a fitted model WITHOUT refactoring: per removed row the rank-one update of the trailing factor and of its
+ * inverse from the L and W = L^-1 the handle holds (two scans, O(N^2), no factorisation), one row at a time in descending index order.
+ * rows_host: n distinct 0-based indices in [0, N), in any order (the same set gives the same bits in any order).  Y_rest_host: the N - n
+ * remaining targets in their new order (the caller owns Y, as in ibo_gp_extend).  L, W, both alpha vectors and the points are rewritten on
+ * the device; R is formed again on request; a kept sweep state is dropped; the row padding stays, so every removed row is head-room for
+ * ibo_gp_extend.  IBO_ERR_ARG -- and nothing changed -- for a NULL argument, n < 1, n >= N, an index out of range or given twice.
+ * IBO_ERR_STATE -- and nothing changed -- when the handle's factor is not that of its own kernel matrix (never fitted, fitted from a
+ * caller-supplied matrix or from an inverse): the caller then calls ibo_gp_fit with the remaining data.  IBO_ERR_NOT_PD (info: the 1-based
+ * row whose step was refused -- W[i][i] not finite and positive, or a sum not finite), and any other error, leave the handle UNFITTED.
+ * Fixed-order sums: the same call on the same model gives the same bits.  Any fitted size (up to 23168 rows).
+ */
+int ibo_gp_remove(ibo_gp_t *gp, int n, const int *rows_host, const double *Y_rest_host, int *info);
 
 /*
  * Preference GP on the device (PrefGaussianProcess.addPreferences, ego/gaussianprocess/__init__.py:347-498: the MAP of
