@@ -178,6 +178,7 @@ static int fit_impl(ibo_gp *g, int ktype, int N, int D, const double *X, const d
     KParams kp;
     IBO_TRY(make_kparams(ktype, D, hyper, nhyper, sf2, &kp));
     g->fitted = false;
+    g->pw.ready = false;                                 // other data from here on, whether or not they can be factored
     IBO_TRY(stage_data(g, N, D, X, Y, false));
     g->kp = kp; g->kp_fit = kp; g->noise = noise;
     const int Np = g->Npad;
@@ -353,6 +354,7 @@ int fit_from_inverse(ibo_gp *g, int ktype, int N, int D, const double *X, const 
     KParams kp;
     IBO_TRY(make_kparams(ktype, D, hyper, nhyper, sf2, &kp));
     g->fitted = false;
+    g->pw.ready = false;
     IBO_TRY(stage_data(g, N, D, X, Y, true));
     g->kp = kp; g->noise = noise;
     const int Np = g->Npad;
@@ -455,15 +457,26 @@ extern "C" int ibo_pref_begin(ibo_gp_t *g)
     IBO_TRY(use_device(g->device));
     IBO_TRY(pref_alloc(g));
     KERNEL_TRY(launch_wtw(g->W.p, g->pw.Et.p, g->pw.Rinv.p, g->Npad, g->stream));       // R^-1 = W^T W (zero on the pad)
-    g->pw.ready = true; g->pw.epoch = g->fit_epoch;
+    g->pw.ready = true; g->pw.epoch = g->fit_epoch; g->pw.N = g->N; g->pw.Npad = g->Npad;
     return IBO_OK;
+}
+
+// The workspace belongs to the model ibo_pref_begin ran on: R^-1 = W^T W is that model's, and every buffer is sized by its Npad.  fit_epoch
+// moves with every fit and every removal; an extension keeps it (a kept sweep state survives one) but changes N.  Both callers of stage_data,
+// the only place that moves Npad, clear pw.ready before they restage (a fit that then FAILS leaves another N and Npad under the old epoch), so
+// ready, epoch and N already decide; Npad is compared all the same, belt and braces, because it is what sizes every buffer written here and
+// ibo_pref_finish cannot ask for `fitted` instead (its own IBO_ERR_NOT_PD leaves the handle unfitted, and the caller's retry with a larger
+// diag must still be accepted).
+static bool pref_owned(const ibo_gp *g)
+{
+    return g->pw.ready && g->pw.epoch == g->fit_epoch && g->pw.N == g->N && g->pw.Npad == g->Npad;
 }
 
 static int pref_check(ibo_gp *g)
 {
     if (!g) return fail(IBO_ERR_ARG, "gp is NULL");
-    if (!g->pw.ready || g->pw.epoch != g->fit_epoch || !g->fitted || !g->plain_fit)
-        return fail(IBO_ERR_STATE, "no ibo_pref_begin since the last plain fit of this model");
+    if (!pref_owned(g) || !g->fitted || !g->plain_fit)
+        return fail(IBO_ERR_STATE, "no ibo_pref_begin since this model was last fitted, extended or reduced");
     return use_device(g->device);
 }
 
@@ -512,7 +525,8 @@ extern "C" int ibo_pref_newton_step(ibo_gp_t *g, int nnz, const int64_t *lin_hos
 extern "C" int ibo_pref_finish(ibo_gp_t *g, int nnz, const int64_t *lin_host, const double *val_host, double diag, int *info)
 {
     if (!g) return fail(IBO_ERR_ARG, "gp is NULL");
-    if (!g->pw.ready || g->reversed || g->N < 1) return fail(IBO_ERR_STATE, "no ibo_pref_begin on this model");
+    if (!pref_owned(g) || g->reversed || g->N < 1)
+        return fail(IBO_ERR_STATE, "no ibo_pref_begin since this model was last fitted, extended or reduced");
     IBO_TRY(use_device(g->device));
     auto &pw = g->pw;
     const int N = g->N, Np = g->Npad;
@@ -525,7 +539,9 @@ extern "C" int ibo_pref_finish(ibo_gp_t *g, int nnz, const int64_t *lin_host, co
     IBO_TRY(g->A.ensure((size_t)N * N));
     IBO_TRY(ensure_R(g));
     KERNEL_TRY(launch_pref_sum(g->R.p, pw.A.p, N, Np, g->A.p, s));
-    return fit_factor(g, g->kp_fit, N, g->noise, true, info);
+    IBO_TRY(fit_factor(g, g->kp_fit, N, g->noise, true, info));
+    pw.epoch = g->fit_epoch;                             // the same points and the same R: the workspace stays with the handle (another ibo_pref_finish is accepted)
+    return IBO_OK;
 }
 
 extern "C" int ibo_gp_set_kstar_sf2(ibo_gp_t *g, double sf2)

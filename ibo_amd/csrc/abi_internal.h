@@ -138,7 +138,7 @@ struct ibo_gp {
         DevBuf<long long> lin;
         DevBuf<int> info;
         bool ready = false;
-        int epoch = -1;
+        unsigned epoch = 0; int N = 0, Npad = 0;     // the model ibo_pref_begin ran on (pref_owned): its fit_epoch, rows and padded rows
     } pw;
     // prior
     int nb = 0; double ptheta = 0.0;

@@ -41,7 +41,8 @@ extern "C" {
                              * 8: - ibo_direct_server_info and the options "direct_resident", "direct_idle_ms" (ibo_direct_max's resident evaluation server, measured
                              * slower than the launches and removed: both keys are unknown options now); + ibo_gp_loo, ibo_loo_grad (leave-one-out predictions and the LOO-CV
                              * objective with its gradient: additions within 8, nothing else changed); + ibo_gp_remove (observations taken out of a fitted model in
-                             * O(N^2): added within 8, nothing else changed) */
+                             * O(N^2): added within 8, nothing else changed); within 8 as well: the ibo_pref_* entries refuse a workspace begun on another
+                             * model (IBO_ERR_STATE where a call used to compute from stale data -- no symbol, signature or valid call order changed) */
 
 /* status codes */
 #define IBO_OK              0
@@ -199,13 +200,19 @@ int ibo_gp_remove(ibo_gp_t *gp, int n, const int *rows_host, const double *Y_res
  * and then L = chol(R + C^-1), :459-498).  The host keeps what is O(pairs) -- Phi, its derivatives, the line search --
  * and the device everything that is N x N: only vectors and the distinct entries of the pair sums cross the bus
  * (round 1 shipped an N x N Hessian per Newton step through ibo_spd_solve, and C and C^-1 through ibo_spd_inverse).
- *   ibo_pref_begin        after a plain ibo_gp_fit of the points: R^-1 = W^T W is formed on the handle
+ *   ibo_pref_begin        after a plain ibo_gp_fit of the points: R^-1 = W^T W is formed on the handle.  The workspace belongs to the
+ *                         model as it is at this call -- this fit, this number of rows, this padding.  After ibo_gp_extend,
+ *                         ibo_gp_remove or another fit of the handle (one that failed included) the three entries below return
+ *                         IBO_ERR_STATE, with handle and outputs untouched, until ibo_pref_begin is called again.  ibo_gp_set_y,
+ *                         ibo_gp_set_prior and ibo_gp_set_kstar_sf2 leave it valid: R does not depend on them.
  *   ibo_pref_rinv_mul     out = R^-1 y
  *   ibo_pref_newton_step  H = R^-1 + sum of the sparse term (lin[e] = row * N + col, distinct entries: the host sums
  *                         the per-pair contributions rho (e_v - e_u)(e_v - e_u)^T); delta = -H^-1 grad; rdelta = R^-1 delta
  *   ibo_pref_finish       C = diag I + sparse term; the handle is refactored from R + C^-1 exactly as
  *                         ibo_gp_fit_with_matrix would (Y as set by ibo_gp_set_y).  IBO_ERR_NOT_PD: call again with a
- *                         larger diag (the reference's regulariser loop, :489-497) or refit.
+ *                         larger diag (the reference's regulariser loop, :489-497) or refit: the workspace survives that failure,
+ *                         and a successful call (the same points, the same R: it may be repeated with another C).  After a success
+ *                         the model is no plain fit any more, so ibo_pref_rinv_mul and ibo_pref_newton_step return IBO_ERR_STATE.
  */
 int ibo_pref_begin(ibo_gp_t *gp);
 int ibo_pref_rinv_mul(ibo_gp_t *gp, const double *y_host, double *out_host);

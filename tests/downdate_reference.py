@@ -14,6 +14,8 @@ With A = L L^T, W = L^-1 and row / column i taken out (m = N - 1 - i rows below 
     W'[j, :] = W~[j, :] / d_j - q_j sum_{k < j} p_k W~[k, :],  column i dropped                                          (prefix scan down columns)
 
 Rows above i keep their entries (W loses its column i, which is zero there).  The step adds the positive semi-definite p p^T: nothing cancels.
+
+append_row is the other half of a sliding window: one step of ibo_gp_extend (GaussianProcess.addData) restated the same way.
 """
 import numpy as np
 
@@ -73,6 +75,59 @@ def remove_rows(L, W, rows):
     for r in reversed(rows):
         L, W = remove_row(L, W, r)
     return L, W
+
+
+def append_row(L, W, k, r):
+    """(L', W') of the model with one more observation, (N + 1) x (N + 1) each: k = the new point's covariances with the N old ones, r its own
+    diagonal entry.  z = W k, d = sqrt(r - z^T z); the new row of L is [z, d], the new row of W is [-z^T W / d, 1 / d]."""
+    L = np.asarray(L, dtype=float); W = np.asarray(W, dtype=float); k = np.asarray(k, dtype=float)
+    N = L.shape[0]
+    z = W @ k
+    d = np.sqrt(r - z @ z)
+    L2 = np.zeros((N + 1, N + 1)); W2 = np.zeros((N + 1, N + 1))
+    L2[:N, :N] = L; L2[N, :N] = z; L2[N, N] = d
+    W2[:N, :N] = W; W2[N, :N] = -(z @ W) / d; W2[N, N] = 1.0 / d
+    return L2, W2
+
+
+def se_ard_matrix(X, ell, noise):
+    """R = K(X, X) of the SE-ARD kernel with length scales ell, diagonal 1 + noise (GaussianProcess._computeCorrelations)"""
+    X = np.asarray(X, dtype=float) / ell
+    R = np.exp(-.5 * ((X[:, None, :] - X[None, :, :]) ** 2).sum(-1))
+    R[np.diag_indices(len(X))] = 1.0 + noise
+    return R
+
+
+def window_plan(seed, N, D, steps, mode):
+    """a seeded sequence of `steps` steps "append one point, remove one row" on N points in the unit cube: (X0, [(x_new, row), ...]).
+    mode "window": the row is 0 (the oldest point goes); mode "random": any of the N + 1 rows present after the append."""
+    rs = np.random.RandomState(seed)
+    X0 = rs.rand(N, D)
+    plan = []
+    for _ in range(steps):
+        x = rs.rand(D)
+        plan.append((x, 0 if mode == "window" else int(rs.randint(0, N + 1))))
+    return X0, plan
+
+
+def run_window(X0, plan, ell, noise, checkpoints):
+    """append_row + remove_row along a window_plan, from numpy's factor of X0.  At every step in `checkpoints` (1-based):
+    {step: (cond_2(R), err L, err W)} against numpy.linalg.cholesky / inv of the matrix of the points held then.  -> (that dict, X at the end)"""
+    X = np.array(X0, dtype=float)
+    L = np.linalg.cholesky(se_ard_matrix(X, ell, noise))
+    W = np.linalg.inv(L)
+    out = {}
+    for step, (x, row) in enumerate(plan, 1):
+        k = np.exp(-.5 * (((X - x) / ell) ** 2).sum(-1))
+        L, W = append_row(L, W, k, 1.0 + noise)
+        X = np.vstack([X, x])
+        L, W = remove_row(L, W, row)
+        X = np.delete(X, row, axis=0)
+        if step in checkpoints:
+            R = se_ard_matrix(X, ell, noise)
+            Lr = np.linalg.cholesky(R)
+            out[step] = (cond2(R), relerr(L, Lr), relerr(W, np.linalg.inv(Lr)))
+    return out, X
 
 
 def cond2(A):

@@ -22,6 +22,8 @@ import grad_reference as gr
 import loo_reference as lr
 from conftest import synth
 from oracle import oracle as orc
+from test_gpu_linalg_entries import option
+from wall_time import wall
 
 pytestmark = pytest.mark.gpu
 
@@ -77,11 +79,28 @@ def ref_R(kind, D, X):
     return orc.GP(orc.Kern(kind, hyper_of(kind, D)), X, np.zeros(len(X)), noise=NOISE).R
 
 
-def check_factor(lib, GP, kind, D, what=""):
-    """GP's L, W and R against NumPy's of the matrix of the points it holds now"""
-    R = ref_R(kind, D, GP.X)
-    c = dr.cond2(R)
-    assert c <= 1e6, (what, c)
+def cond_of(R, how):
+    """cond_2 of the symmetric positive definite R: by SVD; from its eigenvalues (the same number, cheaper); or "bound": the bound
+    N (1 + noise) / noise, which needs no decomposition -- R = sf2 K + (1 + noise - sf2) I with K positive semi-definite and sf2 <= 1, so
+    lambda_min >= noise, and lambda_max <= trace(R) = N (1 + noise).  The bound reads the noise off R's diagonal and asserts sf2 <= 1."""
+    if how == "svd":
+        return dr.cond2(R)
+    if how == "eigvalsh":
+        w = np.linalg.eigvalsh(R)
+        return w[-1] / w[0]
+    assert how == "bound"
+    noise = R[0, 0] - 1.0
+    assert noise > 0 and np.all(np.diag(R) == R[0, 0]) and np.max(np.abs(R - np.diag(np.diag(R)))) <= 1.0
+    return len(R) * (1.0 + noise) / noise
+
+
+def check_factor(lib, GP, kind, D, what="", cond="svd", R=None, max_cond=1e6):
+    """GP's L, W and R against NumPy's of the matrix of the points it holds now (R: that matrix, where the model is not one of new_gp's;
+    cond: how cond_2 is found, see cond_of; max_cond None: no precondition -- the caller says why)"""
+    if R is None:
+        R = ref_R(kind, D, GP.X)
+    c = cond_of(R, cond)
+    assert max_cond is None or c <= max_cond, (what, c)
     Lref = np.linalg.cholesky(R)
     Wref = np.linalg.inv(Lref)
     L, W = GP.L, get_W(lib, GP)
@@ -91,6 +110,7 @@ def check_factor(lib, GP, kind, D, what=""):
     assert eL <= 1e-9 and eW <= 1e-9, (what, eL, eW)
     assert np.array_equal(L, np.tril(L)) and np.array_equal(W, np.tril(W)), what
     np.testing.assert_allclose(GP.R, R, rtol=1e-12, atol=0, err_msg=what)
+    return eL, eW
 
 
 def values_close(a, b, what=""):
@@ -105,6 +125,43 @@ def check_like_fresh(GP, kind, D, prior=False, what="", M=64):
         (m1, v1), (m0, v0) = GP.posteriors(q), fr.posteriors(q)
         values_close(m1, m0, what + " mu"); values_close(v1, v0, what + " s2")
     return fr
+
+
+def prior_tuple(GP):
+    p = GP.prior
+    return None if p is None else (p.means, p.beta, p.theta, p.lowerb, p.width)
+
+
+def check_loo_like_fresh(GP, fr, kind, D, what=""):
+    """leave-one-out predictions and score against the fresh model's, at the bars of tests/test_gpu_loo.py"""
+    pt = prior_tuple(GP)
+    lref = lr.handle_loo(orc.GP(orc.Kern(kind, hyper_of(kind, D)), GP.X, GP.Y, noise=NOISE, prior=None if pt is None else orc.Prior(*pt)))
+    assert lref["cond"] <= 1e6
+    (lm1, ls1), (lm0, ls0) = GP.loo(), fr.loo()
+    assert np.all(np.abs(lm1 - lm0) <= 1e-9 * (np.abs(GP.Y) + np.abs(lref["c"]) / lref["d"])), what
+    assert np.all(np.abs(ls1 - ls0) <= 1e-9 * ls0), what
+    assert abs(GP.loo_score() - fr.loo_score()) <= 1e-9 * (len(GP.Y) + abs(lref["value"])), what
+
+
+def check_readers_like_fresh(GP, fr, kind, D, what=""):
+    """gradients, joint covariance and leave-one-out of GP against the fresh model `fr` on the same data and prior: the checks and bars of
+    test_readers_of_the_handle_agree_with_a_fresh_model below, for callers that drive a handle through more than one step"""
+    hyper = hyper_of(kind, D)
+    fam, w, sf2 = gr.kernel_spec(kind, hyper, D)
+    ref = gr.RefGP(GP.X, GP.Y, NOISE, fam, w, sf2, prior=prior_tuple(GP))
+    Q = np.random.RandomState(6).rand(64, D) * 1.2 - .1
+    Q[:4] = GP.X[[0, len(GP.X) - 1, len(GP.X) // 2, len(GP.X) // 3]]             # on top of training inputs
+    rg = ref.grad(Q)
+    m1, v1, dm1, dv1 = GP.posterior_gradient(Q)
+    m0, v0, dm0, dv0 = fr.posterior_gradient(Q)
+    values_close(m1, m0, what); values_close(v1, v0, what)
+    gr.assert_grad_close(dm1, dm0, rg["smu"], what=what + " dmu")
+    gr.assert_grad_close(dv1, dv0, rg["ss2"], what=what + " ds2")
+    (mc1, S1), (mc0, S0) = GP.posterior_cov(Q), fr.posterior_cov(Q)
+    values_close(mc1, mc0, what)
+    cr.assert_cov_close(S1, S0, cr.cov(ref, Q)[1], sf2, NOISE, what=what + " Sigma")
+    assert np.array_equal(S1, S1.T)
+    check_loo_like_fresh(GP, fr, kind, D, what)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. the factor
@@ -367,3 +424,169 @@ def test_refusals_leave_the_model_as_it_was(lib):
     # removeData on such a model takes the refit route (its factor is not one that can be reduced)
     GP.removeData(0)
     check_like_fresh(GP, kind, D, what="after a matrix fit")
+
+
+# ---------------------------------------------------------------------------------------------------------------- 7. beyond one chunk, other routes, poor conditioning
+def remove_on_device(GP, rows):
+    """removeData by the device route, known to have stayed on it: _remove_device answers False where ibo_gp_remove returns IBO_ERR_STATE
+    or IBO_ERR_NOT_PD, and removeData then refits without a word -- every check after it would read a fresh factor, not downdate.hip's"""
+    def refused(*a, **k):
+        pytest.fail("ibo_gp_remove refused rows %s: removeData fell back to a refit" % (rows,))
+    GP._fit_device = refused
+    try:
+        GP.removeData(rows, _route="device")
+    finally:
+        del GP._fit_device
+
+
+# downdate_scalars_kernel walks p in chunks of 1024 (m = N - 1 - i entries, ts[0] = ts[n] carried from one chunk into the next) and
+# downdate_W_prefix_kernel keeps eight 64-row segments in flight (a second pass from 513 rows below i on): both sides of each edge
+CHUNK_CASES = [("ard", 600, 0), ("ard", 1026, 0), ("ard", 1026, 1), ("ard", 1090, 1), ("ard", 2100, 0), ("ard", 2100, 1075),
+               ("ard", 2100, 1074), ("ard", 2100, 2099), ("m5", 1090, 0)]
+
+
+@pytest.mark.parametrize("kind,N,i", CHUNK_CASES)
+def test_factor_after_one_removal_beyond_one_chunk(lib, kind, N, i):
+    """L, W and R against NumPy at 1e-9 where m = N - 1 - i is 599, 1025 (one element into the second chunk), 1024 (exactly one chunk),
+    1088, 2099 (three chunks, 33 segments), 1024 and 1025 inside a larger model, and 0.  cond_2(R) <= 1e6 is asserted from R's eigenvalues
+    (numpy.linalg.eigvalsh: for a symmetric positive definite matrix the ratio of the extreme ones IS cond_2) up to 1090 rows, and at 2100
+    rows by the bound N (1 + noise) / noise = 23100 (cond_of), which costs nothing: an SVD of 2100 rows alone is several seconds."""
+    D = 4
+    with wall("%s N=%d i=%d" % (kind, N, i)):
+        X, Y = synth(N + i + 3, N, D)
+        GP = new_gp(kind, D, X, Y)
+        remove_on_device(GP, i)
+        keep = np.r_[0:i, i + 1:N]
+        assert len(GP.X) == N - 1 and np.array_equal(GP.X, X[keep]) and np.array_equal(GP.Y, Y[keep])
+        check_factor(lib, GP, kind, D, "%s N=%d i=%d m=%d" % (kind, N, i, N - 1 - i), cond="bound" if N > 1500 else "eigvalsh")
+
+
+def sweep_like_fresh(GP, fr, D, what):
+    """one 9001-candidate sweep on the full-sweep route (it reads the repacked Wp) against the fresh model's"""
+    from ibo_amd import DeviceArray
+    from ibo_amd.acquisition import sweep
+    big = DeviceArray.from_host(np.random.RandomState(10).rand(9001, D))
+    r = sweep(GP, big, acq="ei", native=False, outputs=("mu", "s2", "acq"))
+    f = sweep(fr, big, acq="ei", native=False, outputs=("mu", "s2", "acq"))
+    assert r["kernel"].startswith("sweep2"), r["kernel"]
+    for k in ("mu", "s2", "acq"):
+        values_close(r[k], f[k], "%s 9001 %s" % (what, k))
+    a, b = f["acq"][r["best_idx"]], f["acq"][f["best_idx"]]
+    assert r["best_idx"] == f["best_idx"] or abs(a - b) <= 1e-12 * abs(b), (what, r["best_idx"], f["best_idx"], a, b)
+
+
+ROUTES = {"super": (b"super_min_nb", 32), "two_level": (b"fused2_min_nb", 33)}
+ROUTE_OPS = ["one", "two", "three", "add"]
+
+
+@pytest.mark.parametrize("upto", ROUTE_OPS)
+@pytest.mark.parametrize("route", sorted(ROUTES))
+def test_removal_from_a_model_fitted_on_another_route(lib, route, upto):
+    """2100 rows (33 block columns) fitted in super-panels (super_min_nb = 32) and in the two-level order (fused2_min_nb = 33): fit_factor
+    leaves T, Wp and W in other roles there than on the plain single-level route (T and Wp traded after the transposing pack; T as
+    launch_trinv's scratch), and ibo_gp_remove writes L' into T and trades L and T after an odd number of steps.  One handle goes through
+    remove one row -> remove two rows in one call (even: the factor ends where it began) -> remove three rows through the entry itself
+    (odd) -> addData of one point; the case `upto` replays that sequence up to its step and checks there, so every state of the handle
+    is checked and no case pays for the others' NumPy factors: L (with its deferred zero_upper), W and R against NumPy at 1e-9, the
+    posterior against a fresh model, one sweep on the full-sweep route.  cond_2(R) <= 23100 by the bound (cond_of)."""
+    kind, D, N = "ard", 4, 2100
+    key, val = ROUTES[route]
+    with wall("%s up to %s" % (route, upto)):
+        X, Y = synth(77, N + 1, D)
+        with option(key, val):
+            GP = new_gp(kind, D, X[:N], Y[:N])
+            W_route = get_W(lib, GP) if upto == "one" else None
+            mirror = np.arange(N)
+            for op in ROUTE_OPS[:ROUTE_OPS.index(upto) + 1]:
+                if op == "one":
+                    remove_on_device(GP, 700)
+                    mirror = np.delete(mirror, [700])
+                elif op == "two":
+                    remove_on_device(GP, [3, 1500])
+                    mirror = np.delete(mirror, [3, 1500])
+                elif op == "three":
+                    rows = [0, 1024, len(mirror) - 1]
+                    mirror = np.delete(mirror, rows)
+                    info = ctypes.c_int(0)
+                    y = lib.f64(Y[mirror])
+                    lib.check(lib.lib.ibo_gp_remove(GP._handle(), 3, (ctypes.c_int * 3)(*rows), lib.dp(y), ctypes.byref(info)))
+                    assert info.value == 0
+                    GP.X, GP.Y = X[mirror], Y[mirror]
+                    GP._cache = {}
+                else:
+                    GP._fit_device = lambda *a, **k: pytest.fail("addData refitted although the padding has room")
+                    try:
+                        GP.addData(X[N], Y[N])
+                    finally:
+                        del GP._fit_device
+                    mirror = np.r_[mirror, N]
+        assert np.array_equal(GP.X, X[mirror]) and np.array_equal(GP.Y, Y[mirror])
+        if W_route is not None:
+            # the option did move the fit: the two-level order forms W by recursive doubling, another order of the same sums than the
+            # ride-along's, while super-panels are documented to give the bits of the step-by-step order (their buffers differ, not their sums)
+            same = np.array_equal(W_route, get_W(lib, new_gp(kind, D, X[:N], Y[:N])))
+            assert same == (route == "super"), (route, same)
+        what = "%s after %s" % (route, upto)
+        check_factor(lib, GP, kind, D, what, cond="bound")
+        fr = check_like_fresh(GP, kind, D, what=what)
+        sweep_like_fresh(GP, fr, D, what)
+
+
+COND_CASES = [(1e-4, 2), (1e-3, 1), (1e-4, 1)]
+
+
+@pytest.mark.parametrize("noise,D", COND_CASES)
+def test_removal_and_extension_where_conditioning_is_worst(lib, noise, D):
+    """The data of test_gpu_parity.py::test_tolerance_where_conditioning_is_worst (three clusters of near-duplicates) at N = 300, SE-ARD
+    l = .3, noise 1e-4 and 1e-3: rows [0], [150] and [5, 200] removed from the fitted model by the device route, then one near-duplicate
+    point appended to the last of these.  After each, mu and sigma^2 at 24 candidates (half of them 1e-3 from training points) against the
+    80-bit posterior of the data the model holds, at that test's bars for a fit: 1e-7 for mu (floor 1e-9), 1e-8 for sigma^2 clipped to
+    [1e-8, 10].
+    The factor is held to 1e-9 against NumPy's WITHOUT the cond_2 <= 1e6 precondition of every other case here: cond_2 is 2e5 .. 2.3e6 on
+    these inputs, above the precondition for some of them, and the bar is met all the same -- the float64 restatement of the removal
+    (downdate_reference.remove_rows) is within 2.1e-11 (W) and 3.4e-12 (L) of NumPy's refit on exactly these inputs, and within 3.3e-10
+    (mu) and 1.9e-9 (sigma^2) of the 80-bit values, where a float64 refit is within 1.0e-9 and 6e-10: the reference alone keeps more
+    than five times room under each bar."""
+    from ibo_amd.acquisition import sweep
+    from ibo_amd.gaussianprocess import GaussianProcess
+    from ibo_amd.gaussianprocess.kernel import GaussianKernel_ard
+    from test_gpu_parity import _longdouble_posterior
+    N, ell = 300, .3
+    okern = orc.Kern("ard", np.full(D, ell))
+    kfun = lambda Xm, q: np.array([okern.cov(x, q) for x in Xm])
+
+    def rel(a, b, floor):
+        return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), floor)))
+
+    def check(GP, cand, what):
+        R = orc.GP(okern, GP.X, GP.Y, noise=noise).R
+        eL, eW = check_factor(lib, GP, "ard", D, what, R=R, max_cond=None)
+        r = sweep(GP, cand, acq='ei', xi=.01, native=True, outputs=("mu", "s2"))
+        t_mu, t_s2 = _longdouble_posterior(R, GP.X, GP.Y, kfun, cand, noise)
+        e_mu, e_s2 = rel(r["mu"], t_mu, 1e-9), rel(r["s2"], np.clip(t_s2, 1e-8, 10), 1e-300)
+        print("%s: mu %.3g  s2 %.3g against 80 bits" % (what, e_mu, e_s2))
+        assert e_mu < 1e-7 and e_s2 < 1e-8, (what, e_mu, e_s2)
+
+    with wall("noise %g D=%d" % (noise, D)):
+        rs = np.random.RandomState(N + D)
+        c = rs.rand(3, D)
+        X = np.clip(np.vstack([c[i] + 0.02 * rs.randn(N // 4, D) for i in range(3)] + [rs.rand(N - 3 * (N // 4), D)]), 0, 1)
+        Y = np.sin(3 * X.sum(1)) + .01 * rs.randn(N)
+        for rows in ([0], [N // 2], [5, 200]):
+            GP = GaussianProcess(GaussianKernel_ard(np.full(D, ell)), X, Y, noise=noise)
+            remove_on_device(GP, rows)
+            keep = np.delete(np.arange(N), rows)
+            assert np.array_equal(GP.X, X[keep]) and np.array_equal(GP.Y, Y[keep])
+            cand = np.vstack([rs.rand(12, D), np.clip(X[keep][rs.randint(0, len(keep), 12)] + 1e-3 * rs.randn(12, D), 0, 1)])
+            check(GP, cand, "noise %g D=%d rows %s" % (noise, D, rows))
+        # the rows' head-room is back: a point 1e-3 from a training point of the first cluster goes in without a refit
+        xn = np.clip(GP.X[20] + 1e-3 * rs.randn(D), 0, 1)
+        GP._fit_device = lambda *a, **k: pytest.fail("addData refitted although the padding has room")
+        try:
+            GP.addData(xn, np.sin(3 * xn.sum()))
+        finally:
+            del GP._fit_device
+        assert len(GP.X) == N - 1
+        cand = np.vstack([rs.rand(12, D), np.clip(GP.X[rs.randint(0, N - 1, 12)] + 1e-3 * rs.randn(12, D), 0, 1)])
+        cand[12] = np.clip(xn + 1e-3 * rs.randn(D), 0, 1)       # one of them next to the new point
+        check(GP, cand, "noise %g D=%d rows [5, 200], then one near-duplicate" % (noise, D))
