@@ -2,7 +2,7 @@
 // per-device memory pool and its buffer type, the handle (struct ibo_gp) and the helpers one unit lends another.
 //   abi_core.hip    library / options / device memory / pools / handle life cycle
 //   abi_fit.hip     fit, block extension, preference GP, accessors, ibo_cov_matrix, ibo_spd_*
-//   abi_sweep.hip   candidate sweeps, host batches, DIRECT on the GPU objective
+//   abi_sweep.hip   candidate sweeps, host batches, DIRECT on the GPU objective, the constrained acquisition (ibo_cacq_*)
 //   abi_nlml.hip    marginal-likelihood grid and gradient, ibo_trim
 //   abi_legacy.hip  libego's symbols (acqmaxGP, direct, logCDFs) and ibo_direct_host
 // There is no CPU fallback anywhere behind this header: without a gfx950 device every compute entry point returns IBO_ERR_NO_DEVICE.

@@ -1,0 +1,59 @@
+// cacq.hip -- the combine of a constrained acquisition sweep (ibo_cacq_sweep): val = A P per candidate from the (mu, s2) pairs the
+// per-model sweeps left in device scratch, the exclusion balls, the optional per-candidate outputs and one (max, lowest index) partial
+// per 256 candidates for launch_argmax_final.
+//
+// A streaming pass: 16 bytes per model and candidate in, up to 24 out, one erf chain per model.  One thread per candidate, consecutive
+// lanes on consecutive elements of every array (8-byte loads and stores, coalesced), no LDS beyond the four per-wave partials of the
+// reduction.  At 2^20 candidates and two constraints that is 75 MB against three MFMA-bound sweeps of 16.5 ms.
+#include "cacq.h"
+
+// Arg-max rule and reduction of acq_finish_kernel (sweep2.hip): NaN values and excluded candidates never win, the lowest index wins ties.
+__global__ __launch_bounds__(256) void cacq_finish_kernel(CacqArgs a)
+{
+    __shared__ double sv[4];
+    __shared__ int64_t si[4];
+    const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool valid = li < a.M;
+    const int64_t gi = valid ? li : a.M - 1;
+    double A, P;
+    double val = cacq_value_dev(a.spec, [&](int k, double *mu, double *s2) {
+        *mu = a.ms[(size_t)(2 * k) * a.stride + gi];
+        *s2 = a.ms[(size_t)(2 * k + 1) * a.stride + gi];
+    }, &A, &P);
+    const double *xp = a.cand + gi * a.D;
+    bool excl = false;
+    for (int e = 0; e < a.n_excl; e++) {             // (finish_candidate's rule, coordinates read from the candidate array)
+        double d2 = 0.0;
+        for (int j = 0; j < a.D; j++) { double t = xp[j] - a.excl[(size_t)e * a.D + j]; d2 += t * t; }
+        if (!(sqrt(d2) > a.excl_radius)) excl = true;
+    }
+    if (valid) {
+        if (a.out_acq) a.out_acq[li] = A;
+        if (a.out_pof) a.out_pof[li] = P;
+        if (a.out_val) a.out_val[li] = val;
+    }
+    int64_t idx = a.index_base + a.first + li;
+    if (!valid || excl || !(val == val)) { val = -INFINITY; idx = INT64_MAX; }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(val, o);
+        const int64_t oi = __shfl_xor(idx, o);
+        if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
+    }
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = val; si[threadIdx.x >> 6] = idx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++)
+            if (sv[w] > val || (sv[w] == val && si[w] < idx)) { val = sv[w]; idx = si[w]; }
+        a.part_val[blockIdx.x] = val; a.part_idx[blockIdx.x] = idx;
+    }
+}
+
+int launch_cacq_finish(const CacqArgs &a, hipStream_t s)
+{
+    if (a.M < 1 || a.M > a.stride || (a.first & 255)) return (int)hipErrorInvalidValue;
+    const int64_t nblk = (a.M + 255) / 256;
+    hipLaunchKernelGGL(cacq_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+void ibo_touch_cacq() { hipFuncAttributes a; (void)hipFuncGetAttributes(&a, (const void *)cacq_finish_kernel); }     // (see small2.hip: ibo_touch_small2)

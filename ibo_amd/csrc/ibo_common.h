@@ -226,6 +226,37 @@ __device__ __forceinline__ double acq_value_dev(int acq, int erf_mode, double mu
     return ydiff * cdf + sigma * pdf;
 }
 
+// What a constrained acquisition (ibo_cacq_*) is made of beside the models: the objective's acquisition and one (threshold, sense) per
+// constraint model.  sense +1: feasible where c_j <= thresh_j; -1: where c_j >= thresh_j.
+#define IBO_CACQ_MAX 8          // IBO_CACQ_MAX_CON of ibo_abi.h
+struct CacqSpec {
+    int ncon, acq, erf_mode;
+    double ymax, parm;
+    double thresh[IBO_CACQ_MAX];
+    int sense[IBO_CACQ_MAX];
+};
+
+// The constrained acquisition of one candidate: val = A Phi(z_0) Phi(z_1) .., multiplied in that order; A = EI / PI of the objective
+// (acq == 3: A = 1, the pure probability of feasibility), z_j = s_j (t_j - mu_j) / sigma_j, P = prod_j Phi(z_j) (empty product: 1).
+// MS(k, &mu, &s2): the posterior of model k at the candidate, variance clipped -- k = 0 the objective (not asked for when acq == 3),
+// k = 1 + j constraint j.  Phi in the call's erf flavour, as the objective's.
+template <typename MS>
+__device__ __forceinline__ double cacq_value_dev(const CacqSpec &c, MS ms, double *A, double *P)
+{
+    double mu, s2, a = 1.0;
+    if (c.acq != 3) { ms(0, &mu, &s2); a = acq_value_dev(c.acq, c.erf_mode, mu, sqrt(s2), c.ymax, c.parm); }
+    double p = 1.0, v = a;
+    for (int j = 0; j < c.ncon; j++) {
+        ms(1 + j, &mu, &s2);
+        const double z = (double)c.sense[j] * (c.thresh[j] - mu) / sqrt(s2);
+        double cdf, pdf;
+        gauss_cdf_pdf_dev(c.erf_mode, z, &cdf, &pdf);
+        p *= cdf; v *= cdf;
+    }
+    *A = a; *P = p;
+    return v;
+}
+
 // ---- host-side launch API of the kernels (defined in linalg.hip / assemble.hip / update3.hip / sweep*.hip / small2.hip)
 #define IBO_SPLIT_PANEL 64      // rows per workgroup of the small-batch (SPLIT) sweep
 #define IBO_S2_TCAND 32         // candidates per workgroup of sweep2_kernel (sweep2.hip)

@@ -42,7 +42,9 @@ extern "C" {
                              * slower than the launches and removed: both keys are unknown options now); + ibo_gp_loo, ibo_loo_grad (leave-one-out predictions and the LOO-CV
                              * objective with its gradient: additions within 8, nothing else changed); + ibo_gp_remove (observations taken out of a fitted model in
                              * O(N^2): added within 8, nothing else changed); within 8 as well: the ibo_pref_* entries refuse a workspace begun on another
-                             * model (IBO_ERR_STATE where a call used to compute from stale data -- no symbol, signature or valid call order changed) */
+                             * model (IBO_ERR_STATE where a call used to compute from stale data -- no symbol, signature or valid call order changed);
+                             * + ibo_cacq_sweep, ibo_cacq_batch, ibo_cacq_grad_batch, ibo_cacq_direct_max (EI / PI weighted by the probability of feasibility
+                             * under up to eight constraint models: added within 8, nothing else changed) */
 
 /* status codes */
 #define IBO_OK              0
@@ -441,6 +443,78 @@ int ibo_direct_max(ibo_gp_t *gp, int D, const double *lb, const double *ub,
                    int acq, double parm, int erf_mode, double clamp_lo,
                    int maxiter, int maxtime, int maxsample, int compat,
                    double *opt, double *optx, int64_t *nsamples);
+
+/* ---------------------------------------------------------------- constrained acquisition over several handles */
+/*
+ * EI / PI of an objective model weighted by the probability that up to IBO_CACQ_MAX_CON constraint models are feasible (Schonlau
+ * 1998; Gardner et al. 2014; Gelbart et al. 2014).  Every handle has its own X, N, kernel, noise, prior and k* signal variance;
+ * they share D and the device.  With (mu_j, sigma_j^2) what ibo_acq_batch returns for constraint handle con[j] at x (variance
+ * clipped to [clamp_lo, 10]):
+ *   z_j  = sense_j (thresh_j - mu_j) / sigma_j     sense_j = +1: feasible where c_j(x) <= thresh_j;  -1: where c_j(x) >= thresh_j
+ *   P(x) = prod_j Phi(z_j)                          (ncon = 0: 1)
+ *   A(x) = the objective's IBO_ACQ_EI / IBO_ACQ_PI with the call's parm, ymax, erf_mode;  IBO_ACQ_NONE: A = 1, the pure
+ *          probability of feasibility (what one maximises while no feasible point is known);  IBO_ACQ_UCB: IBO_ERR_ARG (a signed
+ *          value times a probability orders nothing)
+ *   val(x) = A(x) P(x), multiplied in the order A, Phi(z_0), Phi(z_1), ...
+ * Phi and phi are those of the call's erf_mode for the constraints as for the objective (IBO_ERF_NR: the truncated constants too).
+ * ymax NaN = max(Y) of the objective handle, as in ibo_acq_sweep; callers normally pass the best FEASIBLE observation.  A handle
+ * may appear more than once (objective and constraint, or two constraints for a band): the handles are evaluated one after the
+ * other.  A call leaves each handle as a plain ibo_acq_sweep / ibo_acq_batch on it would (k* variance, prior, kept sweep state).
+ *
+ * Errors, all four entries: IBO_ERR_NO_DEVICE without a device (checked first); IBO_ERR_ARG for a NULL obj, ncon outside
+ * [0, IBO_CACQ_MAX_CON], NULL con / thresh / sense or a NULL con[j] with ncon > 0, a sense other than +1 / -1, a non-finite
+ * threshold, handles on different devices or with different D, M < 1, a NULL point array, IBO_ACQ_UCB or an unknown acq / erf_mode,
+ * every output NULL; IBO_ERR_STATE if any handle is not fitted.
+ */
+#define IBO_CACQ_MAX_CON 8
+
+/*
+ * The sweep: cand_dev (M x D, DEVICE) and the exclusion balls, index_base and arg-max rule of ibo_acq_sweep -- NaN values and
+ * excluded candidates never win, the largest val wins, the lowest index wins ties (every val 0.0: the first candidate that is not
+ * excluded), best_idx = -1 when everything is excluded.  acq_dev, pof_dev, val_dev: optional DEVICE outputs (M doubles each): A, P,
+ * val.  With ncon = 0, best_val, best_idx and acq_dev are ibo_acq_sweep's, bit for bit.
+ * Cost: one plain sweep per model (the objective's is skipped for IBO_ACQ_NONE) plus one streaming pass of 16 (ncon + 1) bytes per
+ * candidate; that many bytes of device scratch, at most about 1 GiB (more candidates run in chunks), returned before the call
+ * returns.  Blocking.
+ */
+int ibo_cacq_sweep(ibo_gp_t *obj, int ncon, ibo_gp_t *const *con, const double *thresh, const int *sense,
+                   int64_t M, const double *cand_dev, int acq, double parm, int erf_mode, double clamp_lo, double ymax,
+                   int n_excl, const double *excl_host, double excl_radius, int64_t index_base,
+                   double *acq_dev, double *pof_dev, double *val_dev,
+                   double *best_val, int64_t *best_idx);
+
+/*
+ * The same values for points on the HOST (Q_host: M x D), into host arrays (any of acq_host, pof_host, val_host may be NULL, not
+ * all): one ibo_acq_batch per handle, combined on the host.  acq_host is ibo_acq_batch's acquisition of the objective, bit for bit.
+ */
+int ibo_cacq_batch(ibo_gp_t *obj, int ncon, ibo_gp_t *const *con, const double *thresh, const int *sense,
+                   int64_t M, const double *Q_host, int acq, double parm, int erf_mode, double clamp_lo, double ymax,
+                   double *acq_host, double *pof_host, double *val_host);
+
+/*
+ * ibo_cacq_batch's val (val_host, bit for bit) and its gradient with respect to the query point (dval_host: M x D row-major),
+ * composed on the host from ibo_acq_grad_batch per handle, in a fixed order and without dividing by Phi (finite where a factor
+ * underflows):
+ *   dsigma_j = dsigma^2_j / (2 sigma_j)            (0 where handle j's clip is active, as ibo_acq_grad_batch defines it)
+ *   dz_j     = -(sense_j dmu_j + z_j dsigma_j) / sigma_j
+ *   dP       = sum_j phi(z_j) dz_j prod_{i != j} Phi(z_i)
+ *   dval     = dA P + A dP                          (dA = ibo_acq_grad_batch's dacq; 0 for IBO_ACQ_NONE)
+ * Either output may be NULL, not both.  Cost: ibo_acq_grad_batch's per handle.  The analytic gradient: with IBO_ERF_NR it differs
+ * from the derivative of the returned values by about 1e-6 relative (see ibo_acq_grad_batch).
+ */
+int ibo_cacq_grad_batch(ibo_gp_t *obj, int ncon, ibo_gp_t *const *con, const double *thresh, const int *sense,
+                        int64_t M, const double *Q_host, int acq, double parm, int erf_mode, double clamp_lo, double ymax,
+                        double *val_host, double *dval_host);
+
+/*
+ * ibo_direct_max on val: the same DIRECT, options and batched schedule, every batch of sample points evaluated as
+ * ibo_cacq_batch does.  opt = the maximum of val, optx[D] its location, nsamples optional (not all three NULL).  IBO_ERR_ARG
+ * also for NULL bounds or D other than the models'.
+ */
+int ibo_cacq_direct_max(ibo_gp_t *obj, int ncon, ibo_gp_t *const *con, const double *thresh, const int *sense,
+                        int D, const double *lb, const double *ub, int acq, double parm, int erf_mode, double clamp_lo, double ymax,
+                        int maxiter, int maxtime, int maxsample, int compat,
+                        double *opt, double *optx, int64_t *nsamples);
 
 /* DIRECT minimisation of a HOST callback with the reference's semantics
  * (cpp/direct.cpp:329; what ego.utils.optimize.cdirect wraps), plus the sample
