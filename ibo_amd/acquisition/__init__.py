@@ -13,6 +13,8 @@ plus the batched entry point the GPU makes worthwhile:
 
     sweep(model, candidates, acq='ei', ...) -> dict(best_val, best_idx, [mu, s2, acq])
 
+and the knowledge gradient against a reference set (knowledge.py): KnowledgeGradient, sweepKG, maximizeKG, referenceSet.
+
 The default maximize* path is the reference's cdirectGP -> acqmaxGP -> DIRECT
 (ego/acquisition/__init__.py:307-447, cpp/optimizeGP.cpp:262-349) with the tree
 on the host and every batch of sample points evaluated by the HIP sweep kernel.
@@ -341,3 +343,6 @@ def sweep(model, candidates, acq='ei', xi=0.01, delta=0.1, scale=0.2, parm=None,
     for k, v in outs.items():
         res[k] = v.to_host()
     return res
+
+
+from .knowledge import KnowledgeGradient, sweepKG, maximizeKG, referenceSet          # noqa: E402,F401

@@ -3,6 +3,7 @@
 //   abi_core.hip    library / options / device memory / pools / handle life cycle
 //   abi_fit.hip     fit, block extension, preference GP, accessors, ibo_cov_matrix, ibo_spd_*
 //   abi_sweep.hip   candidate sweeps, host batches, DIRECT on the GPU objective, the constrained acquisition (ibo_cacq_*)
+//   abi_kg.hip      the knowledge gradient (ibo_kg_*)
 //   abi_nlml.hip    marginal-likelihood grid and gradient, ibo_trim
 //   abi_legacy.hip  libego's symbols (acqmaxGP, direct, logCDFs) and ibo_direct_host
 // There is no CPU fallback anywhere behind this header: without a gfx950 device every compute entry point returns IBO_ERR_NO_DEVICE.
@@ -43,6 +44,7 @@ int ibo_fail(int code, const char *fmt, ...);
 // ---- option switches (abi_core.hip: ibo_set_option)
 extern std::atomic<int> g_super_min_nb;        // ibo_set_option("super_min_nb", nb): block columns from which a fit runs in super-panels
 extern std::atomic<int> g_host_pipeline, g_fused2_min_nb, g_gallery_prune, g_nlml_batch, g_chol_left, g_dot_override, g_legacy_exact, g_force_path, g_nlml_groups;
+extern std::atomic<int> g_kg_chunk, g_kg_timing;     // abi_kg.hip: candidates per chunk (0: by bytes); per-stage HIP events
 extern std::mutex g_dev_mu[16];             // serialises the per-device workspaces of ibo_nlml_grid / ibo_nlml_grad / ibo_trim
 extern std::atomic<size_t> g_pool_limit;
 

@@ -44,7 +44,9 @@ extern "C" {
                              * O(N^2): added within 8, nothing else changed); within 8 as well: the ibo_pref_* entries refuse a workspace begun on another
                              * model (IBO_ERR_STATE where a call used to compute from stale data -- no symbol, signature or valid call order changed);
                              * + ibo_cacq_sweep, ibo_cacq_batch, ibo_cacq_grad_batch, ibo_cacq_direct_max (EI / PI weighted by the probability of feasibility
-                             * under up to eight constraint models: added within 8, nothing else changed) */
+                             * under up to eight constraint models: added within 8, nothing else changed);
+                             * + ibo_kg_sweep, ibo_kg_batch, ibo_kg_direct_max, ibo_kg_stage_ms (the knowledge gradient against a reference set) and the
+                             * options "kg_chunk", "kg_timing": added within 8, nothing else changed */
 
 /* status codes */
 #define IBO_OK              0
@@ -96,7 +98,7 @@ int         ibo_selftest_mfma(int device, double *max_abs_err);
  * gradients.  DIRECT's small batches and the copies are not event-timed and not in it.  bench.py reports it as gpu_kernel_s_total
  * so that a line can be related to an outside observer's busy-GPU samples. */
 int         ibo_gpu_time_ms(int device, double *ms);
-/* The twelve option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
+/* The fourteen option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
  * Functional:  "legacy_exact" 1/0 -- acqmaxGP in libego's operation order (default) or on the MFMA sweep kernels (see acqmaxGP);
  *   "nlml_batch" B -- matrices per batched factorisation in ibo_nlml_grid (0: as many as 12 GB hold; the values do not depend on it);
  *   "pool_limit_mb" n -- the per-device free list of recycled buffers (ibo_trim);
@@ -110,7 +112,9 @@ int         ibo_gpu_time_ms(int device, double *ms);
  *   candidates, sweep2_kernel above; GEMV / panel-split / first-generation tile kernels where the dot form is not admissible) / 1 GEMV /
  *   2 MFMA tile / 3 panel-split;  "dot_form" -1 auto / 0 / 1 (k* by differences or by the exponent GEMM);  "gallery_prune" 0/1/2 and
  *   "part_levels" 2..4 (see ibo_acq_sweep_incremental);  "host_pipeline" 1/0 (large host batches in overlapped chunks or in one shot);
- *   "chol_left" 1/0 (ibo_nlml_grid's left-looking order or the right-looking one: identical bits).
+ *   "chol_left" 1/0 (ibo_nlml_grid's left-looking order or the right-looking one: identical bits);  "kg_chunk" m (candidates per chunk of
+ *   the ibo_kg_* entries, 0: by bytes -- identical bits).
+ * Diagnostic:  "kg_timing" 1/0 (see ibo_kg_stage_ms).
  * Env: IBO_SWEEP_IMPL=gemv|mfma, IBO_DOT_FORM, IBO_POOL_LIMIT_MB, IBO_HOST_THREADS (the legacy symbol's host crew), IBO_DEVICE (legacy symbols),
  *   IBO_NLML_GROUPS=1..4 (sub-batches of an ibo_nlml_grid batch, each on its own stream; 2; the values do not depend on it).
  * Threading (the reference's library keeps its whole model in process-wide statics, cpp/optimizeGP.cpp:36-55,240-259, and is not
@@ -515,6 +519,63 @@ int ibo_cacq_direct_max(ibo_gp_t *obj, int ncon, ibo_gp_t *const *con, const dou
                         int D, const double *lb, const double *ub, int acq, double parm, int erf_mode, double clamp_lo, double ymax,
                         int maxiter, int maxtime, int maxsample, int compat,
                         double *opt, double *optx, int64_t *nsamples);
+
+/* ---------------------------------------------------------------- knowledge gradient */
+/*
+ * The knowledge gradient of a candidate x against a reference set A = {a_1 .. a_n} (ref_host, nref x D row-major, host memory,
+ * 1 <= nref <= IBO_KG_MAX_REF): the expected rise of the best posterior mean over the set after one more observation at x.
+ * Conventions of ibo_posterior_cov: k and k* with the handle's k* signal variance, v = W k*, unclipped covariances.
+ *   mu_a     the posterior mean at a, the mean prior included: m + k*.aY - m k*.a1 (ibo_acq_grad_batch's formula)
+ *   s2_x     1 + noise - |v_x|^2 clipped to [clamp_lo, 10] (ibo_posterior_batch's rule), sigma_x = sqrt(s2_x)
+ *   b_a(x)   (k(a, x) - v_a.v_x) / sigma_x: the change of mu_a per standard deviation of the new observation
+ *   lines    with_self = 1: line 0 is the candidate's own, mu_0 = mu_x, b_0 = max(1 - |v_x|^2, 0) / sigma_x, and the reference
+ *            lines follow as 1 .. n; with_self = 0: the n reference lines alone
+ *   KG(x)    max(E_Z[max_i (mu_i + b_i Z)] - max_i mu_i, 0), Z standard normal, Phi from libm's erf
+ *            (a NaN -- a NaN candidate coordinate, say -- stays a NaN: it is returned as such and never wins the arg-max)
+ * The evaluation order is part of the definition.  mu* = max_i mu_i is taken off every mu_i first.  Line i owns z in (lo_i, hi_i),
+ * c_ij = (mu_j - mu_i) / (b_i - b_j), lo_i = max of c_ij over {j : b_j < b_i}, hi_i = min of c_ij over {j : b_j > b_i}; a line j with
+ * b_j = b_i puts line i out when mu_j > mu_i, or when mu_j = mu_i and j < i.  Both differences of c_ij are formed as written, so
+ * c_ij and c_ji are the same bits and two nearly identical lines split the axis at one point.  A line with lo_i < hi_i contributes
+ * (mu_i - mu*) (Phi(hi_i) - Phi(lo_i)) + b_i (phi(lo_i) - phi(hi_i)); a wavefront sums the contributions of one candidate, lane l
+ * those of the lines l, l + 64, .. in ascending order, then over the lanes in a fixed butterfly.
+ * The means are dot products over the k* rows (lane l of a wavefront over the rows l, l + 64, .., then the same butterfly), NOT
+ * ibo_posterior_batch's launches, whose route depends on the batch size: they agree with them to rounding, not bit for bit.
+ * A candidate's KG bits depend on the model, the reference set, with_self and clamp_lo and on nothing else: not on M, on its place in
+ * the array, on the chunking, nor on the entry (sweep, host batch, DIRECT) it came through.
+ * Cost: N^2 (nref + M) flops for V = W K* and 2 N nref M for the cross-covariance on the fp64 MFMA pipe; (nref + with_self)^2 M pair
+ * steps with one fp64 division each on the vector ALU -- the larger part from a few hundred reference points on.
+ * Device scratch, from the pool and returned before the call returns: the reference state (2 np Npad doubles while it is built,
+ * np Npad after; np = nref rounded up to 64) and per chunk of candidates K* and V^T (mc Npad doubles each) and the slopes (mc np),
+ * each at most 256 MiB or 256 candidates where that alone is more, mc <= 65280 (ibo_set_option("kg_chunk", m) sets mc, rounded up to 256).
+ * IBO_ERR_NO_DEVICE without a device (checked first); IBO_ERR_ARG for a NULL gp, reference set or candidate array, nref outside
+ * [1, IBO_KG_MAX_REF], M < 1, every output NULL or a non-finite reference coordinate; IBO_ERR_STATE before a fit.
+ * There are no exclusion balls and no gradients with respect to x.
+ */
+#define IBO_KG_MAX_REF 1024
+
+/* M candidates on the device (cand_dev, M x D): kg_dev (device, M, optional) receives the values; best_val / best_idx the maximum
+ * and the first index that attains it, index_base added (-1 if no value is a number). */
+int ibo_kg_sweep(ibo_gp_t *gp, int nref, const double *ref_host, int64_t M, const double *cand_dev, int with_self,
+                 double clamp_lo, int64_t index_base, double *kg_dev, double *best_val, int64_t *best_idx);
+
+/* M host points: kg_host (M) and, all optional, what the values were made of: mu_ref_host (nref), mu_host and s2_host (M, s2
+ * clipped), b_host (M x nref row-major, b_host[x][a] = b_a(q_x)). */
+int ibo_kg_batch(ibo_gp_t *gp, int nref, const double *ref_host, int64_t M, const double *Q_host, int with_self,
+                 double clamp_lo, double *kg_host, double *mu_ref_host, double *mu_host, double *s2_host, double *b_host);
+
+/* ibo_direct_max on KG: the same DIRECT, options and batched schedule; the reference state is built once and stays on the device
+ * across the batches.  opt = the maximum, optx[D] its location, nsamples optional (not all three NULL).  IBO_ERR_ARG also for NULL
+ * bounds or D other than the model's. */
+int ibo_kg_direct_max(ibo_gp_t *gp, int nref, const double *ref_host, int D, const double *lb, const double *ub,
+                      int with_self, double clamp_lo, int maxiter, int maxtime, int maxsample, int compat,
+                      double *opt, double *optx, int64_t *nsamples);
+
+/* With ibo_set_option("kg_timing", 1) every ibo_kg_* call of this thread waits after each chunk and adds the device time of its
+ * stages (HIP events) to ms[IBO_KG_STAGES]: the reference state, K*, V^T = K* W^T, the row kernel, the cross-covariance, the
+ * expected maximum.  reset != 0 clears the sums after they are read; ms may be NULL.  A diagnostic: the option is process-wide
+ * (every thread's ibo_kg_* calls wait after each chunk while it is set), the sums are per thread. */
+#define IBO_KG_STAGES 6
+int ibo_kg_stage_ms(double *ms, int reset);
 
 /* DIRECT minimisation of a HOST callback with the reference's semantics
  * (cpp/direct.cpp:329; what ego.utils.optimize.cdirect wraps), plus the sample
