@@ -1,0 +1,44 @@
+// abi_eval.h -- what the evaluation units (abi_sweep.hip, abi_batch.hip, abi_cacq.hip, abi_kg.hip) share beyond abi_internal.h: the sweep
+// request, the host batch, and the ONE copy of the arg-max read-back, the exclusion upload, the timed span, the V^T rows and the DIRECT driver.
+#pragma once
+#include "abi_internal.h"
+
+// What one sweep is asked for: the arguments of ibo_acq_sweep, and what the library's own callers add to them.  Lives on the caller's stack.
+struct SweepRequest {
+    int64_t M = 0;
+    const double *cand_dev = nullptr;            // M x D, where the kernels read them (device memory, or pinned host memory)
+    const double *cand_host = nullptr;           // the same candidates where the HOST can read them (pinned staging), or NULL
+    int acq = IBO_ACQ_NONE, erf_mode = IBO_ERF_LIBM;
+    double parm = 0.0, clamp_lo = 0.0, ymax = NAN;       // ymax NaN: the model's largest observation
+    int n_excl = 0; const double *excl_host = nullptr; double excl_radius = 0.0;
+    int64_t index_base = 0;
+    double *mu_dev = nullptr, *s2_dev = nullptr, *acq_dev = nullptr;     // per-candidate outputs, optional
+    double *best_val = nullptr; int64_t *best_idx = nullptr;             // the arg-max, on the host (both NULL: no read-back, no synchronisation)
+    bool incremental = false;                    // keep the candidates' state on the handle (ibo_acq_sweep_incremental)
+    bool timed = true;                           // kernel-time events around the launches (small2.hip's only: the others always record them)
+    bool signal = false;                         // the caller will spin on the handle's host-visible word instead of an event, where the route can write it
+    bool device_result = false;                  // (value, index) stay in res_v / res_i for the exchange
+};
+
+// ---- abi_sweep.hip
+int run_sweep(ibo_gp *g, const SweepRequest &r);
+// the exclusion balls' centres (n_excl x D, host) into the handle's buffer; *n and *ptr are left alone when there are none
+int upload_exclusions(ibo_gp *g, int n_excl, const double *excl_host, int *n, const double **ptr);
+// (res_v, res_i) -> the host, after which the stream is idle; either pointer may be NULL
+int read_result(ibo_gp *g, double *best_val, int64_t *best_idx);
+// the winner among nblk per-workgroup partials (launch_argmax_final into res_v / res_i), then read_result
+int argmax_readback(ibo_gp *g, const double *part_val, const int64_t *part_idx, int64_t nblk, double *best_val, int64_t *best_idx);
+// closes the span an entry opened by recording ev0: records ev1, waits for it and adds ev0 -> ev1 to the device's GPU time
+int finish_span(ibo_gp *g);
+
+// ---- abi_batch.hip
+// host points in, host arrays out (any of mu / s2 / acq may be NULL): one sweep, or the pipelined chunks of a large batch
+int eval_host_points(ibo_gp *g, int64_t M, const double *Q_host, int acq, double parm, int erf_mode,
+                     double clamp_lo, double *mu_host, double *s2_host, double *acq_host, double ymax = NAN);
+// V^T = (W K*)^T of m points (device, m x D; mp = m rounded up to the covariance tile): K* into kt, the rows into vt, both mp x Npad
+int vt_rows(ibo_gp *g, const double *pts_dev, int m, int mp, double *kt, double *vt, hipStream_t s);
+// The DIRECT driver of every GPU objective.  value: the objective's values at a batch of points, to be MAXIMISED (negated here for the
+// minimiser).  label: what IBO_DEBUG's line calls the search.  Returns the search's status, or fills the maximum, its place and the
+// number of samples (each optional).
+int direct_maximize(const ibo::batch_eval_t &value, const char *label, int D, const double *lb, const double *ub,
+                    int maxiter, int maxtime, int maxsample, int compat, double *opt, double *optx, int64_t *nsamples);

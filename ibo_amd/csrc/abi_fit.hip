@@ -103,6 +103,14 @@ static int check_info(ibo_gp *g, int *info)
     return IBO_OK;
 }
 
+// after the stream has passed fit1: fit0 -> fit1 is the fit's time (ibo_gp_last_fit_ms) and goes to the device's GPU time
+static int fit_span(ibo_gp *g)
+{
+    HIP_TRY(hipEventElapsedTime(&g->fit_ms, g->fit0, g->fit1));
+    gpu_time_add(g->device, g->fit_ms);
+    return IBO_OK;
+}
+
 // R = K(X, X) with the reference's hard-wired diagonal 1 + noise (ego/gaussianprocess/__init__.py:138), over the rows the
 // model holds now, by the kernel and in the order of operations the fit's own covariance pass uses: what a fit, or a fit
 // and its extensions, would have written had they kept R up to date.
@@ -162,8 +170,7 @@ static int fit_factor(ibo_gp *g, const KParams &kp, int N, double noise, bool ha
     KERNEL_TRY(launch_alpha(g->W.p, N, Np, g->Y.p, g->tmp.p, g->alphaY.p, g->alpha1.p, s));
     HIP_TRY(hipEventRecord(g->fit1, s));
     IBO_TRY(check_info(g, info));
-    HIP_TRY(hipEventElapsedTime(&g->fit_ms, g->fit0, g->fit1));
-    gpu_time_add(g->device, g->fit_ms);
+    IBO_TRY(fit_span(g));
     g->fitted = true;
     g->plain_fit = !have_A;
     g->fit_epoch++;
@@ -242,8 +249,7 @@ extern "C" int ibo_gp_extend(ibo_gp_t *g, int n, const double *Xnew, const doubl
         if (info) *info = h;
         return fail(IBO_ERR_NOT_PD, "matrix is not positive definite (pivot %d)", h);
     }
-    HIP_TRY(hipEventElapsedTime(&g->fit_ms, g->fit0, g->fit1));
-    gpu_time_add(g->device, g->fit_ms);
+    IBO_TRY(fit_span(g));
     if (g->dot_form) {                              // |x~|^2 of the new points still admits the dot form?
         for (int i = 0; i < n && g->dot_form; i++)
             if (ibo_scaled_norm2(g->kp_fit.sw, Xnew + (size_t)i * D, D) > IBO_DOT_GUARD) g->dot_form = 0;
@@ -313,8 +319,7 @@ extern "C" int ibo_gp_remove(ibo_gp_t *g, int n, const int *rows_host, const dou
     HIP_TRY(hipEventRecord(g->fit1, s));
     g->N = N1;                                          // (what the device holds now, whatever the info word says)
     IBO_TRY(check_info(g, info));                       // synchronises: yp and the pool buffer may go
-    HIP_TRY(hipEventElapsedTime(&g->fit_ms, g->fit0, g->fit1));
-    gpu_time_add(g->device, g->fit_ms);
+    IBO_TRY(fit_span(g));
     g->maxY = my;
     g->Yhost.assign(Y_rest, Y_rest + N1);
     g->L_upper_dirty = true;
@@ -371,8 +376,7 @@ int fit_from_inverse(ibo_gp *g, int ktype, int N, int D, const double *X, const 
     KERNEL_TRY(launch_alpha(g->W.p, N, Np, g->Y.p, g->tmp.p, g->alphaY.p, g->alpha1.p, s));
     HIP_TRY(hipEventRecord(g->fit1, s));
     IBO_TRY(check_info(g, nullptr));
-    HIP_TRY(hipEventElapsedTime(&g->fit_ms, g->fit0, g->fit1));
-    gpu_time_add(g->device, g->fit_ms);
+    IBO_TRY(fit_span(g));
     g->fitted = true;
     g->plain_fit = false;
     g->fit_epoch++;

@@ -2,8 +2,11 @@
 // per-device memory pool and its buffer type, the handle (struct ibo_gp) and the helpers one unit lends another.
 //   abi_core.hip    library / options / device memory / pools / handle life cycle
 //   abi_fit.hip     fit, block extension, preference GP, accessors, ibo_cov_matrix, ibo_spd_*
-//   abi_sweep.hip   candidate sweeps, host batches, DIRECT on the GPU objective, the constrained acquisition (ibo_cacq_*)
+//   abi_sweep.hip   candidate sweeps: the routes, run_sweep, the sweep entries
+//   abi_batch.hip   host batches, query-point gradients, joint posterior and draws, DIRECT on a GPU objective
+//   abi_cacq.hip    the constrained acquisition (ibo_cacq_*)
 //   abi_kg.hip      the knowledge gradient (ibo_kg_*)
+//                   (these four are the evaluation units: what they share among themselves is in abi_eval.h)
 //   abi_nlml.hip    marginal-likelihood grid and gradient, ibo_trim
 //   abi_legacy.hip  libego's symbols (acqmaxGP, direct, logCDFs) and ibo_direct_host
 // There is no CPU fallback anywhere behind this header: without a gfx950 device every compute entry point returns IBO_ERR_NO_DEVICE.
@@ -180,4 +183,4 @@ int fit_from_inverse(ibo_gp *g, int ktype, int N, int D, const double *X, const 
                      const double *hyper, int nhyper, double sf2, double noise, const double *invR);      // abi_fit.hip
 int direct_on_gp(ibo_gp *g, int D, const double *lb, const double *ub, int acq, double parm, int erf_mode,
                  double clamp_lo, int maxiter, int maxtime, int maxsample, int compat,
-                 double *opt, double *optx, int64_t *nsamples);                                           // abi_sweep.hip
+                 double *opt, double *optx, int64_t *nsamples);                                           // abi_batch.hip

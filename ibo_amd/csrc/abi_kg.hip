@@ -8,7 +8,7 @@
 // Scratch, all from the pool and handed back on every exit path: the reference state, 2 np Npad doubles while it is built and np Npad
 // after (np = nref rounded up to 64: 168 MiB each at 20480 rows and 1024 points); per chunk K* and V^T (mc Npad doubles each) and the
 // slopes (mc np doubles), each at most 256 MiB -- or 256 candidates where that alone is more -- and never more than 65280 candidates.
-#include "abi_internal.h"
+#include "abi_eval.h"
 #include "cov.h"
 #include "kg.h"
 
@@ -70,7 +70,7 @@ KgRowsArgs rows_args(const ibo_gp *g, const double *Kt, const double *Vt, const 
 // The reference state; the device is idle when this returns.
 int kg_begin(ibo_gp *g, KgState &st, int nref, const double *ref_host, int with_self, double clamp_lo)
 {
-    const int N = g->N, Np = g->Npad, D = g->D;
+    const int Np = g->Npad, D = g->D;
     hipStream_t s = g->stream;
     st.g = g; st.n = nref; st.np = round_up(nref, IBO_COV_TILE); st.with_self = with_self ? 1 : 0; st.clamp_lo = clamp_lo;
     st.timing = g_kg_timing != 0;
@@ -85,8 +85,7 @@ int kg_begin(ibo_gp *g, KgState &st, int nref, const double *ref_host, int with_
     st.muA_host.resize((size_t)nref);
     IBO_TRY(kg_mark(st, 0));
     HIP_TRY(hipMemcpyAsync(st.A.p, ref_host, sizeof(double) * (size_t)nref * D, hipMemcpyHostToDevice, s));
-    KERNEL_TRY(launch_cov_kstar(g->kp, g->Xp.p, N, Np, g->DP, st.A.p, nref, st.np, ktA.p, s));
-    KERNEL_TRY(launch_cov_tri(ktA.p, (size_t)Np, g->W.p, (size_t)Np, N, st.np, Np, st.vtA.p, (size_t)Np, s));
+    IBO_TRY(vt_rows(g, st.A.p, nref, st.np, ktA.p, st.vtA.p, s));
     KgRowsArgs r = rows_args(g, ktA.p, st.vtA.p, st.A.p, nref, clamp_lo);
     r.mu = st.muA.p;
     KERNEL_TRY(launch_kg_rows(r, s));
@@ -166,17 +165,6 @@ int kg_eval_host(KgState &st, int64_t M, const double *Q_host, double *kg_host, 
     return IBO_OK;
 }
 
-int kg_time(ibo_gp *g)
-{
-    hipStream_t s = g->stream;
-    HIP_TRY(hipEventRecord(g->ev1, s));
-    HIP_TRY(hipEventSynchronize(g->ev1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, g->ev0, g->ev1));
-    gpu_time_add(g->device, ms);
-    return IBO_OK;
-}
-
 }  // namespace
 
 extern "C" int ibo_kg_sweep(ibo_gp_t *g, int nref, const double *ref_host, int64_t M, const double *cand_dev, int with_self,
@@ -201,20 +189,8 @@ extern "C" int ibo_kg_sweep(ibo_gp_t *g, int nref, const double *ref_host, int64
         IBO_TRY(kg_chunk(st, m, cand_dev + (size_t)c0 * D, out));
         if (want_best) KERNEL_TRY(launch_kg_argmax(out, m, c0, index_base, pv.p + c0 / 256, pi.p + c0 / 256, s));
     }
-    if (want_best) {
-        IBO_TRY(g->res_v.ensure(1)); IBO_TRY(g->res_i.ensure(1));
-        SweepArgs f;
-        memset(&f, 0, sizeof(f));
-        f.part_val = pv.p; f.part_idx = pi.p; f.result_val = g->res_v.p; f.result_idx = g->res_i.p;
-        KERNEL_TRY(launch_argmax_final(f, nblk, s));
-        double hv; int64_t hi;
-        HIP_TRY(hipMemcpyAsync(&hv, g->res_v.p, sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&hi, g->res_i.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (best_val) *best_val = hv;
-        if (best_idx) *best_idx = hi;
-    }
-    return kg_time(g);                                       // (waits for the stream: the scratch goes back to the pool after it)
+    if (want_best) IBO_TRY(argmax_readback(g, pv.p, pi.p, nblk, best_val, best_idx));
+    return finish_span(g);                                      // (waits for the stream: the scratch goes back to the pool after it)
 }
 
 extern "C" int ibo_kg_batch(ibo_gp_t *g, int nref, const double *ref_host, int64_t M, const double *Q_host, int with_self,
@@ -227,10 +203,10 @@ extern "C" int ibo_kg_batch(ibo_gp_t *g, int nref, const double *ref_host, int64
     IBO_TRY(kg_begin(g, st, nref, ref_host, with_self, clamp_lo));
     if (mu_ref_host) memcpy(mu_ref_host, st.muA_host.data(), sizeof(double) * (size_t)nref);
     if (kg_host || mu_host || s2_host || b_host) IBO_TRY(kg_eval_host(st, M, Q_host, kg_host, mu_host, s2_host, b_host));
-    return kg_time(g);
+    return finish_span(g);
 }
 
-// direct_on_gp's shape with the reference state kept on the device across the batches
+// direct_on_gp with the reference state kept on the device across the batches
 extern "C" int ibo_kg_direct_max(ibo_gp_t *g, int nref, const double *ref_host, int D, const double *lb, const double *ub,
                                  int with_self, double clamp_lo, int maxiter, int maxtime, int maxsample, int compat,
                                  double *opt, double *optx, int64_t *nsamples)
@@ -240,32 +216,12 @@ extern "C" int ibo_kg_direct_max(ibo_gp_t *g, int nref, const double *ref_host, 
     if (D != g->D) return fail(IBO_ERR_ARG, "bounds have %d dimensions, the model has %d", D, g->D);
     KgState st;
     IBO_TRY(kg_begin(g, st, nref, ref_host, with_self, clamp_lo));
-    const bool dbg = getenv("IBO_DEBUG") != nullptr;
-    double t_eval = 0.0; int n_batches = 0; int64_t n_pts = 0;
-    ibo::batch_eval_t ev = [&](const double *pts, int n, double *vals) -> int {
-        struct timespec a0, a1;
-        if (dbg) clock_gettime(CLOCK_MONOTONIC, &a0);
-        const int rc = kg_eval_host(st, n, pts, vals, nullptr, nullptr, nullptr);
-        if (dbg) { clock_gettime(CLOCK_MONOTONIC, &a1); t_eval += (a1.tv_sec - a0.tv_sec) * 1e3 + (a1.tv_nsec - a0.tv_nsec) * 1e-6; n_batches++; n_pts += n; }
-        if (rc) return rc;
-        for (int i = 0; i < n; i++) vals[i] = -vals[i];     // DIRECT minimises the negated value
-        return 0;
+    const ibo::batch_eval_t value = [&](const double *pts, int n, double *vals) -> int {
+        return kg_eval_host(st, n, pts, vals, nullptr, nullptr, nullptr);
     };
-    ibo::DirectOptions o;
-    o.maxiter = maxiter; o.maxtime = maxtime; o.maxsample = maxsample; o.compat = compat != 0;
-    o.per_rectangle = false;
-    struct timespec w0, w1;
-    clock_gettime(CLOCK_MONOTONIC, &w0);
-    ibo::DirectResult r = ibo::direct_minimize(ev, D, lb, ub, o);
-    clock_gettime(CLOCK_MONOTONIC, &w1);
-    if (dbg) fprintf(stderr, "[libibo_hip] knowledge-gradient DIRECT (%d reference points): %d iterations, %lld samples, %d batches (%lld points): %.2f ms total, %.2f ms in evaluation\n",
-                     nref, r.iterations, (long long)r.nsamples, n_batches, (long long)n_pts,
-                     (w1.tv_sec - w0.tv_sec) * 1e3 + (w1.tv_nsec - w0.tv_nsec) * 1e-6, t_eval);
-    if (r.status) return r.status;
-    if (opt) *opt = -r.fmin;
-    if (optx) for (int i = 0; i < D; i++) optx[i] = r.xmin[i];
-    if (nsamples) *nsamples = r.nsamples;
-    return IBO_OK;
+    char label[64];
+    snprintf(label, sizeof(label), "knowledge-gradient DIRECT (%d reference points)", nref);
+    return direct_maximize(value, label, D, lb, ub, maxiter, maxtime, maxsample, compat, opt, optx, nsamples);
 }
 
 extern "C" int ibo_kg_stage_ms(double *ms, int reset)

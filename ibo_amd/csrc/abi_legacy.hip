@@ -123,17 +123,22 @@ extern "C" const double *acqmaxGP(int ndim, double *lb, double *ub, double *invR
     return res;
 }
 
-extern "C" const double *direct(objective_t objective, int ndim, double *lb, double *ub, int maxiter,
-                                int maxtime, int maxsample)
+// a host callback that takes one point at a time (and may write to it) as DIRECT's batch objective
+static ibo::batch_eval_t objective_batch(objective_t objective, int ndim)
 {
-    std::vector<double> x(ndim);
-    ibo::batch_eval_t ev = [&](const double *pts, int n, double *vals) -> int {
+    return [objective, ndim, x = std::vector<double>(ndim)](const double *pts, int n, double *vals) mutable -> int {
         for (int p = 0; p < n; p++) {
             for (int i = 0; i < ndim; i++) x[i] = pts[(size_t)p * ndim + i];
             vals[p] = objective(ndim, x.data());
         }
         return 0;
     };
+}
+
+extern "C" const double *direct(objective_t objective, int ndim, double *lb, double *ub, int maxiter,
+                                int maxtime, int maxsample)
+{
+    const ibo::batch_eval_t ev = objective_batch(objective, ndim);
     ibo::DirectOptions o;
     o.maxiter = maxiter; o.maxtime = maxtime; o.maxsample = maxsample; o.compat = true; o.per_rectangle = true;
     ibo::DirectResult r = ibo::direct_minimize(ev, ndim, lb, ub, o);
@@ -161,14 +166,7 @@ extern "C" int ibo_direct_host(objective_t objective, int ndim, const double *lb
                                int maxtime, int maxsample, int compat, double *fmin, double *xmin, int64_t *nsamples)
 {
     if (!objective || !lb || !ub) return fail(IBO_ERR_ARG, "NULL argument");
-    std::vector<double> x(ndim);
-    ibo::batch_eval_t ev = [&](const double *pts, int n, double *vals) -> int {
-        for (int p = 0; p < n; p++) {
-            for (int i = 0; i < ndim; i++) x[i] = pts[(size_t)p * ndim + i];
-            vals[p] = objective(ndim, x.data());
-        }
-        return 0;
-    };
+    const ibo::batch_eval_t ev = objective_batch(objective, ndim);
     ibo::DirectOptions o;
     // bit 1 of `compat`: the objective is called on one batch per iteration (probes + guessed child centres), the schedule
     // the GPU objective runs under -- same (fmin, xmin, nsamples) as the per-rectangle call order (tested)
@@ -179,4 +177,3 @@ extern "C" int ibo_direct_host(objective_t objective, int ndim, const double *lb
     if (nsamples) *nsamples = r.nsamples;
     return IBO_OK;
 }
-

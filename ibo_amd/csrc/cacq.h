@@ -1,5 +1,5 @@
 // cacq.h -- the constrained acquisition's combine (cacq.hip): the streaming pass over the per-model (mu, s2) a call's sweeps left in
-// device scratch, and the host twin of its Gaussian cdf / pdf for host batches and their gradients (abi_sweep.hip: ibo_cacq_*).
+// device scratch, and the host twin of its Gaussian cdf / pdf for host batches and their gradients (abi_cacq.hip: ibo_cacq_*).
 #pragma once
 #include "ibo_common.h"
 

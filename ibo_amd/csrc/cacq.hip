@@ -7,11 +7,9 @@
 // reduction.  At 2^20 candidates and two constraints that is 75 MB against three MFMA-bound sweeps of 16.5 ms.
 #include "cacq.h"
 
-// Arg-max rule and reduction of acq_finish_kernel (sweep2.hip): NaN values and excluded candidates never win, the lowest index wins ties.
+// NaN values and excluded candidates never win the arg-max (block256_argmax's rule)
 __global__ __launch_bounds__(256) void cacq_finish_kernel(CacqArgs a)
 {
-    __shared__ double sv[4];
-    __shared__ int64_t si[4];
     const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool valid = li < a.M;
     const int64_t gi = valid ? li : a.M - 1;
@@ -34,18 +32,7 @@ __global__ __launch_bounds__(256) void cacq_finish_kernel(CacqArgs a)
     }
     int64_t idx = a.index_base + a.first + li;
     if (!valid || excl || !(val == val)) { val = -INFINITY; idx = INT64_MAX; }
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(val, o);
-        const int64_t oi = __shfl_xor(idx, o);
-        if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = val; si[threadIdx.x >> 6] = idx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++)
-            if (sv[w] > val || (sv[w] == val && si[w] < idx)) { val = sv[w]; idx = si[w]; }
-        a.part_val[blockIdx.x] = val; a.part_idx[blockIdx.x] = idx;
-    }
+    block256_argmax(val, idx, a.part_val, a.part_idx);
 }
 
 int launch_cacq_finish(const CacqArgs &a, hipStream_t s)

@@ -1,4 +1,4 @@
-// cov.h -- the joint-posterior kernels of ibo_posterior_cov / ibo_posterior_sample (cov.hip) and what the ABI unit (abi_sweep.hip)
+// cov.h -- the joint-posterior kernels of ibo_posterior_cov / ibo_posterior_sample (cov.hip) and what the ABI units (abi_batch.hip, abi_kg.hip)
 // hands them.  Every matrix is row-major with 64-bit offsets: Sigma reaches 2^31 bytes at M = 16384, K* and V 2.1 GB at N = 16400.
 #pragma once
 #include "ibo_common.h"

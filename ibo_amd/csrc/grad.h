@@ -1,4 +1,4 @@
-// grad.h -- the gradient kernels of ibo_acq_grad_batch (grad.hip) and what the ABI unit (abi_sweep.hip) hands them.
+// grad.h -- the gradient kernels of ibo_acq_grad_batch (grad.hip) and what the ABI unit (abi_batch.hip) hands them.
 #pragma once
 #include "ibo_common.h"
 

@@ -351,6 +351,32 @@ __device__ __forceinline__ double finish_candidate(const SweepArgs &a, const dou
     return val;
 }
 
+// The arg-max rule, for every kernel that picks a winner: the larger value wins, the lower index wins ties.  A lane that must never win
+// (out of range, excluded, NaN) comes in with (-inf, INT64_MAX) -- its kernel's own masking line, whose condition differs per kernel.
+// wave_argmax: every lane of the wave ends with the wave's winner.
+__device__ __forceinline__ void wave_argmax(double &v, int64_t &i)
+{
+    for (int o = 32; o > 0; o >>= 1) {
+        double ov = __shfl_xor(v, o);
+        int64_t oi = __shfl_xor(i, o);
+        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+    }
+}
+// ... and of a workgroup of 256 threads: the four waves' winners through LDS; thread 0 stores the workgroup's partial for launch_argmax_final
+__device__ __forceinline__ void block256_argmax(double val, int64_t idx, double *part_val, int64_t *part_idx)
+{
+    __shared__ double sv[4];
+    __shared__ int64_t si[4];
+    wave_argmax(val, idx);
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = val; si[threadIdx.x >> 6] = idx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++)
+            if (sv[w] > val || (sv[w] == val && si[w] < idx)) { val = sv[w]; idx = si[w]; }
+        part_val[blockIdx.x] = val; part_idx[blockIdx.x] = idx;
+    }
+}
+
 int launch_sweep_mfma(const SweepArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 int launch_sweep_gemv(const SweepArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 // large batches, dot form: 32-candidate tiles, 1024-row panels, exponent GEMM on the MFMA unit (sweep2.hip)

@@ -127,28 +127,15 @@ __global__ __launch_bounds__(256) void kg_epigraph_kernel(KgEpiArgs a)
     if (valid && lane == 0) a.kg[xr] = sum < 0.0 ? 0.0 : sum;            // (not fmax: a NaN stays a NaN, and the arg-max passes it over)
 }
 
-// Arg-max rule and reduction of cacq_finish_kernel (cacq.hip): NaN never wins, the lowest index wins ties.
+// A NaN never wins the arg-max (block256_argmax's rule)
 __global__ __launch_bounds__(256) void kg_argmax_kernel(const double *__restrict__ kg, int64_t m, int64_t first, int64_t index_base,
                                                         double *__restrict__ part_val, int64_t *__restrict__ part_idx)
 {
-    __shared__ double sv[4];
-    __shared__ int64_t si[4];
     const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
     double val = li < m ? kg[li] : -INFINITY;
     int64_t idx = index_base + first + li;
     if (!(li < m) || !(val == val)) { val = -INFINITY; idx = INT64_MAX; }
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(val, o);
-        const int64_t oi = __shfl_xor(idx, o);
-        if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = val; si[threadIdx.x >> 6] = idx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++)
-            if (sv[w] > val || (sv[w] == val && si[w] < idx)) { val = sv[w]; idx = si[w]; }
-        part_val[blockIdx.x] = val; part_idx[blockIdx.x] = idx;
-    }
+    block256_argmax(val, idx, part_val, part_idx);
 }
 
 int launch_kg_rows(const KgRowsArgs &a, hipStream_t s)

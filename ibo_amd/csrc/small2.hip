@@ -351,11 +351,7 @@ __device__ __forceinline__ bool small_finish_body(const SweepArgs &a, const doub
     double val = finish_candidate<SYSOUT>(a, a.cand + ci * a.kp.D, q, my, m1, li, valid, excl);
     int64_t idx = a.index_base + li;
     if (!valid || excl || !(val == val)) { val = -INFINITY; idx = INT64_MAX; }
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(val, o);
-        const int64_t oi = __shfl_xor(idx, o);
-        if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
-    }
+    wave_argmax(val, idx);
     if (lane == 0 && a.part_val) { a.part_val[item] = val; a.part_idx[item] = idx; }
     SST(2, 2);
     return true;

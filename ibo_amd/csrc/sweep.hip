@@ -25,15 +25,6 @@
 
 #define TC 64          // candidates per workgroup
 
-__device__ __forceinline__ void wave_argmax(double &v, int64_t &i)
-{
-    for (int o = 32; o > 0; o >>= 1) {
-        double ov = __shfl_xor(v, o);
-        int64_t oi = __shfl_xor(i, o);
-        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-    }
-}
-
 // Tile configuration of the main kernel.  NW waves per workgroup, each owning RBW
 // row-blocks (16 rows) x 4 candidate-blocks (16 candidates) of the 512-row panel:
 // NW * RBW = 32.  KCH = rows of K* per LDS stage.  fp64 MFMA issues at one per 64

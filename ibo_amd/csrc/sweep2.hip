@@ -38,8 +38,6 @@
 // candidate.  Summation order and formulas are those of finish_candidate (shared with sweep.hip's epilogue).
 __global__ __launch_bounds__(256) void acq_finish_kernel(SweepArgs a)
 {
-    __shared__ double sv[4];
-    __shared__ int64_t si[4];
     const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool valid = li < a.M;
     const int64_t gi = valid ? li : a.M - 1;
@@ -48,18 +46,7 @@ __global__ __launch_bounds__(256) void acq_finish_kernel(SweepArgs a)
     double val = finish_candidate(a, a.cand + gi * a.kp.D, q, a.qpart[a.M + gi], a.qpart[2 * a.M + gi], li, valid, excl);
     int64_t idx = a.index_base + li;
     if (!valid || excl || !(val == val)) { val = -INFINITY; idx = INT64_MAX; }
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(val, o);
-        const int64_t oi = __shfl_xor(idx, o);
-        if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = val; si[threadIdx.x >> 6] = idx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++)
-            if (sv[w] > val || (sv[w] == val && si[w] < idx)) { val = sv[w]; idx = si[w]; }
-        a.part_val[blockIdx.x] = val; a.part_idx[blockIdx.x] = idx;
-    }
+    block256_argmax(val, idx, a.part_val, a.part_idx);
 }
 
 // The kept state's values per TILE of 32 candidates (same arithmetic as acq_finish_kernel): tile_ub = the largest value of the
