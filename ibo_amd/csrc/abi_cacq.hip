@@ -3,6 +3,8 @@
 #include "abi_eval.h"
 #include "cacq.h"
 
+std::atomic<int> g_cacq_chunk{0};     // ibo_set_option("cacq_chunk", m): candidates per chunk of ibo_cacq_sweep (rounded up to 256); 0: by bytes
+
 static_assert(IBO_CACQ_MAX == IBO_CACQ_MAX_CON, "the kernel argument arrays hold every constraint the ABI admits");
 
 // the leading arguments of the four ibo_cacq_* entries
@@ -64,6 +66,7 @@ extern "C" int ibo_cacq_sweep(ibo_gp_t *obj, int ncon, ibo_gp_t *const *con, con
     a.D = D; a.index_base = index_base; a.excl_radius = excl_radius;
     IBO_TRY(upload_exclusions(g, n_excl, excl_host, &a.n_excl, &a.excl));
     int64_t mc = (((int64_t)1 << 30) / (16 * (ncon + 1))) / 256 * 256;        // candidates per chunk: a multiple of the combine's workgroup
+    if (g_cacq_chunk > 0) mc = ((int64_t)g_cacq_chunk + 255) / 256 * 256;
     if (M <= mc) mc = M;
     const int64_t nblk = (M + 255) / 256;
     ScopedBuf<double> ms, pv;

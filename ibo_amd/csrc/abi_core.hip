@@ -348,6 +348,7 @@ extern "C" int ibo_set_option(const char *key, int value)
     if (!strcmp(key, "fused2_min_nb")) { if (value < 1) return fail(IBO_ERR_ARG, "fused2_min_nb < 1"); g_fused2_min_nb = value; return IBO_OK; }
     if (!strcmp(key, "super_min_nb")) { if (value < 2 * kSuperPanel) return fail(IBO_ERR_ARG, "super_min_nb < %d", 2 * kSuperPanel); g_super_min_nb = value; return IBO_OK; }
     if (!strcmp(key, "kg_chunk")) { if (value < 0) return fail(IBO_ERR_ARG, "kg_chunk < 0"); g_kg_chunk = value; return IBO_OK; }
+    if (!strcmp(key, "cacq_chunk")) { if (value < 0) return fail(IBO_ERR_ARG, "cacq_chunk < 0"); g_cacq_chunk = value; return IBO_OK; }
     if (!strcmp(key, "kg_timing")) { g_kg_timing = value; return IBO_OK; }
     if (!strcmp(key, "arena_mb")) { if (value < 0) return fail(IBO_ERR_ARG, "arena_mb < 0"); g_arena_mb = value; return IBO_OK; }
     if (!strcmp(key, "pool_limit_mb")) { if (value < 0) return fail(IBO_ERR_ARG, "pool_limit_mb < 0"); g_pool_limit = (size_t)value << 20; return IBO_OK; }

@@ -47,6 +47,7 @@ int ibo_fail(int code, const char *fmt, ...);
 // ---- option switches (abi_core.hip: ibo_set_option)
 extern std::atomic<int> g_super_min_nb;        // ibo_set_option("super_min_nb", nb): block columns from which a fit runs in super-panels
 extern std::atomic<int> g_host_pipeline, g_fused2_min_nb, g_gallery_prune, g_nlml_batch, g_chol_left, g_dot_override, g_legacy_exact, g_force_path, g_nlml_groups;
+extern std::atomic<int> g_cacq_chunk;                // abi_cacq.hip: candidates per chunk of ibo_cacq_sweep (0: by bytes)
 extern std::atomic<int> g_kg_chunk, g_kg_timing;     // abi_kg.hip: candidates per chunk (0: by bytes); per-stage HIP events
 extern std::mutex g_dev_mu[16];             // serialises the per-device workspaces of ibo_nlml_grid / ibo_nlml_grad / ibo_trim
 extern std::atomic<size_t> g_pool_limit;

@@ -325,9 +325,18 @@ __device__ __forceinline__ double finish_candidate(const SweepArgs &a, const dou
                                                    int64_t li, bool valid, bool &excluded)
 {
     auto X = [&](int j) { return SYS ? __hip_atomic_load(xp + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : xp[j]; };
+    // A candidate with a NaN coordinate has a NaN posterior, and k* does not say so by itself: v_max_f64 returns its other operand, so
+    // exp_fast's clamp, sqrt_fast's floor and s2_kstar's z = fmax(-2y, 0) turn the NaN exponent into a point infinitely far away (the
+    // squared exponential by differences: k* = 3e-308, the prior variance -- a value that can win) or on top of every observation (Matern).
+    // The coordinates are in L2 from the staging; the NaN goes into the sums themselves (no flag kept alive: see the note on a.kp.D above).
+    // Not under SYS: those batches come from the host, have no arg-max, and a read of the pinned coordinates would put a bus round trip
+    // into every DIRECT batch.
+    if (!SYS)
+        for (int j = 0; j < a.kp.D; j++)
+            if (!(xp[j] == xp[j])) q = muY = NAN;
     const double m = (a.prior.nb > 0) ? prior_mean_dev(a.prior, a.kp.D, X) : 0.0;
     const double mu = (a.prior.nb > 0) ? (m + muY - m * mu1) : muY;
-    double s2 = 1.0 + a.noise - q;
+    double s2 = 1.0 + a.noise - q;                  // (a NaN passes both clamps)
     if (s2 < a.clamp_lo) s2 = a.clamp_lo;
     else if (s2 > 10.0) s2 = 10.0;
     const double val = (a.acq == 3) ? mu : acq_value_dev(a.acq, a.erf_mode, mu, sqrt(s2), a.ymax, a.parm);

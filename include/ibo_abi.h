@@ -46,7 +46,8 @@ extern "C" {
                              * + ibo_cacq_sweep, ibo_cacq_batch, ibo_cacq_grad_batch, ibo_cacq_direct_max (EI / PI weighted by the probability of feasibility
                              * under up to eight constraint models: added within 8, nothing else changed);
                              * + ibo_kg_sweep, ibo_kg_batch, ibo_kg_direct_max, ibo_kg_stage_ms (the knowledge gradient against a reference set) and the
-                             * options "kg_chunk", "kg_timing": added within 8, nothing else changed */
+                             * options "kg_chunk", "kg_timing": added within 8, nothing else changed;
+                             * + the option "cacq_chunk" (within 8: no symbol changed) */
 
 /* status codes */
 #define IBO_OK              0
@@ -98,7 +99,7 @@ int         ibo_selftest_mfma(int device, double *max_abs_err);
  * gradients.  DIRECT's small batches and the copies are not event-timed and not in it.  bench.py reports it as gpu_kernel_s_total
  * so that a line can be related to an outside observer's busy-GPU samples. */
 int         ibo_gpu_time_ms(int device, double *ms);
-/* The fourteen option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
+/* The fifteen option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
  * Functional:  "legacy_exact" 1/0 -- acqmaxGP in libego's operation order (default) or on the MFMA sweep kernels (see acqmaxGP);
  *   "nlml_batch" B -- matrices per batched factorisation in ibo_nlml_grid (0: as many as 12 GB hold; the values do not depend on it);
  *   "pool_limit_mb" n -- the per-device free list of recycled buffers (ibo_trim);
@@ -113,7 +114,8 @@ int         ibo_gpu_time_ms(int device, double *ms);
  *   2 MFMA tile / 3 panel-split;  "dot_form" -1 auto / 0 / 1 (k* by differences or by the exponent GEMM);  "gallery_prune" 0/1/2 and
  *   "part_levels" 2..4 (see ibo_acq_sweep_incremental);  "host_pipeline" 1/0 (large host batches in overlapped chunks or in one shot);
  *   "chol_left" 1/0 (ibo_nlml_grid's left-looking order or the right-looking one: identical bits);  "kg_chunk" m (candidates per chunk of
- *   the ibo_kg_* entries, 0: by bytes -- identical bits).
+ *   the ibo_kg_* entries, 0: by bytes -- identical bits);  "cacq_chunk" m (candidates per chunk of ibo_cacq_sweep, rounded up to 256,
+ *   0: by bytes, 2^30 / (16 (ncon + 1)) -- identical bits).
  * Diagnostic:  "kg_timing" 1/0 (see ibo_kg_stage_ms).
  * Env: IBO_SWEEP_IMPL=gemv|mfma, IBO_DOT_FORM, IBO_POOL_LIMIT_MB, IBO_HOST_THREADS (the legacy symbol's host crew), IBO_DEVICE (legacy symbols),
  *   IBO_NLML_GROUPS=1..4 (sub-batches of an ibo_nlml_grid batch, each on its own stream; 2; the values do not depend on it).
@@ -375,8 +377,14 @@ int ibo_posterior_sample(ibo_gp_t *gp, int64_t M, const double *Q_host, int with
  *   mu_dev, s2_dev, acq_dev   optional DEVICE outputs (M doubles each) or NULL
  *   best_val, best_idx        HOST outputs: maximum of the (positive) acquisition
  *                and the FIRST index attaining it (numpy.argmax order, and the
- *                strict '<' of cpp/direct.cpp:124).  best_idx = -1 if every
- *                candidate is excluded.
+ *                strict '<' of cpp/direct.cpp:124).  NaN values never win; a candidate
+ *                with a NaN coordinate has NaN outputs (and so never wins either).
+ *                When nothing is admissible -- every candidate excluded or NaN --
+ *                best_idx = -1 (index_base is NOT added) and best_val = -INFINITY,
+ *                on every route and in every entry that reports an arg-max
+ *                (ibo_acq_sweep_incremental, ibo_acq_sweep_exchange, ibo_cacq_sweep,
+ *                ibo_kg_sweep).  tests/test_gpu_argmax_contract.py holds every
+ *                kernel to this rule at its reduction boundaries.
  * Blocking.  The posterior part costs N^2 + 3ND + 4N flops per candidate.
  */
 int ibo_acq_sweep(ibo_gp_t *gp, int64_t M, const double *cand_dev,
