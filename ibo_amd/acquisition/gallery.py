@@ -14,6 +14,9 @@ and `seed=` makes the default sampling reproducible (the reference is unseeded).
 thompsonGallery (an addition to the reference): the one-shot alternative by Thompson
 sampling -- each member is the arg-max of one joint posterior draw over a candidate
 set (GaussianProcess.sample_posterior), under the same distance rule.
+
+thompsonSweepGallery: the same walk over the arg-maxes of pathwise draws (pathwise.PosteriorPaths), swept once over a candidate
+array of any length -- sample_posterior stops at 16384 points.
 """
 from copy import deepcopy
 
@@ -170,4 +173,31 @@ def thompsonGallery(GP, candidates, N, seed=None, draws=None, noise=True):
         k = int(np.argmax(np.where(np.isnan(f), -np.inf, f)))
         if _separated(C[k], gallery):
             gallery.append(np.array(C[k]))
+    return gallery
+
+
+def thompsonSweepGallery(GP, candidates, N, seed=None, paths=None, n_features=2048):
+    """thompsonGallery for candidate arrays of any length: `paths` (default 8 N, at most 256) pathwise posterior draws
+    (PosteriorPaths(GP, paths, n_features, seed)) are swept ONCE over the candidates -- an (M, D) ndarray or a _lib.DeviceArray
+    already in HBM -- and their arg-maxes are walked in order exactly as thompsonGallery walks its draws: a path's first maximiser
+    (NaN never wins) joins the gallery when it is farther than MIN_SEPARATION from every member.  Returns a list of candidate rows,
+    shorter than N only when the paths run out first.  The draws are of the latent function (thompsonGallery's noise=False)."""
+    from .pathwise import PosteriorPaths, MAX_PATHS
+    paths = min(8 * int(N), MAX_PATHS) if paths is None else int(paths)
+    dev = isinstance(candidates, _lib.DeviceArray)
+    C = candidates if dev else np.atleast_2d(np.asarray(candidates, dtype=float))
+    P = PosteriorPaths(GP, n_paths=paths, n_features=n_features, seed=seed)
+    try:
+        idx = P.sweep(C)["best_idx"]
+    finally:
+        P.close()
+    gallery = []
+    for k in idx:
+        if len(gallery) >= N:
+            break
+        if k < 0:
+            continue
+        x = C.view_rows(int(k), int(k) + 1).to_host()[0] if dev else np.array(C[int(k)])
+        if _separated(x, gallery):
+            gallery.append(x)
     return gallery

@@ -47,7 +47,10 @@ extern "C" {
                              * under up to eight constraint models: added within 8, nothing else changed);
                              * + ibo_kg_sweep, ibo_kg_batch, ibo_kg_direct_max, ibo_kg_stage_ms (the knowledge gradient against a reference set) and the
                              * options "kg_chunk", "kg_timing": added within 8, nothing else changed;
-                             * + the option "cacq_chunk" (within 8: no symbol changed) */
+                             * + the option "cacq_chunk" (within 8: no symbol changed);
+                             * + ibo_paths_create, ibo_paths_destroy, ibo_paths_info, ibo_paths_coef, ibo_paths_sweep, ibo_paths_batch, ibo_paths_direct_max
+                             * (pathwise posterior draws: Thompson sampling over whole candidate arrays) and the option "paths_chunk": added within 8,
+                             * nothing else changed */
 
 /* status codes */
 #define IBO_OK              0
@@ -99,7 +102,7 @@ int         ibo_selftest_mfma(int device, double *max_abs_err);
  * gradients.  DIRECT's small batches and the copies are not event-timed and not in it.  bench.py reports it as gpu_kernel_s_total
  * so that a line can be related to an outside observer's busy-GPU samples. */
 int         ibo_gpu_time_ms(int device, double *ms);
-/* The fifteen option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
+/* The sixteen option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
  * Functional:  "legacy_exact" 1/0 -- acqmaxGP in libego's operation order (default) or on the MFMA sweep kernels (see acqmaxGP);
  *   "nlml_batch" B -- matrices per batched factorisation in ibo_nlml_grid (0: as many as 12 GB hold; the values do not depend on it);
  *   "pool_limit_mb" n -- the per-device free list of recycled buffers (ibo_trim);
@@ -115,7 +118,8 @@ int         ibo_gpu_time_ms(int device, double *ms);
  *   "part_levels" 2..4 (see ibo_acq_sweep_incremental);  "host_pipeline" 1/0 (large host batches in overlapped chunks or in one shot);
  *   "chol_left" 1/0 (ibo_nlml_grid's left-looking order or the right-looking one: identical bits);  "kg_chunk" m (candidates per chunk of
  *   the ibo_kg_* entries, 0: by bytes -- identical bits);  "cacq_chunk" m (candidates per chunk of ibo_cacq_sweep, rounded up to 256,
- *   0: by bytes, 2^30 / (16 (ncon + 1)) -- identical bits).
+ *   0: by bytes, 2^30 / (16 (ncon + 1)) -- identical bits);  "paths_chunk" m (candidates per launch of the ibo_paths_* entries, rounded up to
+ *   256, 0: 2^21 -- identical bits).
  * Diagnostic:  "kg_timing" 1/0 (see ibo_kg_stage_ms).
  * Env: IBO_SWEEP_IMPL=gemv|mfma, IBO_DOT_FORM, IBO_POOL_LIMIT_MB, IBO_HOST_THREADS (the legacy symbol's host crew), IBO_DEVICE (legacy symbols),
  *   IBO_NLML_GROUPS=1..4 (sub-batches of an ibo_nlml_grid batch, each on its own stream; 2; the values do not depend on it).
@@ -584,6 +588,57 @@ int ibo_kg_direct_max(ibo_gp_t *gp, int nref, const double *ref_host, int D, con
  * (every thread's ibo_kg_* calls wait after each chunk while it is set), the sums are per thread. */
 #define IBO_KG_STAGES 6
 int ibo_kg_stage_ms(double *ms, int reset);
+
+/* ---------------------------------------------------------------- pathwise posterior draws */
+/*
+ * A posterior draw as a FUNCTION (Matheron's rule with a random-Fourier-feature prior; Wilson et al. 2020), S of them in one object:
+ *   path_s(x) = m(x) + sum_j phi_j(x) w_sj + sum_i k(x, X_i) c_si - m(x) sum_i k(x, X_i) a1_i        (the last term only with a mean prior)
+ *   phi_j(x)  = sqrt(2 sf2 / F) cos(omega_j . x + b_j),   c_s = aY - A^-1 (Phi(X) w_s + eps_s),   A^-1 = W^T W with the handle's W
+ * so that path_s = mu + g_s with mu the posterior mean of ibo_posterior_batch (m + k*.aY - m k*.a1) and
+ * g_s(x) = phi(x).w_s - k*(x)^T A^-1 (Phi(X) w_s + eps_s).  k and k* carry the handle's k* signal variance sf2 as it is when the object
+ * is created.  For a plainly fitted model (A = R = K(X, X; sf2) with 1 + noise on the diagonal), w_s ~ N(0, I_F),
+ * eps_s ~ N(0, (1 + noise - sf2) I_N) and omega drawn from the kernel's spectral density, g_s is a draw of the latent posterior:
+ * Cov g = k(a, b) - v_a.v_b (ibo_posterior_cov's Sigma off the diagonal, sf2 - |v_a|^2 on it) up to the feature error, which falls as
+ * 1 / sqrt(F).  The arrays are the CALLER's: omega_host (F x D), phase_host (F, best reduced into [0, 2 pi)), w_host (S x F),
+ * eps_host (S x N); nothing here judges them (ibo_amd.acquisition.pathwise.spectralDraws makes them).
+ * The evaluation order is part of the definition: per (candidate, path) ONE accumulator takes the F feature terms in ascending j, then
+ * the N kernel terms in ascending i, in k-steps of four on v_mfma_f64_16x16x4_f64 (zero terms pad F and N to multiples of 32); the
+ * mean prior comes last, as m + acc - m acc1.  omega_j . x + b_j is formed in double-double and reduced by pi / 2 in fixed cost
+ * (accurate to 2e-16 for |omega . x + b| < 2^30); k(x, X_i) by differences.  A value's bits depend on the object and the candidate's
+ * coordinates and on nothing else: not on M, the candidate's place, the chunking, nor the entry (sweep, host batch, DIRECT).
+ * A NaN coordinate gives NaN in every path of that candidate, and NaN never wins.
+ * The object is a self-contained SNAPSHOT on the device (rows, kernel parameters, prior arrays, draws, coefficients, its own stream):
+ * it stays valid after ibo_gp_extend / ibo_gp_remove / a refit / ibo_gp_destroy of the model -- a draw of the posterior as it was.
+ * One object belongs to one thread at a time.
+ * Cost: creation N^2 S + 2 N F S; evaluation 2 (Fp + Np32) Sp flops per candidate on the fp64 MFMA pipe plus about 10 D + 45 vector
+ * instructions per (candidate, feature) and 3 D + 40 per (candidate, model row), generated once per tile of 64 (63 with a mean prior)
+ * paths.  Device memory: (Fp + Np32) x Sp doubles of coefficients (Fp, Np32: F, N rounded up to 32; Sp: 64 per tile of paths).
+ * Not provided: gradients with respect to x, exclusion balls, preference / augmented models (A - K is not diagonal there), the RCCL
+ * exchange.
+ * IBO_ERR_NO_DEVICE without a device (checked first); IBO_ERR_ARG for NULLs, sizes outside the limits, M < 1, every output NULL,
+ * `path` out of range or D other than the object's; IBO_ERR_STATE for an unfitted handle (or one fitted from libego's inverse).
+ */
+typedef struct ibo_paths ibo_paths_t;
+#define IBO_PATHS_MAX_PATHS    256
+#define IBO_PATHS_MAX_FEATURES 16384
+int ibo_paths_create(ibo_gp_t *gp, int nfeat, const double *omega_host /* F x D */, const double *phase_host /* F */,
+                     int npaths, const double *w_host /* S x F */, const double *eps_host /* S x N */, ibo_paths_t **out);
+int ibo_paths_destroy(ibo_paths_t *p);
+/* any of the outputs may be NULL */
+int ibo_paths_info(ibo_paths_t *p, int *npaths, int *nfeat, int *N, int *D, int *device);
+/* the coefficients as the device holds them, S x (F + N): w_s, then c_s */
+int ibo_paths_coef(ibo_paths_t *p, double *coef_host);
+/* M candidates on the device (cand_dev, M x D): values_dev (device, S x M path-major, optional) receives the values; per path
+ * best_val / best_idx (host, S each, optional) the maximum and the first index that attains it, index_base added -- or -inf and -1
+ * (no base added) when no value of that path is a number. */
+int ibo_paths_sweep(ibo_paths_t *p, int64_t M, const double *cand_dev, int64_t index_base,
+                    double *values_dev, double *best_val, int64_t *best_idx);
+/* M host points: values_host (S x M path-major) */
+int ibo_paths_batch(ibo_paths_t *p, int64_t M, const double *Q_host, double *values_host);
+/* ibo_direct_max on ONE path: the same DIRECT, options and batched schedule; every batch evaluated as ibo_paths_batch evaluates that
+ * path.  opt = the maximum, optx[D] its location, nsamples optional (not all three NULL). */
+int ibo_paths_direct_max(ibo_paths_t *p, int path, int D, const double *lb, const double *ub, int maxiter, int maxtime,
+                         int maxsample, int compat, double *opt, double *optx, int64_t *nsamples);
 
 /* DIRECT minimisation of a HOST callback with the reference's semantics
  * (cpp/direct.cpp:329; what ego.utils.optimize.cdirect wraps), plus the sample
