@@ -14,6 +14,8 @@ plus the batched entry point the GPU makes worthwhile:
     sweep(model, candidates, acq='ei', ...) -> dict(best_val, best_idx, [mu, s2, acq])
 
 and the knowledge gradient against a reference set (knowledge.py): KnowledgeGradient, sweepKG, maximizeKG, referenceSet.
+The value of a batch -- Monte-Carlo parallel EI with pending points and a greedy batch builder (batch.py): baseSamples, ParallelEI,
+sweepQEI, maximizeQEI, jointQEI, proposeBatch.
 Posterior draws as functions -- Thompson sampling over whole candidate arrays (pathwise.py): PosteriorPaths, spectralDraws.
 
 The default maximize* path is the reference's cdirectGP -> acqmaxGP -> DIRECT
@@ -347,4 +349,5 @@ def sweep(model, candidates, acq='ei', xi=0.01, delta=0.1, scale=0.2, parm=None,
 
 
 from .knowledge import KnowledgeGradient, sweepKG, maximizeKG, referenceSet          # noqa: E402,F401
+from .batch import baseSamples, ParallelEI, sweepQEI, maximizeQEI, jointQEI, proposeBatch      # noqa: E402,F401
 from .pathwise import PosteriorPaths, spectralDraws                                  # noqa: E402,F401

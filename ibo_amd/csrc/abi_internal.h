@@ -7,7 +7,8 @@
 //   abi_cacq.hip    the constrained acquisition (ibo_cacq_*)
 //   abi_kg.hip      the knowledge gradient (ibo_kg_*)
 //   abi_paths.hip   pathwise posterior draws (ibo_paths_*)
-//                   (these five are the evaluation units: what they share among themselves is in abi_eval.h)
+//   abi_qei.hip     the Monte-Carlo parallel expected improvement (ibo_qei_*)
+//                   (these six are the evaluation units: what they share among themselves is in abi_eval.h)
 //   abi_nlml.hip    marginal-likelihood grid and gradient, ibo_trim
 //   abi_legacy.hip  libego's symbols (acqmaxGP, direct, logCDFs) and ibo_direct_host
 // There is no CPU fallback anywhere behind this header: without a gfx950 device every compute entry point returns IBO_ERR_NO_DEVICE.
@@ -50,6 +51,7 @@ extern std::atomic<int> g_super_min_nb;        // ibo_set_option("super_min_nb",
 extern std::atomic<int> g_host_pipeline, g_fused2_min_nb, g_gallery_prune, g_nlml_batch, g_chol_left, g_dot_override, g_legacy_exact, g_force_path, g_nlml_groups;
 extern std::atomic<int> g_cacq_chunk;                // abi_cacq.hip: candidates per chunk of ibo_cacq_sweep (0: by bytes)
 extern std::atomic<int> g_kg_chunk, g_kg_timing;     // abi_kg.hip: candidates per chunk (0: by bytes); per-stage HIP events
+extern std::atomic<int> g_qei_chunk, g_qei_timing;   // abi_qei.hip: candidates per chunk (0: by bytes); per-stage HIP events
 extern std::atomic<int> g_paths_chunk;               // abi_paths.hip: candidates per launch of the ibo_paths_* entries (0: 2^21)
 extern std::mutex g_dev_mu[16];             // serialises the per-device workspaces of ibo_nlml_grid / ibo_nlml_grad / ibo_trim
 extern std::atomic<size_t> g_pool_limit;

@@ -27,7 +27,8 @@ struct KgRowsArgs {
 int launch_kg_rows(const KgRowsArgs &a, hipStream_t s);
 
 // B[x][a] for x < m, a < n from the 64 x 64 tiles of VtX VtA^T (VtX: mp x >= K, VtA: np x >= K, mp, np multiples of 64, K of 32);
-// sigma_x = sqrt(s2[x]).  B: mp x ldb, ldb >= np; entries beyond (m, n) are written as 0.
+// sigma_x = sqrt(s2[x]).  B: mp x ldb, ldb >= np; entries beyond (m, n) are written as 0.  unscaled != 0: B[x][a] = k(a, x) - v_a.v_x, the
+// covariance itself (s2 is not read) -- the same tile body and the same difference, without the division.
 struct KgCrossArgs {
     KParams kp;
     const double *VtX; size_t ldx; int m, mp;
@@ -36,6 +37,7 @@ struct KgCrossArgs {
     const double *X, *A;                // m x D, n x D
     const double *s2;                   // m
     double *B; size_t ldb;
+    int unscaled;
 };
 int launch_kg_cross(const KgCrossArgs &a, hipStream_t s);
 

@@ -2,7 +2,7 @@
 //
 //   kg_rows_kernel      one wavefront per row of Kt / Vt: k*.aY, k*.a1, |v|^2 -> mu, the clipped s2
 //   kg_cross_kernel     B = (K(X, A) - VtX VtA^T) / sigma_x on v_mfma_f64_16x16x4_f64 through cv_tile<false> (cov_dev.h): 64 x 64 tiles of
-//                       (candidates x reference points), stored candidate-major
+//                       (candidates x reference points), stored candidate-major; <false>: without the division (qei.hip's covariances)
 //   kg_epigraph_kernel  the expected maximum of n (+ 1) lines per candidate: one wavefront per candidate, its slopes in LDS, the reference
 //                       means in LDS once per workgroup; lane l owns the lines l, l + 64, .. and scans all the others (n^2 pair steps
 //                       with one fp64 division each -- the cost of the whole acquisition from a few hundred lines on)
@@ -48,6 +48,7 @@ __global__ __launch_bounds__(256) void kg_rows_kernel(KgRowsArgs a)
 }
 
 // one 64 x 64 tile per workgroup: blockIdx.y the candidates' tile, blockIdx.x the reference points'
+template <bool SCALED>
 __global__ void __launch_bounds__(256) kg_cross_kernel(KgCrossArgs a)
 {
     __shared__ double As[64 * CV_LD], Bs[64 * CV_LD];
@@ -69,7 +70,8 @@ __global__ void __launch_bounds__(256) kg_cross_kernel(KgCrossArgs a)
                 double v = 0.0;
                 if (x < a.m && c < a.n) {
                     const double k = cov_from_z_rt(a.kp.family, wsqdist_dev(a.kp.w, a.A + (size_t)c * D, a.X + (size_t)x * D, D), a.kp.sf2);
-                    v = (k - acc[i][j][e]) / sqrt(a.s2[x]);
+                    v = k - acc[i][j][e];
+                    if (SCALED) v = v / sqrt(a.s2[x]);
                 }
                 a.B[(size_t)x * a.ldb + c] = v;
             }
@@ -149,7 +151,8 @@ int launch_kg_cross(const KgCrossArgs &a, hipStream_t s)
 {
     if (a.m < 1 || a.m > a.mp || a.n < 1 || a.n > a.np || (a.mp & 63) || (a.np & 63) || (a.K & (CV_KB - 1)) || a.ldb < (size_t)a.np)
         return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(kg_cross_kernel, dim3(a.np / 64, a.mp / 64), dim3(256), 0, s, a);
+    if (a.unscaled) hipLaunchKernelGGL(kg_cross_kernel<false>, dim3(a.np / 64, a.mp / 64), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(kg_cross_kernel<true>, dim3(a.np / 64, a.mp / 64), dim3(256), 0, s, a);
     return (int)hipGetLastError();
 }
 

@@ -50,7 +50,9 @@ extern "C" {
                              * + the option "cacq_chunk" (within 8: no symbol changed);
                              * + ibo_paths_create, ibo_paths_destroy, ibo_paths_info, ibo_paths_coef, ibo_paths_sweep, ibo_paths_batch, ibo_paths_direct_max
                              * (pathwise posterior draws: Thompson sampling over whole candidate arrays) and the option "paths_chunk": added within 8,
-                             * nothing else changed */
+                             * nothing else changed;
+                             * + ibo_qei_sweep, ibo_qei_batch, ibo_qei_direct_max, ibo_qei_stage_ms (Monte-Carlo parallel expected improvement with pending
+                             * points) and the options "qei_chunk", "qei_timing": added within 8, nothing else changed */
 
 /* status codes */
 #define IBO_OK              0
@@ -102,7 +104,7 @@ int         ibo_selftest_mfma(int device, double *max_abs_err);
  * gradients.  DIRECT's small batches and the copies are not event-timed and not in it.  bench.py reports it as gpu_kernel_s_total
  * so that a line can be related to an outside observer's busy-GPU samples. */
 int         ibo_gpu_time_ms(int device, double *ms);
-/* The sixteen option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
+/* The eighteen option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
  * Functional:  "legacy_exact" 1/0 -- acqmaxGP in libego's operation order (default) or on the MFMA sweep kernels (see acqmaxGP);
  *   "nlml_batch" B -- matrices per batched factorisation in ibo_nlml_grid (0: as many as 12 GB hold; the values do not depend on it);
  *   "pool_limit_mb" n -- the per-device free list of recycled buffers (ibo_trim);
@@ -119,8 +121,9 @@ int         ibo_gpu_time_ms(int device, double *ms);
  *   "chol_left" 1/0 (ibo_nlml_grid's left-looking order or the right-looking one: identical bits);  "kg_chunk" m (candidates per chunk of
  *   the ibo_kg_* entries, 0: by bytes -- identical bits);  "cacq_chunk" m (candidates per chunk of ibo_cacq_sweep, rounded up to 256,
  *   0: by bytes, 2^30 / (16 (ncon + 1)) -- identical bits);  "paths_chunk" m (candidates per launch of the ibo_paths_* entries, rounded up to
- *   256, 0: 2^21 -- identical bits).
- * Diagnostic:  "kg_timing" 1/0 (see ibo_kg_stage_ms).
+ *   256, 0: 2^21 -- identical bits);  "qei_chunk" m (candidates per chunk of the ibo_qei_* entries, rounded up to 256, 0: by bytes --
+ *   identical bits).
+ * Diagnostic:  "kg_timing" 1/0 (see ibo_kg_stage_ms);  "qei_timing" 1/0 (see ibo_qei_stage_ms).
  * Env: IBO_SWEEP_IMPL=gemv|mfma, IBO_DOT_FORM, IBO_POOL_LIMIT_MB, IBO_HOST_THREADS (the legacy symbol's host crew), IBO_DEVICE (legacy symbols),
  *   IBO_NLML_GROUPS=1..4 (sub-batches of an ibo_nlml_grid batch, each on its own stream; 2; the values do not depend on it).
  * Threading (the reference's library keeps its whole model in process-wide statics, cpp/optimizeGP.cpp:36-55,240-259, and is not
@@ -588,6 +591,75 @@ int ibo_kg_direct_max(ibo_gp_t *gp, int nref, const double *ref_host, int D, con
  * (every thread's ibo_kg_* calls wait after each chunk while it is set), the sums are per thread. */
 #define IBO_KG_STAGES 6
 int ibo_kg_stage_ms(double *ms, int reset);
+
+/* ---------------------------------------------------------------- parallel expected improvement (Monte-Carlo q-EI) */
+/*
+ * The expected improvement of a candidate x evaluated TOGETHER with a pending set P = {p_1 .. p_p} (pend_host, npend x D row-major, host
+ * memory, 0 <= npend <= IBO_QEI_MAX_PENDING; NULL allowed when npend = 0) over the joint predictive distribution,
+ *   qEI(x | P) = E[max(max(y(x), max_j y(p_j)) - t, 0)],   t = ymax + xi (ymax NaN: the model's largest observation, as ibo_acq_batch),
+ * estimated with the CALLER's base samples Z_host (nsamp x (npend + 1) row-major, 1 <= nsamp <= IBO_QEI_MAX_SAMPLES; column j belongs to
+ * pending point j, the last column to the candidate).  The library draws nothing.
+ * Conventions of ibo_posterior_cov with with_noise = 1: k and k* with the handle's k* signal variance, v = W k*.  Means are the row
+ * kernel's of the knowledge gradient, m + k*.aY - m k*.a1 as dot products over the k* rows (NOT ibo_posterior_batch's launches).
+ * The pending state, once per call:
+ *   mu_P     the means at the pending points
+ *   S_PP     S_ab = k(p_a, p_b) - v_a.v_b (the entry a > b as the device forms it, mirrored), S_aa = ((1 + noise) - |v_a|^2) + jitter
+ *   L_P      the Cholesky factor of S_PP, on the host in plain double, row by row: L_ji = (S_ji - sum_{k<i} L_jk L_ik) / L_ii for i < j, then
+ *            L_jj = sqrt(S_jj - sum_{k<j} L_jk^2); every sum starts from the S entry and takes its terms in ascending k, each by one fused
+ *            multiply-add acc = fma(-a, b, acc).  A pivot that is not a positive finite number returns IBO_ERR_NOT_PD with the 1-based
+ *            pivot in *info (0 otherwise; info may be NULL).
+ *   g_s      max_j y_sj,  y_sj = mu_P,j + sum_{i<=j} L_ji z_si taken as y = mu_P,j; y = fma(L_ji, z_si, y) in ascending i; -inf when npend = 0
+ *   base     (1/S) sum_s max(g_s - t, 0), the value of the pending set alone (0 when npend = 0), summed in the order given below
+ * Per candidate x:
+ *   mu_x, s2_x = clip(1 + noise - |v_x|^2, clamp_lo, 10)              (the knowledge gradient's row kernel)
+ *   c_j      k(p_j, x) - v_pj.v_x: the tile product of the knowledge gradient's cross kernel WITHOUT its division by sigma_x
+ *   l        L_P^-1 c by forward substitution: l_j = (c_j - sum_{i<j} L_ji l_i) / L_jj, acc = c_j; acc = fma(-L_ji, l_i, acc) in ascending i
+ *   d        r = s2_x; r = fma(-l_j, l_j, r) in ascending j;  d = sqrt(r) if r > 0, else 0
+ *   f_s      f = mu_x; f = fma(l_j, z_sj, f) in ascending j; f = fma(d, z_sp, f)
+ *   qEI      (1/S) sum_s max(max(f_s, g_s) - t, 0): the term of sample s is h - t with h = f_s if f_s > g_s, else g_s, and is added only if
+ *            it is > 0.  A wavefront sums one candidate: lane l the samples l, l + 64, .. in ascending order, then over the lanes in a fixed
+ *            butterfly (offsets 32, 16, .. 1), then one division by S.  base is summed the same way, which is why
+ *            qEI(x | P) >= base holds EXACTLY for every candidate: termwise max(f, g) >= g, and every rounding on the way is monotone.
+ * (l, d) is the last row of the Cholesky factor of the bordered (p + 1) x (p + 1) joint covariance, applied to the same z; for npend = 0
+ * and S -> infinity the value is ibo_acq_batch's EI with libm erf.  The evaluation order above is part of the definition.  A candidate's
+ * bits depend on the model, P, Z, t, clamp_lo and jitter and on nothing else: not on M, on its place in the array, on the chunking, nor on
+ * the entry (sweep, host batch, DIRECT) it came through.  A NaN candidate coordinate gives a NaN value, which never wins the arg-max.
+ * Cost: N^2 (npend + M) flops for V = W K* and 2 N 64 M for the cross-covariance (the pending set fills one 64-wide tile column) on the
+ * fp64 MFMA pipe; nsamp (npend + 1) M fused multiply-adds on the vector ALU in the finish.
+ * Device scratch, from the pool and returned before the call returns: the pending state (3 x 64 Npad doubles while it is built, 64 Npad
+ * after, and (npend + 2) nsamp' doubles of samples, nsamp' = nsamp rounded up to 256) and per chunk of candidates K* and V^T (mc Npad
+ * doubles each) and the covariances (64 mc), each at most 256 MiB or 256 candidates where that alone is more, mc <= 65280
+ * (ibo_set_option("qei_chunk", m) sets mc, rounded up to 256).
+ * IBO_ERR_NO_DEVICE without a device (checked first); IBO_ERR_ARG for a NULL gp, Z_host, candidate array (or pend_host with npend > 0),
+ * npend or nsamp outside their limits, M < 1, every output NULL, a non-finite pending coordinate, base sample, xi or jitter, jitter < 0;
+ * IBO_ERR_STATE before a fit (checked before the values are looked at).  There are no exclusion balls and no gradients with respect to x.
+ */
+#define IBO_QEI_MAX_PENDING 15
+#define IBO_QEI_MAX_SAMPLES 4096
+
+/* M candidates on the device (cand_dev, M x D): qei_dev (device, M, optional) receives the values; base (optional) the pending set's own
+ * value; best_val / best_idx the maximum and the first index that attains it, index_base added (-inf and -1 if no value is a number). */
+int ibo_qei_sweep(ibo_gp_t *gp, int npend, const double *pend_host, int nsamp, const double *Z_host, double ymax, double xi,
+                  double clamp_lo, double jitter, int64_t M, const double *cand_dev, int64_t index_base, double *qei_dev,
+                  double *base, double *best_val, int64_t *best_idx, int *info);
+
+/* M host points: qei_host (M) and, all optional (but not all NULL), what the values were made of: base, mu_pend_host (npend), S_pend_host
+ * (npend x npend row-major, jitter included), mu_host and s2_host (M, s2 clipped), c_host (M x npend row-major, c_host[x][j] = c_j(q_x)). */
+int ibo_qei_batch(ibo_gp_t *gp, int npend, const double *pend_host, int nsamp, const double *Z_host, double ymax, double xi,
+                  double clamp_lo, double jitter, int64_t M, const double *Q_host, double *qei_host, double *base,
+                  double *mu_pend_host, double *S_pend_host, double *mu_host, double *s2_host, double *c_host, int *info);
+
+/* ibo_direct_max on qEI(. | P): the same DIRECT, options and batched schedule; the pending state and the samples are built once and stay
+ * on the device across the batches.  opt = the maximum, optx[D] its location, nsamples optional (not all three NULL).  IBO_ERR_ARG also
+ * for NULL bounds or D other than the model's. */
+int ibo_qei_direct_max(ibo_gp_t *gp, int npend, const double *pend_host, int nsamp, const double *Z_host, double ymax, double xi,
+                       double clamp_lo, double jitter, int D, const double *lb, const double *ub, int maxiter, int maxtime,
+                       int maxsample, int compat, double *opt, double *optx, int64_t *nsamples, int *info);
+
+/* ibo_kg_stage_ms for the ibo_qei_* entries, under ibo_set_option("qei_timing", 1): the pending state (its device part), K*,
+ * V^T = K* W^T, the row kernel, the cross-covariance, the Monte-Carlo finish. */
+#define IBO_QEI_STAGES 6
+int ibo_qei_stage_ms(double *ms, int reset);
 
 /* ---------------------------------------------------------------- pathwise posterior draws */
 /*
