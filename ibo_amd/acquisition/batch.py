@@ -27,27 +27,17 @@ GaussianProcess -- but not while an augmented factor is in force (addObservation
 model's D are refused (ValueError); a 1-D sequence is one point.
 """
 import ctypes
+import functools
 
 import numpy as np
 
 from .. import _lib
+from . import _args
 
 MAX_PENDING = 15        # IBO_QEI_MAX_PENDING
 MAX_SAMPLES = 4096      # IBO_QEI_MAX_SAMPLES
-
-
-def _points(GP, P, what):
-    """an (M, D) float64 matrix of points of the model's dimension; a 1-D sequence is ONE point (D coordinates), as everywhere else"""
-    if len(GP.X) == 0:
-        raise ValueError("model has no data")
-    if getattr(GP, "_augdev", None) is not None:
-        raise ValueError("the parallel expected improvement is not defined on an augmented factor (addObservationPoint): its "
-                         "covariances would come from one factor and its means from another")
-    P = _lib.f64(np.atleast_2d(np.asarray(P, dtype=float)))
-    D = np.asarray(GP.X).shape[1]
-    if P.ndim != 2 or P.shape[1] != D or len(P) < 1:
-        raise ValueError("%s must be (M, %d) points, got shape %s" % (what, D, P.shape))
-    return P
+_NOUN = "parallel expected improvement"
+_points = functools.partial(_args._points, noun=_NOUN)
 
 
 def baseSamples(q, n_samples=512, seed=0, antithetic=True):
@@ -144,13 +134,7 @@ def sweepQEI(GP, candidates, pending=None, n_samples=512, seed=0, xi=0.0, jitter
     _lib.DeviceArray already in HBM.  Returns (best_val, best_idx) or, with values=True, (best_val, best_idx, values (M,)); the first
     maximiser wins ties, index_base is added to the index."""
     acq = ParallelEI(GP, pending, n_samples, seed, xi, jitter, Z)
-    D = acq.pending.shape[1]
-    if isinstance(candidates, _lib.DeviceArray):
-        cand = candidates
-    else:
-        cand = _lib.DeviceArray.from_host(_points(GP, candidates, "candidates"), GP._dev.device)
-    if len(cand.shape) != 2 or cand.shape[1] != D:
-        raise ValueError("candidates must be (M, %d) points, got shape %s" % (D, cand.shape))
+    cand, _ = _args._candidates(GP, candidates, acq.pending.shape[1], _NOUN)
     M = cand.shape[0]
     GP._push_prior()
     out = _lib.DeviceArray((M,), GP._dev.device) if values else None
@@ -165,10 +149,7 @@ def maximizeQEI(GP, bounds, pending=None, n_samples=512, seed=0, xi=0.0, jitter=
     """Maximise qEI(. | pending) over the box `bounds` with DIRECT on the GPU objective (ibo_qei_direct_max) -> (opt, optx).
     opt is ParallelEI(GP, pending, ...).f(optx), bit for bit."""
     acq = ParallelEI(GP, pending, n_samples, seed, xi, jitter, Z)
-    lb = _lib.f64([b[0] for b in bounds]); ub = _lib.f64([b[1] for b in bounds])
-    D = len(lb)
-    if D != acq.pending.shape[1]:
-        raise ValueError("bounds have %d dimensions, the model has %d" % (D, acq.pending.shape[1]))
+    lb, ub, D = _args._bounds(bounds, acq.pending.shape[1])
     GP._push_prior()
     opt = ctypes.c_double(); optx = np.empty(D); ns = ctypes.c_int64(); info = ctypes.c_int()
     _lib.check(_lib.lib.ibo_qei_direct_max(*(acq._head() + (D, _lib.dp(lb), _lib.dp(ub), int(maxiter), int(maxtime), int(maxsample),
@@ -203,13 +184,7 @@ def proposeBatch(GP, bounds=None, candidates=None, q=4, pending=None, n_samples=
     Z = np.asarray(Z, dtype=float)
     if Z.ndim != 2 or Z.shape[1] < w:
         raise ValueError("Z must be (S, >= %d), got shape %s" % (w, Z.shape))
-    cand = host = None
-    if candidates is not None:
-        if isinstance(candidates, _lib.DeviceArray):
-            cand = candidates
-        else:
-            host = _points(GP, candidates, "candidates")
-            cand = _lib.DeviceArray.from_host(host, GP._dev.device)
+    cand, host = (None, None) if candidates is None else _args._candidates(GP, candidates, P.shape[1], _NOUN)
     Xq = []
     value = 0.0
     for _ in range(q):

@@ -23,27 +23,17 @@ GaussianProcess -- but not while an augmented factor is in force (addObservation
 model's D are refused (ValueError); a 1-D sequence is one point.
 """
 import ctypes
+import functools
 
 import numpy as np
 
 from .. import _lib
 from ..utils.latinhypercube import lhcSample
+from . import _args
 
 MAX_REF = 1024          # IBO_KG_MAX_REF
-
-
-def _points(GP, P, what):
-    """an (M, D) float64 matrix of points of the model's dimension; a 1-D sequence is ONE point (D coordinates), as everywhere else"""
-    if len(GP.X) == 0:
-        raise ValueError("model has no data")
-    if getattr(GP, "_augdev", None) is not None:
-        raise ValueError("the knowledge gradient is not defined on an augmented factor (addObservationPoint): its covariances would "
-                         "come from one factor and its means from another")
-    P = _lib.f64(np.atleast_2d(np.asarray(P, dtype=float)))
-    D = np.asarray(GP.X).shape[1]
-    if P.ndim != 2 or P.shape[1] != D or len(P) < 1:
-        raise ValueError("%s must be (M, %d) points, got shape %s" % (what, D, P.shape))
-    return P
+_NOUN = "knowledge gradient"
+_points = functools.partial(_args._points, noun=_NOUN)
 
 
 def _ref(GP, ref_points):
@@ -104,12 +94,7 @@ def sweepKG(GP, candidates, ref_points, with_self=True, values=False, index_base
     or a _lib.DeviceArray already in HBM.  Returns (best_val, best_idx) or, with values=True, (best_val, best_idx, values (M,));
     the first maximiser wins ties, index_base is added to the index."""
     A = _ref(GP, ref_points)
-    if isinstance(candidates, _lib.DeviceArray):
-        cand = candidates
-    else:
-        cand = _lib.DeviceArray.from_host(_points(GP, candidates, "candidates"), GP._dev.device)
-    if len(cand.shape) != 2 or cand.shape[1] != A.shape[1]:
-        raise ValueError("candidates must be (M, %d) points, got shape %s" % (A.shape[1], cand.shape))
+    cand, _ = _args._candidates(GP, candidates, A.shape[1], _NOUN)
     M = cand.shape[0]
     GP._push_prior()
     out = _lib.DeviceArray((M,), GP._dev.device) if values else None
@@ -124,10 +109,7 @@ def maximizeKG(GP, bounds, ref_points=None, n_ref=256, seed=0, maxiter=50, maxti
     """Maximise the knowledge gradient over the box `bounds` with DIRECT on the GPU objective (ibo_kg_direct_max) -> (opt, optx).
     ref_points=None: referenceSet(GP, bounds, n_ref, seed).  opt is KnowledgeGradient(GP, ref_points, with_self).f(optx), bit for bit."""
     A = _ref(GP, referenceSet(GP, bounds, n_ref, seed) if ref_points is None else ref_points)
-    lb = _lib.f64([b[0] for b in bounds]); ub = _lib.f64([b[1] for b in bounds])
-    D = len(lb)
-    if D != A.shape[1]:
-        raise ValueError("bounds have %d dimensions, the model has %d" % (D, A.shape[1]))
+    lb, ub, D = _args._bounds(bounds, A.shape[1])
     GP._push_prior()
     opt = ctypes.c_double(); optx = np.empty(D); ns = ctypes.c_int64()
     _lib.check(_lib.lib.ibo_kg_direct_max(GP._handle(), len(A), _lib.dp(A), D, _lib.dp(lb), _lib.dp(ub), int(bool(with_self)),

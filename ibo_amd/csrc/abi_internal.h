@@ -8,7 +8,8 @@
 //   abi_kg.hip      the knowledge gradient (ibo_kg_*)
 //   abi_paths.hip   pathwise posterior draws (ibo_paths_*)
 //   abi_qei.hip     the Monte-Carlo parallel expected improvement (ibo_qei_*)
-//                   (these six are the evaluation units: what they share among themselves is in abi_eval.h)
+//   abi_rows.hip    the row pipeline of the two above: chunk, scratch, stage clock, host batch, device sweep (abi_rows.h)
+//                   (these seven are the evaluation units: what they share among themselves is in abi_eval.h)
 //   abi_nlml.hip    marginal-likelihood grid and gradient, ibo_trim
 //   abi_legacy.hip  libego's symbols (acqmaxGP, direct, logCDFs) and ibo_direct_host
 // There is no CPU fallback anywhere behind this header: without a gfx950 device every compute entry point returns IBO_ERR_NO_DEVICE.

@@ -2,16 +2,15 @@
 // (kernels: qei.hip, kg.hip, cov.hip).
 //
 // ONE route for every entry: the pending state (the pending points, their V^T rows, mu_P, L_P on the host, the transposed samples with g
-// beside them) is built once per call and stays on the device; candidates go through qei_chunk in chunks of a multiple of 256 -- K* and V^T
-// by cov.hip's launchers, kg.hip's row kernel, kg.hip's cross kernel without its division, the finish.  None of these lets a row's result
-// depend on the rows beside it, so a candidate's bits are the same from a sweep, a host batch or a DIRECT batch, whatever the chunk.
+// beside them) is built once per call and stays on the device; candidates go through the row pipeline (abi_rows.h) in chunks of a multiple
+// of 256 -- K* and V^T by cov.hip's launchers, kg.hip's row kernel, and this unit's tail: kg.hip's cross kernel without its division, the
+// finish.  None of these lets a row's result depend on the rows beside it, so a candidate's bits are the same from a sweep, a host batch or
+// a DIRECT batch, whatever the chunk.
 //
 // Scratch, all from the pool and handed back on every exit path: the pending state (3 x 64 Npad doubles while it is built, 64 Npad after,
 // and (p + 2) Sp doubles of samples); per chunk K* and V^T (mc Npad doubles each) and the covariances (mc x 64), each at most 256 MiB -- or
 // 256 candidates where that alone is more -- and never more than 65280 candidates.
-#include "abi_eval.h"
-#include "cov.h"
-#include "kg.h"
+#include "abi_rows.h"
 #include "qei.h"
 
 std::atomic<int> g_qei_chunk{0};      // ibo_set_option("qei_chunk", m): candidates per chunk (rounded up to 256); 0: by bytes
@@ -20,32 +19,14 @@ static thread_local double t_qei_ms[IBO_QEI_STAGES];
 
 namespace {
 
-enum { ST_PEND = 0, ST_KSTAR, ST_TRI, ST_ROWS, ST_CROSS, ST_FINISH };
-
 struct QeiState {
-    ibo_gp *g = nullptr;
     int p = 0, S = 0, Sp = 0;
-    double t = 0.0, clamp_lo = 0.0, base = 0.0;
-    int64_t mc = 0;                                  // candidates per chunk
+    double t = 0.0, base = 0.0;
     std::vector<double> muP_host, S_host, zg_host;
     double L[QEI_MAX_P * (QEI_MAX_P + 1) / 2];
     ScopedBuf<double> P, vtP, ZG;                    // the pending state
-    ScopedBuf<double> cand, kt, vt, mu, s2, C, val;  // one chunk
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool timing = false;
-    ~QeiState() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    RowPipeline rows;                                // the chunks: its cross block holds the covariances C, 64 wide (none when p = 0)
 };
-
-int qei_mark(QeiState &st, int k) { if (st.timing) HIP_TRY(hipEventRecord(st.ev[k], st.g->stream)); return IBO_OK; }
-// after a synchronisation: the time between marks k0 and k1 goes to stage `stage`
-int qei_account(QeiState &st, int k0, int k1, int stage)
-{
-    if (!st.timing) return IBO_OK;
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, st.ev[k0], st.ev[k1]));
-    t_qei_ms[stage] += ms;
-    return IBO_OK;
-}
 
 inline bool is_fin(double v) { return fabs(v) < HUGE_VAL; }
 
@@ -69,19 +50,9 @@ int qei_check(ibo_gp *g, int npend, const double *pend_host, int nsamp, const do
     return IBO_OK;
 }
 
-KgRowsArgs rows_args(const ibo_gp *g, const double *Kt, const double *Vt, const double *Q, int m, double clamp_lo)
-{
-    KgRowsArgs r;
-    memset(&r, 0, sizeof(r));
-    r.Kt = Kt; r.ldk = (size_t)g->Npad; r.Vt = Vt; r.ldv = (size_t)g->Npad;
-    r.alphaY = g->alphaY.p; r.alpha1 = g->alpha1.p; r.Q = Q; r.D = g->D; r.prior = prior_of(g);
-    r.N = g->N; r.K = g->N; r.m = m; r.noise = g->noise; r.clamp_lo = clamp_lo;
-    return r;
-}
-
 KgCrossArgs cross_args(const QeiState &st, const double *VtX, int m, int mp, const double *X, double *B)
 {
-    const ibo_gp *g = st.g;
+    const ibo_gp *g = st.rows.g;
     KgCrossArgs c;
     memset(&c, 0, sizeof(c));
     c.kp = g->kp; c.VtX = VtX; c.ldx = (size_t)g->Npad; c.m = m; c.mp = mp; c.VtA = st.vtP.p; c.lda = (size_t)g->Npad; c.n = st.p; c.np = IBO_COV_TILE;
@@ -104,20 +75,33 @@ double lane_order_mean(const std::vector<double> &term, int S)
     return v[0] / (double)S;
 }
 
+// The pipeline's tail: the covariances with the pending points (if there are any), then the finish.
+int qei_tail(QeiState &st, int m, int mp, const double *cand, double *out)
+{
+    RowPipeline &r = st.rows;
+    hipStream_t s = r.g->stream;
+    if (st.p > 0) KERNEL_TRY(launch_kg_cross(cross_args(st, r.vt.p, m, mp, cand, r.cross.p), s));
+    IBO_TRY(r.clock.mark(4));
+    QeiFinishArgs f;
+    memset(&f, 0, sizeof(f));
+    f.m = m; f.p = st.p; f.S = st.S; f.Sp = st.Sp; f.t = st.t; f.ZG = st.ZG.p; f.mu = r.mu.p; f.s2 = r.s2.p; f.C = r.cross.p; f.ldc = (size_t)IBO_COV_TILE;
+    f.qei = out;
+    memcpy(f.L, st.L, sizeof(f.L));
+    KERNEL_TRY(launch_qei_finish(f, s));
+    return r.clock.mark(5);
+}
+
 // The pending state; the device is idle when this returns.
 int qei_begin(ibo_gp *g, QeiState &st, int npend, const double *pend_host, int nsamp, const double *Z_host, double ymax, double xi,
               double clamp_lo, double jitter, int *info)
 {
     const int Np = g->Npad, D = g->D, p = npend, T = IBO_COV_TILE;
     hipStream_t s = g->stream;
-    st.g = g; st.p = p; st.S = nsamp; st.Sp = round_up(nsamp, QEI_SB); st.clamp_lo = clamp_lo;
+    StageClock &clock = st.rows.clock;
+    st.p = p; st.S = nsamp; st.Sp = round_up(nsamp, QEI_SB);
     st.t = ((ymax == ymax) ? ymax : g->maxY) + xi;
-    st.timing = g_qei_timing != 0;
-    if (st.timing)
-        for (hipEvent_t &e : st.ev) HIP_TRY(hipEventCreate(&e));
-    const size_t lim = (size_t)256 << 20;
-    int64_t mc = g_qei_chunk > 0 ? (int64_t)g_qei_chunk : (int64_t)std::min(lim / ((size_t)Np * sizeof(double)), lim / ((size_t)T * sizeof(double)));
-    st.mc = std::min<int64_t>(std::max<int64_t>((mc + (g_qei_chunk > 0 ? 255 : 0)) / 256 * 256, 256), 65280);      // (cov_kstar_kernel: one grid row per point, at most 65535)
+    IBO_TRY(st.rows.begin(g, clamp_lo, g_qei_chunk, (size_t)T, p > 0 ? (size_t)T : 0, false, g_qei_timing != 0, t_qei_ms));
+    st.rows.tail = [&st](int m, int mp, const double *cand, double *out) { return qei_tail(st, m, mp, cand, out); };
     st.muP_host.assign((size_t)p, 0.0); st.S_host.assign((size_t)p * p, 0.0);
     memset(st.L, 0, sizeof(st.L));
     IBO_TRY(st.ZG.ensure((size_t)(p + 2) * st.Sp));
@@ -126,7 +110,7 @@ int qei_begin(ibo_gp *g, QeiState &st, int npend, const double *pend_host, int n
         std::vector<double> q_host((size_t)p), B_host((size_t)p * T);
         IBO_TRY(st.P.ensure((size_t)p * D)); IBO_TRY(st.vtP.ensure((size_t)T * Np)); IBO_TRY(ktP.ensure((size_t)T * Np));
         IBO_TRY(muP.ensure((size_t)T)); IBO_TRY(qP.ensure((size_t)T)); IBO_TRY(Bpp.ensure((size_t)T * T));
-        IBO_TRY(qei_mark(st, 0));
+        IBO_TRY(clock.mark(0));
         HIP_TRY(hipMemcpyAsync(st.P.p, pend_host, sizeof(double) * (size_t)p * D, hipMemcpyHostToDevice, s));
         IBO_TRY(vt_rows(g, st.P.p, p, T, ktP.p, st.vtP.p, s));
         KgRowsArgs r = rows_args(g, ktP.p, st.vtP.p, st.P.p, p, clamp_lo);
@@ -136,9 +120,9 @@ int qei_begin(ibo_gp *g, QeiState &st, int npend, const double *pend_host, int n
         HIP_TRY(hipMemcpyAsync(st.muP_host.data(), muP.p, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(q_host.data(), qP.p, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(B_host.data(), Bpp.p, sizeof(double) * (size_t)p * T, hipMemcpyDeviceToHost, s));
-        IBO_TRY(qei_mark(st, 1));
+        IBO_TRY(clock.mark(1));
         HIP_TRY(hipStreamSynchronize(s));
-        IBO_TRY(qei_account(st, 0, 1, ST_PEND));
+        IBO_TRY(clock.account(0, 1, ST_STATE));
         // S_PP: the lower triangle as the cross kernel formed it, mirrored; the diagonal from |v_a|^2
         for (int a = 0; a < p; a++) {
             for (int b = 0; b < a; b++) st.S_host[(size_t)a * p + b] = st.S_host[(size_t)b * p + a] = B_host[(size_t)a * T + b];
@@ -187,71 +171,6 @@ int qei_begin(ibo_gp *g, QeiState &st, int npend, const double *pend_host, int n
     return IBO_OK;
 }
 
-// room for chunks of up to m candidates (the device is idle: a larger buffer replaces a smaller one)
-int qei_reserve(QeiState &st, int64_t m, bool need_cand, bool need_val)
-{
-    const size_t mp = (size_t)round_up((int)std::min(m, st.mc), IBO_COV_TILE), Np = (size_t)st.g->Npad;
-    if (need_cand) IBO_TRY(st.cand.ensure(mp * st.g->D));
-    if (need_val) IBO_TRY(st.val.ensure(mp));
-    IBO_TRY(st.kt.ensure(mp * Np)); IBO_TRY(st.vt.ensure(mp * Np));
-    if (st.p > 0) IBO_TRY(st.C.ensure(mp * IBO_COV_TILE));
-    IBO_TRY(st.mu.ensure(mp)); IBO_TRY(st.s2.ensure(mp));
-    return IBO_OK;
-}
-
-// One chunk: m <= st.mc candidates at cand (device, m x D) -> out (device, m); the per-candidate pieces stay in st.mu / s2 / C.
-// Nothing is waited for unless the stages are being timed.
-int qei_chunk(QeiState &st, int m, const double *cand, double *out)
-{
-    ibo_gp *g = st.g;
-    const int N = g->N, Np = g->Npad, mp = round_up(m, IBO_COV_TILE);
-    hipStream_t s = g->stream;
-    IBO_TRY(qei_mark(st, 0));
-    KERNEL_TRY(launch_cov_kstar(g->kp, g->Xp.p, N, Np, g->DP, cand, m, mp, st.kt.p, s));
-    IBO_TRY(qei_mark(st, 1));
-    KERNEL_TRY(launch_cov_tri(st.kt.p, (size_t)Np, g->W.p, (size_t)Np, N, mp, Np, st.vt.p, (size_t)Np, s));
-    IBO_TRY(qei_mark(st, 2));
-    KgRowsArgs r = rows_args(g, st.kt.p, st.vt.p, cand, m, st.clamp_lo);
-    r.mu = st.mu.p; r.s2 = st.s2.p;
-    KERNEL_TRY(launch_kg_rows(r, s));
-    IBO_TRY(qei_mark(st, 3));
-    if (st.p > 0) KERNEL_TRY(launch_kg_cross(cross_args(st, st.vt.p, m, mp, cand, st.C.p), s));
-    IBO_TRY(qei_mark(st, 4));
-    QeiFinishArgs f;
-    memset(&f, 0, sizeof(f));
-    f.m = m; f.p = st.p; f.S = st.S; f.Sp = st.Sp; f.t = st.t; f.ZG = st.ZG.p; f.mu = st.mu.p; f.s2 = st.s2.p; f.C = st.C.p; f.ldc = (size_t)IBO_COV_TILE;
-    f.qei = out;
-    memcpy(f.L, st.L, sizeof(f.L));
-    KERNEL_TRY(launch_qei_finish(f, s));
-    IBO_TRY(qei_mark(st, 5));
-    if (st.timing) {
-        HIP_TRY(hipStreamSynchronize(s));
-        for (int k = 0; k < 5; k++) IBO_TRY(qei_account(st, k, k + 1, ST_KSTAR + k));
-    }
-    return IBO_OK;
-}
-
-// Host points in chunks: upload, qei_chunk, read back what is asked for (any of the outputs may be NULL).  The device is idle on return.
-int qei_eval_host(QeiState &st, int64_t M, const double *Q_host, double *qei_host, double *mu_host, double *s2_host, double *c_host)
-{
-    ibo_gp *g = st.g;
-    const size_t D = (size_t)g->D, p = (size_t)st.p;
-    hipStream_t s = g->stream;
-    IBO_TRY(qei_reserve(st, M, true, true));
-    for (int64_t c0 = 0; c0 < M; c0 += st.mc) {
-        const int m = (int)std::min(M - c0, st.mc);
-        HIP_TRY(hipMemcpyAsync(st.cand.p, Q_host + (size_t)c0 * D, sizeof(double) * m * D, hipMemcpyHostToDevice, s));
-        IBO_TRY(qei_chunk(st, m, st.cand.p, st.val.p));
-        if (qei_host) HIP_TRY(hipMemcpyAsync(qei_host + c0, st.val.p, sizeof(double) * m, hipMemcpyDeviceToHost, s));
-        if (mu_host) HIP_TRY(hipMemcpyAsync(mu_host + c0, st.mu.p, sizeof(double) * m, hipMemcpyDeviceToHost, s));
-        if (s2_host) HIP_TRY(hipMemcpyAsync(s2_host + c0, st.s2.p, sizeof(double) * m, hipMemcpyDeviceToHost, s));
-        if (c_host && p > 0) HIP_TRY(hipMemcpy2DAsync(c_host + (size_t)c0 * p, sizeof(double) * p, st.C.p, sizeof(double) * IBO_COV_TILE, sizeof(double) * p,
-                                                      (size_t)m, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return IBO_OK;
-}
-
 }  // namespace
 
 extern "C" int ibo_qei_sweep(ibo_gp_t *g, int npend, const double *pend_host, int nsamp, const double *Z_host, double ymax, double xi,
@@ -260,27 +179,12 @@ extern "C" int ibo_qei_sweep(ibo_gp_t *g, int npend, const double *pend_host, in
 {
     IBO_TRY(qei_check(g, npend, pend_host, nsamp, Z_host, xi, jitter, cand_dev != nullptr, M, info));
     if (!qei_dev && !base && !best_val && !best_idx) return fail(IBO_ERR_ARG, "every output is NULL");
-    hipStream_t s = g->stream;
-    const int D = g->D;
-    HIP_TRY(hipEventRecord(g->ev0, s));
+    HIP_TRY(hipEventRecord(g->ev0, g->stream));
     QeiState st;
     IBO_TRY(qei_begin(g, st, npend, pend_host, nsamp, Z_host, ymax, xi, clamp_lo, jitter, info));
     if (base) *base = st.base;
     if (!qei_dev && !best_val && !best_idx) return finish_span(g);
-    IBO_TRY(qei_reserve(st, M, false, qei_dev == nullptr));
-    const int64_t nblk = (M + 255) / 256;
-    ScopedBuf<double> pv;
-    ScopedBuf<int64_t> pi;
-    const bool want_best = best_val || best_idx;
-    if (want_best) { IBO_TRY(pv.ensure((size_t)nblk)); IBO_TRY(pi.ensure((size_t)nblk)); }
-    for (int64_t c0 = 0; c0 < M; c0 += st.mc) {            // (one stream: a chunk's kernels start after the last chunk's have read the scratch)
-        const int m = (int)std::min(M - c0, st.mc);
-        double *out = qei_dev ? qei_dev + c0 : st.val.p;
-        IBO_TRY(qei_chunk(st, m, cand_dev + (size_t)c0 * D, out));
-        if (want_best) KERNEL_TRY(launch_kg_argmax(out, m, c0, index_base, pv.p + c0 / 256, pi.p + c0 / 256, s));
-    }
-    if (want_best) IBO_TRY(argmax_readback(g, pv.p, pi.p, nblk, best_val, best_idx));
-    return finish_span(g);                                      // (waits for the stream: the scratch goes back to the pool after it)
+    return st.rows.sweep(M, cand_dev, index_base, qei_dev, best_val, best_idx);
 }
 
 extern "C" int ibo_qei_batch(ibo_gp_t *g, int npend, const double *pend_host, int nsamp, const double *Z_host, double ymax, double xi,
@@ -295,7 +199,7 @@ extern "C" int ibo_qei_batch(ibo_gp_t *g, int npend, const double *pend_host, in
     if (base) *base = st.base;
     if (mu_pend_host && npend > 0) memcpy(mu_pend_host, st.muP_host.data(), sizeof(double) * (size_t)npend);
     if (S_pend_host && npend > 0) memcpy(S_pend_host, st.S_host.data(), sizeof(double) * (size_t)npend * npend);
-    if (qei_host || mu_host || s2_host || (c_host && npend > 0)) IBO_TRY(qei_eval_host(st, M, Q_host, qei_host, mu_host, s2_host, c_host));
+    if (qei_host || mu_host || s2_host || (c_host && npend > 0)) IBO_TRY(st.rows.eval_host(M, Q_host, qei_host, mu_host, s2_host, c_host, (size_t)npend));
     return finish_span(g);
 }
 
@@ -310,7 +214,7 @@ extern "C" int ibo_qei_direct_max(ibo_gp_t *g, int npend, const double *pend_hos
     QeiState st;
     IBO_TRY(qei_begin(g, st, npend, pend_host, nsamp, Z_host, ymax, xi, clamp_lo, jitter, info));
     const ibo::batch_eval_t value = [&](const double *pts, int n, double *vals) -> int {
-        return qei_eval_host(st, n, pts, vals, nullptr, nullptr, nullptr);
+        return st.rows.eval_host(n, pts, vals, nullptr, nullptr, nullptr, 0);
     };
     char label[64];
     snprintf(label, sizeof(label), "parallel-EI DIRECT (%d pending, %d samples)", npend, nsamp);

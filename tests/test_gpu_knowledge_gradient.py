@@ -172,6 +172,60 @@ def test_bit_invariance_and_argmax(lib):
     assert b2.value == one["kg"][k] and i2.value == 7 + (k if k < 20 else 20)
 
 
+def stage_ms(lib, entry, reset):
+    """the six per-stage sums of ibo_kg_stage_ms / ibo_qei_stage_ms"""
+    ms = np.full(6 + 2, GUARD)
+    lib.check(getattr(lib.lib, entry)(lib.dp(ms), reset))
+    assert np.all(ms[6:] == GUARD)
+    return ms[:6]
+
+
+def test_timing_leaves_the_values_alone_and_fills_its_own_sums(lib):
+    """kg_timing over three chunks (256 + 256 + 88): the same bits from the sweep and the host batch, six sums, their reset, none of qEI's"""
+    from ibo_amd import DeviceArray
+    GP, _ = gp_of("m5", 3, 65, True)
+    h = GP._handle()
+    GP._push_prior()
+    A = kr.ref_points(GP.X, 64); C = pc.queries(GP.X, 600, seed=11)
+    Af = lib.f64(A)
+    dc = DeviceArray.from_host(C, GP._dev.device)
+
+    def sweep():
+        out = DeviceArray((600,), GP._dev.device)
+        bv = ctypes.c_double(); bi = ctypes.c_int64()
+        lib.check(lib.lib.ibo_kg_sweep(h, 64, lib.dp(Af), 600, dc.ptr, 1, kr.CLAMP_PY, 3, out.ptr, ctypes.byref(bv), ctypes.byref(bi)))
+        return out.to_host(), bv.value, bi.value
+
+    def sums_of_a_timed_call():
+        ms = stage_ms(lib, "ibo_kg_stage_ms", 1)
+        print("kg stage sums (ms):", ms)
+        assert np.all(np.isfinite(ms)) and np.all(ms >= 0)
+        assert np.all(ms > 0)                                       # every stage launches a kernel: there is a reference set
+        assert np.all(stage_ms(lib, "ibo_kg_stage_ms", 0) == 0)     # the read above reset them
+        assert np.all(stage_ms(lib, "ibo_qei_stage_ms", 0) == 0)    # and nothing went to the other unit's
+
+    lib.check(lib.lib.ibo_set_option(b"kg_chunk", 256))
+    try:
+        lib.check(lib.lib.ibo_kg_stage_ms(None, 1)); lib.check(lib.lib.ibo_qei_stage_ms(None, 1))
+        lib.check(lib.lib.ibo_kg_stage_ms(None, 0))
+        v0, b0, i0 = sweep()
+        host0 = kg_call(lib, h, A, C, 1)
+        assert np.all(stage_ms(lib, "ibo_kg_stage_ms", 0) == 0)     # timing off: nothing is added
+        lib.check(lib.lib.ibo_set_option(b"kg_timing", 1))
+        v1, b1, i1 = sweep()
+        sums_of_a_timed_call()
+        host1 = kg_call(lib, h, A, C, 1)
+        sums_of_a_timed_call()
+    finally:
+        lib.check(lib.lib.ibo_set_option(b"kg_timing", 0))
+        lib.check(lib.lib.ibo_set_option(b"kg_chunk", 0))
+        lib.check(lib.lib.ibo_kg_stage_ms(None, 1))
+    assert np.array_equal(v1, v0) and b1 == b0 and i1 == i0 and i0 == 3 + int(np.argmax(v0))
+    for k in ("kg", "mu_ref", "mu", "s2", "b"):
+        assert np.array_equal(host1[k], host0[k]), k
+    assert np.array_equal(host0["kg"], v0)
+
+
 def test_many_candidates_on_a_small_model(lib):
     """N = 10 rows: the chunk is bounded by the launch grid (65280 candidates), not by bytes; 70000 candidates cross that bound"""
     from ibo_amd import DeviceArray

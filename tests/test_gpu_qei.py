@@ -204,6 +204,61 @@ def test_one_route_bit_for_bit(lib):
     assert np.array_equal(v0[100:400], one0) and np.array_equal(v0[611:911], one0) and base0 == 0.0
 
 
+def stage_ms(lib, entry, reset):
+    """the six per-stage sums of ibo_qei_stage_ms / ibo_kg_stage_ms"""
+    ms = np.full(6 + 2, GUARD)
+    lib.check(getattr(lib.lib, entry)(lib.dp(ms), reset))
+    assert np.all(ms[6:] == GUARD)
+    return ms[:6]
+
+
+def test_timing_leaves_the_values_alone_and_fills_its_own_sums(lib):
+    """qei_timing over three chunks (256 + 256 + 88), with 7 pending points and with none: the same bits from the sweep and the host batch,
+    six sums, their reset, none of the knowledge gradient's"""
+    from ibo_amd import DeviceArray
+    GP, _ = gp_of("m5", 3, 65, True)
+    h = GP._handle()
+    GP._push_prior()
+    C = pc.queries(GP.X, 600, seed=11)
+    dc = DeviceArray.from_host(C, GP._dev.device)
+
+    def sums_of_a_timed_call(p):
+        ms = stage_ms(lib, "ibo_qei_stage_ms", 1)
+        print("qei stage sums (ms), p = %d:" % p, ms)
+        assert np.all(np.isfinite(ms)) and np.all(ms >= 0)
+        launching = [1, 2, 3, 5] + ([0, 4] if p else [])            # the pending state and the cross stage launch nothing without pending points
+        assert np.all(ms[launching] > 0)
+        if not p:
+            assert ms[0] == 0.0
+        assert np.all(stage_ms(lib, "ibo_qei_stage_ms", 0) == 0)    # the read above reset them
+        assert np.all(stage_ms(lib, "ibo_kg_stage_ms", 0) == 0)     # and nothing went to the other unit's
+
+    lib.check(lib.lib.ibo_set_option(b"qei_chunk", 256))
+    try:
+        lib.check(lib.lib.ibo_qei_stage_ms(None, 1)); lib.check(lib.lib.ibo_kg_stage_ms(None, 1))
+        lib.check(lib.lib.ibo_qei_stage_ms(None, 0))
+        for p in (7, 0):
+            P = qr.pending_points(GP.X, p); Z = qr.samples(256, p + 1)
+            lib.check(lib.lib.ibo_set_option(b"qei_timing", 0))
+            sweep0 = sweep_call(lib, h, P, Z, dc, 600, index_base=3)
+            host0 = qei_call(lib, h, P, Z, C)
+            assert np.all(stage_ms(lib, "ibo_qei_stage_ms", 0) == 0)    # timing off: nothing is added
+            lib.check(lib.lib.ibo_set_option(b"qei_timing", 1))
+            sweep1 = sweep_call(lib, h, P, Z, dc, 600, index_base=3)
+            sums_of_a_timed_call(p)
+            host1 = qei_call(lib, h, P, Z, C)
+            sums_of_a_timed_call(p)
+            (b0, i0, v0, base0), (b1, i1, v1, base1) = sweep0, sweep1
+            assert np.array_equal(v1, v0) and b1 == b0 and i1 == i0 and base1 == base0 and i0 == 3 + int(np.argmax(v0))
+            for k in ("qei", "mu_pend", "S_pend", "mu", "s2", "c"):
+                assert np.array_equal(host1[k], host0[k]), (k, p)
+            assert host1["base"] == host0["base"] == base0 and np.array_equal(host0["qei"], v0)
+    finally:
+        lib.check(lib.lib.ibo_set_option(b"qei_timing", 0))
+        lib.check(lib.lib.ibo_set_option(b"qei_chunk", 0))
+        lib.check(lib.lib.ibo_qei_stage_ms(None, 1))
+
+
 @pytest.mark.parametrize("D,p", [(2, 2), (4, 0)])
 def test_direct_equals_the_host_tree_on_single_points(lib, D, p):
     from ibo_amd.acquisition import ParallelEI, maximizeQEI
