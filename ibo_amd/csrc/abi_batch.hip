@@ -1,6 +1,7 @@
 // abi_batch.hip -- host points behind the C ABI: batches of posteriors and acquisition values (eval_host_points, one sweep or pipelined
 // chunks), query-point gradients, the joint posterior and draws from it, and DIRECT over a GPU objective (direct_maximize, the one driver).
 #include "abi_eval.h"
+#include "abi_factor.h"
 #include "grad.h"
 #include "cov.h"
 
@@ -290,18 +291,14 @@ extern "C" int ibo_posterior_sample(ibo_gp_t *g, int64_t M, const double *Q_host
     const int Mp = round_up((int)M, IBO_COV_TILE), Sp = round_up(nsamp, IBO_COV_TILE);
     ScopedBuf<double> S, d64, Z, F;
     ScopedBuf<int> dinfo;
-    IBO_TRY(S.ensure((size_t)Mp * Mp)); IBO_TRY(d64.ensure((size_t)(Mp / 64) * 4096)); IBO_TRY(dinfo.ensure(1));
+    IBO_TRY(S.ensure((size_t)Mp * Mp)); IBO_TRY(d64.ensure(diag64_size(Mp))); IBO_TRY(dinfo.ensure(1));
     IBO_TRY(Z.ensure((size_t)Sp * Mp)); IBO_TRY(F.ensure((size_t)Sp * Mp));
     HIP_TRY(hipEventRecord(g->ev0, s));
     IBO_TRY(cov_sigma(g, M, Q_host, (with_noise ? 1.0 + g->noise : 1.0) + jitter, 1, S.p, (size_t)Mp));
-    KERNEL_TRY(launch_cholesky(S.p, Mp, d64.p, dinfo.p, s));
-    int h = 0;
-    HIP_TRY(hipMemcpyAsync(&h, dinfo.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (h != 0) {
-        if (info) *info = h;
-        return fail(IBO_ERR_NOT_PD, "posterior covariance + %g I is not positive definite (pivot %d)", jitter, h);
-    }
+    KERNEL_TRY(launch_cholesky(S.p, Mp, d64.p, dinfo.p, s));                  // (FACTOR_IN_PLACE's route; only the factor is wanted)
+    char noun[64];
+    snprintf(noun, sizeof noun, "posterior covariance + %g I", jitter);
+    IBO_TRY(factor_info(dinfo.p, s, noun, info));
     HIP_TRY(hipMemsetAsync(Z.p, 0, sizeof(double) * (size_t)Sp * Mp, s));
     HIP_TRY(hipMemcpy2DAsync(Z.p, sizeof(double) * Mp, Z_host, sizeof(double) * M, sizeof(double) * M, nsamp, hipMemcpyHostToDevice, s));
     KERNEL_TRY(launch_cov_tri(Z.p, (size_t)Mp, S.p, (size_t)Mp, (int)M, Sp, Mp, F.p, (size_t)Mp, s));

@@ -1,7 +1,9 @@
 // abi_internal.h -- what the translation units behind the C ABI (include/ibo_abi.h) share: the error channel, the option switches, the
 // per-device memory pool and its buffer type, the handle (struct ibo_gp) and the helpers one unit lends another.
 //   abi_core.hip    library / options / device memory / pools / handle life cycle
-//   abi_fit.hip     fit, block extension, preference GP, accessors, ibo_cov_matrix, ibo_spd_*
+//   abi_fit.hip     fit, block extension, removal of rows, set_y, prior, accessors, ibo_cov_matrix
+//   abi_pref.hip    the preference GP's device steps (ibo_pref_*)
+//   abi_factor.hip  factor-and-invert for all of these and the gradients: route choice, the routine, the info word; ibo_spd_* (abi_factor.h)
 //   abi_sweep.hip   candidate sweeps: the routes, run_sweep, the sweep entries
 //   abi_batch.hip   host batches, query-point gradients, joint posterior and draws, DIRECT on a GPU objective
 //   abi_cacq.hip    the constrained acquisition (ibo_cacq_*)
@@ -164,19 +166,7 @@ static inline PriorDev prior_of(const ibo_gp *g)
     p.nb = g->nb; p.theta = g->ptheta; p.means = g->pmeans.p; p.beta = g->pbeta.p; p.lowerb = g->plowerb.p; p.width = g->pwidth.p;
     return p;
 }
-// Which order factors an Np-row matrix: the single-level right-looking order with pipelined block columns and W = L^-1 riding along
-// (launch_cholesky_fused) below g_fused2_min_nb block columns, the two-level order (panels of four, K = 256 updates, recursive-doubling
-// inversion) from there on: 104 block columns (6656 rows) by default -- with the eight-wave pipelined column and two steps per pass the
-// single-level order wins up to there (N = 4096: 2.49 -> 2.07 ms; 6400 rows: 6.20 against 6.50; 7040: 8.18 against 7.70).  ONE predicate for
-// ibo_gp_fit, the preference GP's factorisations and ibo_nlml_grad: the order fixes the last bits of L and W.
-static inline bool single_level_order(int Np) { return Np / 64 < g_fused2_min_nb; }
-
-// The super-panels address their tall store [A ; E] (2 Np^2 doubles) through a buffer descriptor with 32-bit offsets: only while it lies inside
-// 2^31 - 1 bytes (11584 rows; an option that keeps a larger matrix in the single-level order takes the step-by-step launches instead)
-static inline bool super_order(int Np) { return single_level_order(Np) && Np / 64 >= g_super_min_nb && 2 * (size_t)Np * Np * sizeof(double) <= 0x7fffffffu; }
-// The packed stores of the left-looking updates (update3.hip) are addressed with 32-bit unsigned byte offsets: one matrix must lie inside
-// 2^32 - 1 bytes (23168 rows)
-static inline bool u3_fits(int Np) { return (size_t)Np * Np * sizeof(double) <= 0xffffffffu; }
+// (which order factors a matrix, and the factor-and-invert routine itself: abi_factor.h)
 
 // ---- helpers one unit lends another
 int exp_table(int device, const double **out);                                                            // abi_sweep.hip: 2^(j/2048), one per device
@@ -185,6 +175,8 @@ int ibo_comm_exchange_dev(ibo_comm_t *c, hipStream_t s, const double *res_v, con
 uint64_t alloc_generation(int device, const void *p, size_t bytes, size_t *offset);                       // abi_core.hip
 int ensure_pinned(ibo_gp *g, size_t need);                                                                // abi_core.hip
 int make_kparams(int ktype, int D, const double *hyper, int nhyper, double sf2, KParams *kp);             // abi_fit.hip
+int ensure_R(ibo_gp *g);                                                                                  // abi_fit.hip: R = K(X, X) + diag, formed on request
+int fit_factor(ibo_gp *g, const KParams &kp, int N, double noise, bool have_A, int *info);                // abi_fit.hip: a fit after staging (have_A: of g->A)
 int fit_from_inverse(ibo_gp *g, int ktype, int N, int D, const double *X, const double *Y,
                      const double *hyper, int nhyper, double sf2, double noise, const double *invR);      // abi_fit.hip
 int direct_on_gp(ibo_gp *g, int D, const double *lb, const double *ub, int acq, double parm, int erf_mode,

@@ -1,6 +1,6 @@
 // abi_nlml.hip -- the marginal-likelihood side of the C ABI: the batched theta-grid, one value + gradient, and ibo_trim (which owns
 // their per-device workspaces).
-#include "abi_internal.h"
+#include "abi_factor.h"
 #include "loo.h"
 
 // ------------------------------------------------------------------------ marginal-likelihood grid
@@ -80,7 +80,7 @@ extern "C" int ibo_nlml_grid(int device, int ktype, int N, int D, const double *
     hipStream_t s = nullptr;
     IBO_TRY(dX.ensure((size_t)N * D)); IBO_TRY(dY.ensure(N));
     IBO_TRY(dout.ensure(2 * (size_t)n_theta)); IBO_TRY(dinfo.ensure(n_theta));
-    IBO_TRY(dL.ensure(nn * B)); IBO_TRY(d64.ensure((size_t)(Np / 64) * 4096 * B));
+    IBO_TRY(dL.ensure(nn * B)); IBO_TRY(d64.ensure(diag64_size(Np) * B));
     // packed operands of the trailing updates, per matrix: the factor's finished columns in fragment order (update3.hip; the
     // right-looking A/B order writes and reads one panel of it at a time)
     const bool left = g_chol_left != 0;
@@ -155,7 +155,7 @@ extern "C" int ibo_nlml_grid(int device, int ktype, int N, int D, const double *
                 hipStream_t sg = ws.streams[g];
                 HIP_TRY(hipEventRecord(ws.t0[g], sg));
                 const int k0 = (int)((long long)nb * g / G), k1 = (int)((long long)nb * (g + 1) / G), ng = k1 - k0;
-                grp[g] = CholGroup{dL.p + nn * k0, d64.p + (size_t)(Np / 64) * 4096 * k0, ws.dP.p + pws * k0, dinfo.p + t0 + k0, ng, sg,
+                grp[g] = CholGroup{dL.p + nn * k0, d64.p + diag64_size(Np) * k0, ws.dP.p + pws * k0, dinfo.p + t0 + k0, ng, sg,
                                    with_flags ? ws.dflags.p + 4 * k0 : nullptr};
                 KERNEL_TRY(launch_cov_matrix_batched(ws.dkp.p + t0 + k0, ng, N, dX.p, D, IBO_DIAG_KERNEL_PLUS_NOISE, noise, dL.p + nn * k0, Np, nn, sg, dot_ok));
                 KERNEL_TRY(launch_nlml_aug(dL.p + nn * k0, Np, N, dY.p, sg, ng, nn));
@@ -210,8 +210,8 @@ static int grad_prepare(GradWorkspace &ws, const KParams &kp, int N, int D, cons
                    &dal = ws.dal, &da1 = ws.da1, &tmp = ws.tmp;
     DevBuf<int> &dinfo = ws.dinfo;
     IBO_TRY(dX.ensure((size_t)N * D)); IBO_TRY(dY.ensure(Np)); IBO_TRY(dL.ensure(nn)); IBO_TRY(dW.ensure(nn));
-    IBO_TRY(dT.ensure(nn)); IBO_TRY(dKi.ensure(nn)); IBO_TRY(d64.ensure((size_t)(Np / 64) * 4096));
-    IBO_TRY(dal.ensure(Np)); IBO_TRY(da1.ensure(Np)); IBO_TRY(tmp.ensure(2 * (size_t)Np + 2 * (size_t)(Np / 64) * Np + 64));
+    IBO_TRY(dT.ensure(nn)); IBO_TRY(dKi.ensure(nn)); IBO_TRY(d64.ensure(diag64_size(Np)));
+    IBO_TRY(dal.ensure(Np)); IBO_TRY(da1.ensure(Np)); IBO_TRY(tmp.ensure(alpha_scratch(Np)));
     IBO_TRY(dinfo.ensure(1));
     hipStream_t s = nullptr;
     if (ws.hostX.size() != (size_t)N * D || memcmp(ws.hostX.data(), X, sizeof(double) * N * D) != 0) {
@@ -227,32 +227,24 @@ static int grad_prepare(GradWorkspace &ws, const KParams &kp, int N, int D, cons
         ws.hostY.swap(yp);
     }
     if (!ws.pin) HIP_TRY(hipHostMalloc((void **)&ws.pin, sizeof(double) * (IBO_GRAD_MAX + 4), hipHostMallocDefault));
-    // up to 2048 rows: the fit's route -- fused steps with W = L^-1 riding along (dT: the matrix being reduced, dKi: (L^-1)^T
-    // until the transpose) -- instead of the three-kernel columns and the recursive-doubling inversion
-    const bool fused = single_level_order(Np);
-    if (!u3_fits(Np)) return fail(IBO_ERR_ARG, "at most 23168 rows: the factorisation's packed store must lie inside 2^32 - 1 bytes (model: %d padded rows)", Np);
+    // the fit's routes: the matrix in dT (in super-panels: in the tall buffer, with the ride-along's identity), the factor into dL, (L^-1)^T
+    // (or the doubling's scratch) in dKi, W into dW -- no packed copy: nothing sweeps here; the two-level order is lent no packed-update store
+    FactorRoute route;
+    IBO_TRY(factor_route(Np, FACTOR_FIT, &route));
+    const bool fused = route != ROUTE_TWO_LEVEL;
+    FactorBufs b = {};
+    b.A = dT.p; b.eye = dW.p;
+    if (route == ROUTE_RIDE_SUPER) {
+        IBO_TRY(ws.tall.ensure(2 * nn)); IBO_TRY(ws.Pk2.ensure(2 * nn));
+        b.A = ws.tall.p; b.eye = ws.tall.p + nn; b.Pk = ws.Pk2.p;
+    }
+    b.L = dL.p; b.Et = dKi.p; b.W = dW.p; b.d64 = d64.p; b.info = dinfo.p;
+    b.info_zero = true; b.eye_ready = fused;             // (launch_cov_fit's one pass)
     if (!ws.t0) { HIP_TRY(hipEventCreate(&ws.t0)); HIP_TRY(hipEventCreate(&ws.t1)); }
     HIP_TRY(hipEventRecord(ws.t0, s));
-    if (fused && super_order(Np)) {
-        // (the fit's rule: from g_super_min_nb block columns on in super-panels -- the matrix and the ride-along's identity in one tall buffer; same bits)
-        IBO_TRY(ws.tall.ensure(2 * nn)); IBO_TRY(ws.Pk2.ensure(2 * nn));
-        KERNEL_TRY(launch_cov_fit(kp, N, dX.p, D, IBO_DIAG_KERNEL_PLUS_NOISE, noise, ws.tall.p, Np, ws.tall.p + nn, dinfo.p, s));
-        KERNEL_TRY(launch_cholesky_super(ws.tall.p, dL.p, Np, d64.p, dinfo.p, s, dKi.p, ws.Pk2.p, true));
-    } else if (fused) {
-        KERNEL_TRY(launch_cov_fit(kp, N, dX.p, D, IBO_DIAG_KERNEL_PLUS_NOISE, noise, dT.p, Np, dW.p, dinfo.p, s));
-        KERNEL_TRY(launch_cholesky_fused(dT.p, dL.p, Np, d64.p, dinfo.p, s, dW.p, dKi.p, true));
-    } else {
-        // beyond: the two-level order with fused in-panel columns, out of place
-        KERNEL_TRY(launch_cov_fit(kp, N, dX.p, D, IBO_DIAG_KERNEL_PLUS_NOISE, noise, dT.p, Np, nullptr, dinfo.p, s));
-        KERNEL_TRY(launch_cholesky_fused2(dT.p, dL.p, Np, d64.p, dinfo.p, 4, s, true));
-    }
+    KERNEL_TRY(launch_cov_fit(kp, N, dX.p, D, IBO_DIAG_KERNEL_PLUS_NOISE, noise, b.A, Np, fused ? b.eye : nullptr, dinfo.p, s));
     // no look at the info word until everything is queued: a failed factorisation only turns the rest into NaNs
-    if (fused) KERNEL_TRY(launch_transpose_pack(dKi.p, N, Np, dW.p, nullptr, s));      // W, pad rows zero (no packed copy: nothing sweeps here)
-    else {
-        KERNEL_TRY(launch_zero_upper(dL.p, Np, s));
-        KERNEL_TRY(launch_trinv(dL.p, Np, d64.p, dW.p, dT.p, s));
-        KERNEL_TRY(launch_pack_w(dW.p, N, Np, 0, dW.p, dT.p, s));                      // zero the pad rows
-    }
+    IBO_TRY(factor_invert(route, N, Np, b, s));
     KERNEL_TRY(launch_alpha(dW.p, N, Np, dY.p, tmp.p, dal.p, da1.p, s));
     // K^-1 = W^T W: with the ride-along, W^T is what the factorisation left in dKi -- no transpose; the result goes to dT, free by now
     const double *Kinv = fused ? dT.p : dKi.p;
@@ -273,9 +265,35 @@ static int grad_prepare(GradWorkspace &ws, const KParams &kp, int N, int D, cons
         }
         KERNEL_TRY(launch_syrk3(dKi.p, dL.p, dT.p, Np, ws.dtasks.p, ws.ntasks, ws.dsums.p, ws.nsums, ws.dpiece.p, s));
     } else if (fused) KERNEL_TRY(launch_wtw(dW.p, dKi.p, dT.p, Np, s, 1, 1));
-    else KERNEL_TRY(launch_wtw(dW.p, dT.p, dKi.p, Np, s, 1));
+    else KERNEL_TRY(launch_wtw(dW.p, dT.p, dKi.p, Np, s, 1));                      // (dT: scratch for W^T)
     *Kinv_out = Kinv;
     return IBO_OK;
+}
+
+// modes / dims -> the derivative spec the contraction kernels take (ngrad = 0: none)
+static int grad_spec(int ngrad, const int *modes, const int *dims, int D, GradSpec *gs)
+{
+    gs->nh = ngrad;
+    for (int h = 0; h < ngrad; h++) {
+        if (modes[h] < 0 || modes[h] > 4 || dims[h] < 0 || dims[h] >= D) return fail(IBO_ERR_ARG, "bad derivative spec");
+        gs->mode[h] = modes[h]; gs->dim[h] = dims[h];
+    }
+    return IBO_OK;
+}
+
+// The end of an evaluation queued behind grad_prepare: ws.t1, the `nres` result doubles and the info word through the pinned block behind ONE
+// synchronisation, the span t0 -> t1 to the device's GPU time, the pivot check.  The results are then at ws.pin.
+static int grad_finish(GradWorkspace &ws, int device, const double *res_dev, int nres)
+{
+    hipStream_t s = nullptr;
+    HIP_TRY(hipEventRecord(ws.t1, s));
+    HIP_TRY(hipMemcpyAsync(ws.pin, res_dev, sizeof(double) * nres, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ws.pin + IBO_GRAD_MAX + 2, ws.dinfo.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    int h = 0;
+    memcpy(&h, ws.pin + IBO_GRAD_MAX + 2, sizeof(int));
+    { float ms = 0.f; if (hipEventElapsedTime(&ms, ws.t0, ws.t1) == hipSuccess) gpu_time_add(device, ms); }
+    return factor_info_word(h, "covariance matrix", nullptr);
 }
 
 // NLML and its gradient w.r.t. the log hyper-parameters for ONE theta: marginalLikelihood(...,
@@ -292,35 +310,22 @@ extern "C" int ibo_nlml_grad(int device, int ktype, int N, int D, const double *
     KParams kp;
     IBO_TRY(make_kparams(ktype, D, hyper, nhyper, sf2, &kp));
     GradSpec gs;
-    gs.nh = ngrad;
-    for (int h = 0; h < ngrad; h++) {
-        if (modes[h] < 0 || modes[h] > 4 || dims[h] < 0 || dims[h] >= D) return fail(IBO_ERR_ARG, "bad derivative spec");
-        gs.mode[h] = modes[h]; gs.dim[h] = dims[h];
-    }
+    IBO_TRY(grad_spec(ngrad, modes, dims, D, &gs));
     const int Np = round_up(N, 64);
     const int nblk = ((N + 15) / 16) * ((N + 15) / 16);
     GradWorkspace &ws = g_grad_ws[device & 15];
     DevBuf<double> &dX = ws.dX, &dal = ws.dal, &dpart = ws.dpart, &dout = ws.dout;
-    DevBuf<int> &dinfo = ws.dinfo;
     IBO_TRY(dpart.ensure((size_t)ngrad * nblk)); IBO_TRY(dout.ensure(ngrad + 2));
     hipStream_t s = nullptr;
     const double *Kinv = nullptr;
     IBO_TRY(grad_prepare(ws, kp, N, D, X, Y, noise, dout.p + ngrad, &Kinv));
     KERNEL_TRY(launch_nlml_grad(kp, gs, N, dX.p, D, Kinv, Np, dal.p, dpart.p, dout.p, s));
-    HIP_TRY(hipEventRecord(ws.t1, s));
-    HIP_TRY(hipMemcpyAsync(ws.pin, dout.p, sizeof(double) * (ngrad + 2), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ws.pin + IBO_GRAD_MAX + 2, dinfo.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    IBO_TRY(grad_finish(ws, device, dout.p, ngrad + 2));
     const double *res = ws.pin;
-    int h = 0;
-    memcpy(&h, ws.pin + IBO_GRAD_MAX + 2, sizeof(int));
-    { float ms = 0.f; if (hipEventElapsedTime(&ms, ws.t0, ws.t1) == hipSuccess) gpu_time_add(device, ms); }
-    if (h != 0) return fail(IBO_ERR_NOT_PD, "covariance matrix is not positive definite (pivot %d)", h);
     for (int i = 0; i < ngrad; i++) grad_host[i] = res[i];
     *nlml_host = 0.5 * res[ngrad] + res[ngrad + 1] + 0.5 * N * log(2.0 * M_PI);
     return IBO_OK;
 }
-
 
 // The leave-one-out objective (Rasmussen & Williams 5.4.2, to be minimised like the NLML), its gradient w.r.t. the log hyper-parameters and the
 // leave-one-out predictions for ONE theta: ibo_nlml_grad's sequence up to K^-1 on its workspace, then loo.hip.
@@ -336,11 +341,7 @@ extern "C" int ibo_loo_grad(int device, int ktype, int N, int D, const double *X
     KParams kp;
     IBO_TRY(make_kparams(ktype, D, hyper, nhyper, sf2, &kp));
     GradSpec gs;
-    gs.nh = grad_host ? ngrad : 0;
-    for (int h = 0; h < gs.nh; h++) {
-        if (modes[h] < 0 || modes[h] > 4 || dims[h] < 0 || dims[h] >= D) return fail(IBO_ERR_ARG, "bad derivative spec");
-        gs.mode[h] = modes[h]; gs.dim[h] = dims[h];
-    }
+    IBO_TRY(grad_spec(grad_host ? ngrad : 0, modes, dims, D, &gs));
     const int Np = round_up(N, 64);
     GradWorkspace &ws = g_grad_ws[device & 15];
     IBO_TRY(ws.lout.ensure(IBO_GRAD_MAX + 1)); IBO_TRY(ws.lmu.ensure(2 * (size_t)Np));
@@ -351,14 +352,7 @@ extern "C" int ibo_loo_grad(int device, int ktype, int N, int D, const double *X
     double *dmu = ws.lmu.p, *ds2 = ws.lmu.p + Np;
     KERNEL_TRY(launch_loo_value(Kinv, (size_t)Np, N, ws.dY.p, ws.dal.p, mu_host ? dmu : nullptr, s2_host ? ds2 : nullptr, ws.lout.p + IBO_GRAD_MAX, s));
     if (gs.nh) KERNEL_TRY(launch_loo_contract(kp, gs, N, Np, ws.dX.p, D, Kinv, ws.dal.p, ws.lpart.p, ws.lout.p, s));
-    HIP_TRY(hipEventRecord(ws.t1, s));
-    HIP_TRY(hipMemcpyAsync(ws.pin, ws.lout.p, sizeof(double) * (IBO_GRAD_MAX + 1), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ws.pin + IBO_GRAD_MAX + 2, ws.dinfo.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    int h = 0;
-    memcpy(&h, ws.pin + IBO_GRAD_MAX + 2, sizeof(int));
-    { float ms = 0.f; if (hipEventElapsedTime(&ms, ws.t0, ws.t1) == hipSuccess) gpu_time_add(device, ms); }
-    if (h != 0) return fail(IBO_ERR_NOT_PD, "covariance matrix is not positive definite (pivot %d)", h);
+    IBO_TRY(grad_finish(ws, device, ws.lout.p, IBO_GRAD_MAX + 1));
     if (mu_host) HIP_TRY(hipMemcpy(mu_host, dmu, sizeof(double) * N, hipMemcpyDeviceToHost));
     if (s2_host) HIP_TRY(hipMemcpy(s2_host, ds2, sizeof(double) * N, hipMemcpyDeviceToHost));
     for (int i = 0; i < gs.nh; i++) grad_host[i] = ws.pin[i];

@@ -406,28 +406,8 @@ int launch_zero_upper(double *A, int Npad, hipStream_t s)
 }
 
 
-// W[r][c] = Et[c][r] for c <= r, 0 above the diagonal (Et = (L^-1)^T from the ride-along; its blocks below the
-// diagonal were never written)
-__global__ void transpose_lower_kernel(const double *__restrict__ Et, double *__restrict__ W, int Npad)
-{
-    __shared__ double tile[64][65];
-    const int bx = blockIdx.x * 64, by = blockIdx.y * 64;       // W block (row block y, column block x)
-    if (blockIdx.x > blockIdx.y) {
-        for (int e = threadIdx.x; e < 4096; e += 256) W[(size_t)(by + (e >> 6)) * Npad + bx + (e & 63)] = 0.0;
-        return;
-    }
-    for (int e = threadIdx.x; e < 4096; e += 256) {
-        const int r = e >> 6, c = e & 63;
-        tile[r][c] = Et[(size_t)(bx + r) * Npad + by + c];       // Et block (x, y)
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < 4096; e += 256) {
-        const int r = e >> 6, c = e & 63;
-        W[(size_t)(by + r) * Npad + bx + c] = (bx + c <= by + r) ? tile[c][r] : 0.0;
-    }
-}
-
-// The same with the result's rows >= N zeroed, and a second copy in MFMA fragment order (pack_w_kernel's layout, mode 0):
+// W[r][c] = Et[c][r] for c <= r, 0 above the diagonal (Et = (L^-1)^T from the ride-along; its blocks below the diagonal were never
+// written), the result's rows >= N zeroed, and (if wanted) a second copy in MFMA fragment order (pack_w_kernel's layout, mode 0):
 // the fit's transpose and packing passes in one.  Wp must not be Et's buffer.
 __global__ void transpose_pack_kernel(const double *__restrict__ Et, int N, int Npad, double *__restrict__ W,
                                       double *__restrict__ Wp)
@@ -463,12 +443,6 @@ int launch_transpose_pack(const double *Et, int N, int Npad, double *W, double *
     // (up to ~1500 rows the grid is at most two workgroups per CU and a workgroup's three passes over its 4096 elements are what the kernel lasts:
     // 1024 threads take four elements each instead of sixteen)
     hipLaunchKernelGGL(transpose_pack_kernel, dim3(Npad / 64, Npad / 64), dim3(Npad <= 1536 ? 1024 : 256), 0, s, Et, N, Npad, W, Wp);
-    return (int)hipGetLastError();
-}
-
-int launch_transpose_lower(const double *Et, double *W, int Npad, hipStream_t s)
-{
-    hipLaunchKernelGGL(transpose_lower_kernel, dim3(Npad / 64, Npad / 64), dim3(256), 0, s, Et, W, Npad);
     return (int)hipGetLastError();
 }
 

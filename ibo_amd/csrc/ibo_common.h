@@ -460,12 +460,10 @@ static const int kSuperFrom = 64;       // block columns (4096 rows) from which 
 static const int kSuperPanel = 16;
 int launch_cholesky_super(double *tall, double *out, int Npad, double *diag64, int *info_dev, hipStream_t s, double *Eout, double *Pk,
                           bool info_is_zero = false);
-int launch_transpose_lower(const double *Et, double *W, int Npad, hipStream_t s);
-// W = Et^T (lower, rows >= N zero) and its MFMA-fragment-order copy Wp (another buffer than Et) in one pass
+// W = Et^T (lower, rows >= N zero) and, unless Wp is null, its MFMA-fragment-order copy Wp (another buffer than Et) in one pass
 int launch_transpose_pack(const double *Et, int N, int Npad, double *W, double *Wp, hipStream_t s);
-// W = L^-1 (row-major, ld = Npad) using diag64 from launch_cholesky and a scratch T (Npad x Npad)
-int launch_trinv(const double *L, int Npad, const double *diag64, double *W, double *T, hipStream_t s,
-                 bool zero_fill = true);
+// W = L^-1 (row-major, ld = Npad; only the blocks on and below the diagonal are written) using diag64 from launch_cholesky and a scratch T (Npad x Npad)
+int launch_trinv(const double *L, int Npad, const double *diag64, double *W, double *T, hipStream_t s);
 // zero the strict upper triangle (ld = Npad)
 int launch_zero_upper(double *A, int Npad, hipStream_t s);
 // Wout/Wp from S; mode 0: W[i][j] = S[i][j]; mode 1: W[i][j] = S[N-1-j][N-1-i] (i,j < N);

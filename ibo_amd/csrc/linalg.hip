@@ -8,14 +8,17 @@
 //
 // Layout: every N x N matrix lives row-major with leading dimension Npad (a multiple of 64) so that all tile kernels run
 // without bounds checks; the pad is the identity for matrices that get factored and zero for W.
-// Orders (the order fixes the rounding, so it depends on the matrix size and the entry point, never on a batch size):
+// Orders (the order fixes the rounding, so it depends on the matrix size and the entry point, never on a batch size; which caller takes
+// which is decided in ONE place, factor_route in abi_factor.hip):
 //   * single matrix, < 104 block columns: plain right-looking, one launch per block column, out of place, W riding along
-//     (launch_cholesky_fused: chol_step8_kernel below four block columns, chol_pipe8_kernel -- software-pipelined -- from there);
+//     (launch_cholesky_fused: chol_step8_kernel below four block columns, chol_pipe8_kernel -- software-pipelined -- from there; from
+//     64 block columns in super-panels, launch_cholesky_super: the same bits; both launch from pipe8_schedule, chol_schedule.h);
 //   * single matrix beyond: two-level (panels of four block columns, K = 256 updates), then launch_trinv (launch_cholesky_fused2);
-//   * in place, any batch (the legacy inverse, ibo_spd_*, preference GPs beyond the first range): launch_cholesky_batched;
+//   * in place, any batch (the legacy inverse, ibo_spd_*, posterior draws, preference GPs beyond the first range): launch_cholesky_batched;
 //   * the likelihood grid: left-looking from a packed copy of the factor (launch_cholesky_batched_left, update3.hip).
 // Covariance assembly, packing, the alpha vectors, the gradient contraction and the small per-model kernels: assemble.hip.
 #include "ibo_common.h"
+#include "chol_schedule.h"
 #include <atomic>
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -1534,34 +1537,15 @@ int launch_cholesky_fused(double *work, double *out, int Npad, double *diag64, i
         const bool pairs = nb >= kPairsFrom;
         int split = nb;                                 // (pairs: first column whose pair of steps waits for the odd launch)
         for (int jb = 0; jb < nb; jb++) {
-            const int m = nb - jb - 1, nE = Ework ? jb + 1 : 0;
-            const int nrow = m + nE + 1;                                                  // (one more: the diagonal block's keeper)
-            const int ntile = jb > 0 ? m * (m + 1) / 2 + (Ework ? jb * m : 0) : 0;        // step jb - 1 right of column jb
             if (pairs) {
-                // two steps per pass.  The pair of steps (2 p, 2 p + 1) is due on every column right of 2 p + 2 and may ride in launch
-                // 2 p + 2 or 2 p + 3: the columns up to `split` (at least the two that the next launches factor) take it in the even launch,
-                // the rest in the odd one -- which also carries step jb - 1 for column jb + 1 alone -- so that both launches have about
-                // the same number of tiles to hide under their chain.
-                const int nE1 = Ework ? 1 : 0;
-                int nsingle = 0, q = 0, c_lo = 0, c_hi = 0;
-                if (jb & 1) {
-                    nsingle = m > 0 ? m + nE1 * jb : 0;
-                    if (jb >= 3) { q = jb - 2; c_lo = split < nb ? split : nb; c_hi = nb; }
-                } else if (jb >= 2) {
-                    q = jb - 1;
-                    // tiles of column k: (nb - k) of the matrix + (q + 1) of E; half of them, but columns jb + 1 and jb + 2 in any case
-                    long total = 0, run = 0;
-                    for (int k = jb + 1; k < nb; k++) total += (nb - k) + nE1 * (q + 1);
-                    const long later = nb - jb - 2 > 0 ? (nb - jb - 2) + nE1 * (jb + 1) : 0;        // the odd launch's own tiles (column jb + 2)
-                    split = jb + 1;
-                    while (split < nb && (split < jb + 3 || 2 * run < total + later)) { run += (nb - split) + nE1 * (q + 1); split++; }
-                    c_lo = jb + 1; c_hi = split;
-                }
-                long npair = 0;
-                for (int k = c_lo; k < c_hi; k++) npair += (nb - k) + nE1 * (q + 1);
-                hipLaunchKernelGGL(chol_pipe8_kernel<1>, dim3(nrow + nsingle + (int)npair), dim3(512), 0, s, work, out, Npad, jb, diag64, info_dev,
-                                   nrow, Ework, Eout, nb, jb > 0 ? 1 : 0, nsingle, q, c_lo, c_hi);
+                // two steps per pass: which launch applies which pair of steps to which columns is pipe8_schedule's (chol_schedule.h)
+                const Pipe8Launch l = pipe8_schedule(nb, jb, 0, nb, Ework != nullptr, split);
+                hipLaunchKernelGGL(chol_pipe8_kernel<1>, dim3(l.grid), dim3(512), 0, s, work, out, Npad, jb, diag64, info_dev,
+                                   l.nrow, Ework, Eout, nb, l.pre, l.nsingle, l.q, l.c_lo, l.c_hi);
             } else {
+                const int m = nb - jb - 1, nE = Ework ? jb + 1 : 0;
+                const int nrow = m + nE + 1;                                                  // (one more: the diagonal block's keeper)
+                const int ntile = jb > 0 ? m * (m + 1) / 2 + (Ework ? jb * m : 0) : 0;        // step jb - 1 right of column jb
                 hipLaunchKernelGGL(chol_pipe8_kernel<0>, dim3(nrow + ntile), dim3(512), 0, s, work, out, Npad, jb, diag64, info_dev, nrow,
                                    Ework, Eout, nb, jb > 0 ? 1 : 0, 0, 0, 0, 0);
             }
@@ -1599,31 +1583,6 @@ int launch_cholesky_fused(double *work, double *out, int Npad, double *diag64, i
 // transpose + alpha 125.  Measured and not kept: the later super-panels' part of an update on a second stream beside the next chain (its
 // 64 KB workgroups hold the CUs the chain's 133 KB workgroups need: the next super-panel's first launch waits for them, 2.07 ms), panels
 // of 8 / 24 / 32 block columns (2.21 / 2.08 / 2.17 ms).
-static void pipe8_launch_in_panel(double *work, double *out, int Npad, int jb, int c0, int c1, int &split, double *diag64, int *info_dev, hipStream_t s,
-                                  double *Ework, double *Eout)
-{
-    const int nb = Npad / 64;
-    const int m = nb - jb - 1, nE = jb + 1;
-    const int nrow = m + nE + 1;
-    int nsingle = 0, q = 0, c_lo = 0, c_hi = 0;
-    if (jb & 1) {
-        if (jb + 1 < c1) nsingle = m + jb;                     // step jb - 1 on column jb + 1 (the next super-panel's first column takes it deep)
-        if (jb >= c0 + 3) { q = jb - 2; c_lo = split < c1 ? split : c1; c_hi = c1; }
-    } else if (jb >= c0 + 2) {
-        q = jb - 1;
-        long total = 0, run = 0;
-        for (int k = jb + 1; k < c1; k++) total += (nb - k) + (q + 1);
-        const long later = jb + 2 < c1 ? (nb - jb - 2) + (jb + 1) : 0;
-        split = jb + 1;
-        while (split < c1 && (split < jb + 3 || 2 * run < total + later)) { run += (nb - split) + (q + 1); split++; }
-        c_lo = jb + 1; c_hi = split;
-    } else split = c1;                                         // a super-panel's first launch: no pair is due yet
-    long npair = 0;
-    for (int k = c_lo; k < c_hi; k++) npair += (nb - k) + (q + 1);
-    hipLaunchKernelGGL(chol_pipe8_kernel<1>, dim3(nrow + nsingle + (int)npair), dim3(512), 0, s, work, out, Npad, jb, diag64, info_dev,
-                       nrow, Ework, Eout, nb, jb > c0 ? 1 : 0, nsingle, q, c_lo, c_hi);
-}
-
 int launch_cholesky_super(double *tall, double *out, int Npad, double *diag64, int *info_dev, hipStream_t s, double *Eout, double *Pk,
                           bool info_is_zero)
 {
@@ -1634,7 +1593,12 @@ int launch_cholesky_super(double *tall, double *out, int Npad, double *diag64, i
     for (int c0 = 0; c0 < nb; c0 += S) {
         const int c1 = c0 + S < nb ? c0 + S : nb;
         int split = c1;
-        for (int jb = c0; jb < c1; jb++) pipe8_launch_in_panel(work, out, Npad, jb, c0, c1, split, diag64, info_dev, s, Ework, Eout);
+        for (int jb = c0; jb < c1; jb++) {
+            // (step jb - 1 on column c1, the next super-panel's first, is not carried here: that column takes it deep)
+            const Pipe8Launch l = pipe8_schedule(nb, jb, c0, c1, true, split);
+            hipLaunchKernelGGL(chol_pipe8_kernel<1>, dim3(l.grid), dim3(512), 0, s, work, out, Npad, jb, diag64, info_dev,
+                               l.nrow, Ework, Eout, nb, l.pre, l.nsingle, l.q, l.c_lo, l.c_hi);
+        }
         if (c1 >= nb) break;
         // the finished columns in fragment order (the matrix's rows below the super-panel, E's rows 0 .. 64 c1), then every later column's update
         int rc = launch_chol_pack3(out, Npad, 64 * c1, 64 * c0, 64 * (c1 - c0), 1, 0, Pk, 0, s);
@@ -1816,12 +1780,10 @@ void trinv_W_kernel(double *__restrict__ W, const double *__restrict__ T, int Np
             for (int q = 0; q < 4; q++) C[(size_t)TNN_ROW(m, q) * Npad + TNN_COL(n)] = -acc[m][n][q];
 }
 
-int launch_trinv(const double *L, int Npad, const double *diag64, double *W, double *T, hipStream_t s, bool zero_fill)
+int launch_trinv(const double *L, int Npad, const double *diag64, double *W, double *T, hipStream_t s)
 {
     int nb = Npad / 64;
-    // the doubling only ever reads and writes blocks on or below the diagonal; the zeros above it are for
-    // consumers that take W as a full matrix (the fit path re-writes all of W in pack_w_kernel instead)
-    if (zero_fill) HIPCHK(hipMemsetAsync(W, 0, sizeof(double) * (size_t)Npad * Npad, s));
+    // (the doubling only ever reads and writes blocks on or below the diagonal; W's other blocks are the caller's: pack_w_kernel rewrites all of W)
     hipLaunchKernelGGL(trinv_place_diag_kernel, dim3(nb), dim3(256), 0, s, diag64, W, Npad);
     for (int sz = 1; sz < nb; sz *= 2) {
         int nodes = (nb + 2 * sz - 1) / (2 * sz);

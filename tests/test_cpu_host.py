@@ -574,3 +574,31 @@ def test_direct_host_under_address_and_undefined_behaviour_sanitizers(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     assert "0 failure(s)" in r.stdout and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+
+
+def test_pipelined_cholesky_schedule_against_the_loops_it_replaced_and_the_kernels_invariant(tmp_path):
+    """The launch schedule of the pipelined single-level order (csrc/chol_schedule.h: which launch applies which pair of steps to which
+    block columns) is one host function for launch_cholesky_fused and launch_cholesky_super.  tools/chol_schedule_check.cpp, built with
+    g++ -fsanitize=address,undefined where the toolchain has the run-time, runs it for every size from 4 to 362 block columns, with and
+    without the ride-along, and from 32 block columns in super-panels: (a) it returns field by field what the two loops it replaced
+    returned; (b) within a panel every column receives each earlier step exactly once, in ascending order, never before the step's own
+    column has been factored and always before or inside the launch that factors the column, and the grid is exactly the tiles
+    chol_pipe8_kernel<1> enumerates."""
+    import shutil, subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    probe = tmp_path / "p.cpp"
+    probe.write_text("int main(){return 0;}\n")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    if subprocess.run(["g++", san[0], str(probe), "-o", str(tmp_path / "p")], capture_output=True).returncode != 0:
+        san = []
+    exe = tmp_path / "chol_schedule_check"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall"] + san + ["-I", os.path.join(root, "ibo_amd", "csrc"),
+                    os.path.join(root, "tools", "chol_schedule_check.cpp"), "-o", str(exe)], check=True, timeout=300)
+    env = dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1")
+    env.pop("LD_PRELOAD", None)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert " 0 failure(s)" in r.stdout and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+    assert int(r.stdout.split()[0]) > 190000          # every size, both forms and the super-panels were walked

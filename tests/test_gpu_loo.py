@@ -231,6 +231,37 @@ def test_loo_likelihood_on_each_route_to_the_inverse(lib, case):
     run_case(case, repeat=True)
 
 
+def test_nlml_and_loo_gradients_on_a_small_two_level_matrix(lib):
+    """fused2_min_nb = 3 sends 150 rows (three block columns) of ibo_nlml_grad and ibo_loo_grad through the two-level order and the
+    doubling tail (launch_trinv without a fill, launch_pack_w) that the 6700-row cases reach by size: value to 1e-9 relative, gradient to
+    1e-8 of its largest component (test_nlml_gradient_on_the_two_level_branch's bounds) against the float64 restatements, the
+    leave-one-out predictions to check_points' bounds, and a repeat gives the same bits."""
+    from ibo_amd.gaussianprocess.trainhyper import looLikelihood, marginalLikelihood
+    theta, D, N = [.4, .5, .6], 3, 150
+    X, Y = synth(150, N, D)
+    k, ok = make_kernel("ard", theta), orc.Kern("ard", theta)
+    ov, og = orc.marginal_likelihood(ok, X, Y, D, True, lr.NOISE)
+    ref = lr.objective(ok, X, Y, lr.NOISE, D)
+    lib.check(lib.lib.ibo_set_option(b"fused2_min_nb", 3))
+    try:
+        v, g = marginalLikelihood(k, X, Y, D, True, noise=lr.NOISE)
+        lv, lg, (mu, s2) = looLikelihood(k, X, Y, D, True, noise=lr.NOISE, predictions=True)
+        v2, g2 = marginalLikelihood(k, X, Y, D, True, noise=lr.NOISE)
+        lv2, lg2, (mu2, s22) = looLikelihood(k, X, Y, D, True, noise=lr.NOISE, predictions=True)
+    finally:
+        lib.check(lib.lib.ibo_set_option(b"fused2_min_nb", 104))
+    g, lg, og = np.asarray(g), np.asarray(lg), np.asarray(og)
+    print("nlml: value rel err %.3g  gradient err / max %.3g" % (abs(v - ov) / abs(ov), np.abs(g - og).max() / np.abs(og).max()))
+    print("loo:  value rel err %.3g  gradient err / max %.3g" % (abs(lv - ref["value"]) / abs(ref["value"]),
+                                                                 np.abs(lg - ref["grad"]).max() / np.abs(ref["grad"]).max()))
+    assert abs(v - ov) <= 1e-9 * abs(ov) and np.abs(g - og).max() <= 1e-8 * np.abs(og).max(), (v, ov, g, og)
+    assert abs(lv - ref["value"]) <= 1e-9 * abs(ref["value"]) and np.abs(lg - ref["grad"]).max() <= 1e-8 * np.abs(ref["grad"]).max(), \
+        (lv, ref["value"], lg, ref["grad"])
+    check_points((mu, s2, None), ref, Y, "two-level, 150 rows")
+    assert v2 == v and np.array_equal(np.asarray(g2), g)
+    assert lv2 == lv and np.array_equal(np.asarray(lg2), lg) and np.array_equal(mu2, mu) and np.array_equal(s22, s2)
+
+
 # ---------------------------------------------------------------------------------------------------------------- 5. shared workspace
 def test_loo_and_nlml_share_one_workspace(lib):
     from ibo_amd.gaussianprocess.trainhyper import looLikelihood, marginalLikelihood

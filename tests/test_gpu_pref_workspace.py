@@ -1,5 +1,5 @@
 """
-The preference workspace of ibo_pref_begin belongs to the model it was begun on (csrc/abi_fit.hip, pref_owned): this fit, this number of
+The preference workspace of ibo_pref_begin belongs to the model it was begun on (csrc/abi_pref.hip, pref_owned): this fit, this number of
 rows, this padding.  After ibo_gp_extend, ibo_gp_remove or another fit of the handle, ibo_pref_rinv_mul, ibo_pref_newton_step and
 ibo_pref_finish return IBO_ERR_STATE with the handle and their outputs untouched, until ibo_pref_begin is called again; the reference's
 regulariser loop (ibo_pref_finish again with a larger diag after IBO_ERR_NOT_PD) keeps working.
