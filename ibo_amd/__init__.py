@@ -7,6 +7,7 @@ misterwindupbird/IBO, behind the reference's own Python API.
     from ibo_amd.acquisition import maximizeEI, maximizePI, maximizeUCB, EI, PI, UCB, sweep
     from ibo_amd.acquisition.gallery import fastUCBGallery
     from ibo_amd.acquisition.constrained import Constraint, sweepConstrained, maximizeCEI, ConstrainedEI, feasibleIncumbent
+    from ibo_amd.acquisition.multiobjective import sweepEHVI, maximizeEHVI, ExpectedHypervolumeImprovement, paretoFront, hypervolume
     from ibo_amd.utils.optimize import direct, cdirect
     from ibo_amd.utils.latinhypercube import lhcSample
     from ibo_amd.utils.testfunctions import Hartman6, Shekel5, Synthetic, learnHyper
@@ -29,7 +30,7 @@ def install_as_ego():
     """alias ibo_amd.* as ego.* (drop-in for the reference's import paths)"""
     import importlib
     names = ["", ".gaussianprocess", ".gaussianprocess.kernel", ".gaussianprocess.prior",
-             ".gaussianprocess.trainhyper", ".acquisition", ".acquisition.gallery", ".acquisition.constrained", ".utils",
+             ".gaussianprocess.trainhyper", ".acquisition", ".acquisition.gallery", ".acquisition.constrained", ".acquisition.multiobjective", ".utils",
              ".utils.optimize", ".utils.latinhypercube", ".utils.testfunctions"]
     for n in names:
         sys.modules["ego" + n] = importlib.import_module("ibo_amd" + n)

@@ -16,6 +16,8 @@ plus the batched entry point the GPU makes worthwhile:
 and the knowledge gradient against a reference set (knowledge.py): KnowledgeGradient, sweepKG, maximizeKG, referenceSet.
 The value of a batch -- Monte-Carlo parallel EI with pending points and a greedy batch builder (batch.py): baseSamples, ParallelEI,
 sweepQEI, maximizeQEI, jointQEI, proposeBatch.
+Two objectives -- the expected hypervolume improvement over a Pareto front (multiobjective.py, imported as a submodule like
+constrained.py): sweepEHVI, maximizeEHVI, ExpectedHypervolumeImprovement, paretoFront, hypervolume, observedFront.
 Posterior draws as functions -- Thompson sampling over whole candidate arrays (pathwise.py): PosteriorPaths, spectralDraws.
 
 The default maximize* path is the reference's cdirectGP -> acqmaxGP -> DIRECT

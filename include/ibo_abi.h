@@ -52,7 +52,9 @@ extern "C" {
                              * (pathwise posterior draws: Thompson sampling over whole candidate arrays) and the option "paths_chunk": added within 8,
                              * nothing else changed;
                              * + ibo_qei_sweep, ibo_qei_batch, ibo_qei_direct_max, ibo_qei_stage_ms (Monte-Carlo parallel expected improvement with pending
-                             * points) and the options "qei_chunk", "qei_timing": added within 8, nothing else changed */
+                             * points) and the options "qei_chunk", "qei_timing": added within 8, nothing else changed;
+                             * + ibo_ehvi_sweep, ibo_ehvi_batch, ibo_ehvi_grad_batch, ibo_ehvi_direct_max (the expected hypervolume improvement of two
+                             * objectives over a Pareto front), ibo_ehvi_scan_ms and the options "ehvi_chunk", "ehvi_timing": added within 8, nothing else changed */
 
 /* status codes */
 #define IBO_OK              0
@@ -104,7 +106,7 @@ int         ibo_selftest_mfma(int device, double *max_abs_err);
  * gradients.  DIRECT's small batches and the copies are not event-timed and not in it.  bench.py reports it as gpu_kernel_s_total
  * so that a line can be related to an outside observer's busy-GPU samples. */
 int         ibo_gpu_time_ms(int device, double *ms);
-/* The eighteen option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
+/* The twenty option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
  * Functional:  "legacy_exact" 1/0 -- acqmaxGP in libego's operation order (default) or on the MFMA sweep kernels (see acqmaxGP);
  *   "nlml_batch" B -- matrices per batched factorisation in ibo_nlml_grid (0: as many as 12 GB hold; the values do not depend on it);
  *   "pool_limit_mb" n -- the per-device free list of recycled buffers (ibo_trim);
@@ -122,8 +124,9 @@ int         ibo_gpu_time_ms(int device, double *ms);
  *   the ibo_kg_* entries, 0: by bytes -- identical bits);  "cacq_chunk" m (candidates per chunk of ibo_cacq_sweep, rounded up to 256,
  *   0: by bytes, 2^30 / (16 (ncon + 1)) -- identical bits);  "paths_chunk" m (candidates per launch of the ibo_paths_* entries, rounded up to
  *   256, 0: 2^21 -- identical bits);  "qei_chunk" m (candidates per chunk of the ibo_qei_* entries, rounded up to 256, 0: by bytes --
- *   identical bits).
- * Diagnostic:  "kg_timing" 1/0 (see ibo_kg_stage_ms);  "qei_timing" 1/0 (see ibo_qei_stage_ms).
+ *   identical bits);  "ehvi_chunk" m (candidates per chunk of the ibo_ehvi_* entries, rounded up to 256, 0: by bytes, 2^25 -- identical bits
+ *   among chunks of up to 4096 and among larger ones, see the ibo_ehvi_* entries).
+ * Diagnostic:  "kg_timing" 1/0 (see ibo_kg_stage_ms);  "qei_timing" 1/0 (see ibo_qei_stage_ms);  "ehvi_timing" 1/0 (see ibo_ehvi_scan_ms).
  * Env: IBO_SWEEP_IMPL=gemv|mfma, IBO_DOT_FORM, IBO_POOL_LIMIT_MB, IBO_HOST_THREADS (the legacy symbol's host crew), IBO_DEVICE (legacy symbols),
  *   IBO_NLML_GROUPS=1..4 (sub-batches of an ibo_nlml_grid batch, each on its own stream; 2; the values do not depend on it).
  * Threading (the reference's library keeps its whole model in process-wide statics, cpp/optimizeGP.cpp:36-55,240-259, and is not
@@ -534,6 +537,82 @@ int ibo_cacq_direct_max(ibo_gp_t *obj, int ncon, ibo_gp_t *const *con, const dou
                         int D, const double *lb, const double *ub, int acq, double parm, int erf_mode, double clamp_lo, double ymax,
                         int maxiter, int maxtime, int maxsample, int compat,
                         double *opt, double *optx, int64_t *nsamples);
+
+/* ---------------------------------------------------------------- expected hypervolume improvement (two objectives) */
+/*
+ * Two objectives, each known through its own fitted handle obj[0], obj[1] (a handle may be both; a preference GP may be either), both to
+ * be MAXIMISED, assumed independent; a reference point ref = (r1, r2); a front: nfront points (front_host, nfront x 2 row-major, host
+ * memory) in objective space.  The acquisition is the expected growth of the hypervolume the front dominates above ref after one
+ * observation of both objectives at x (Emmerich et al. 2006; Yang et al. 2019) -- in closed form.  The reference has no counterpart: its
+ * acquisitions (ego/acquisition/__init__.py) rank candidates for one objective only.
+ *
+ * The front's canonical form (made on the host by every entry): points not strictly above ref in BOTH coordinates go, then dominated
+ * points and duplicates; the rest sorted ascending in the first coordinate, (a_1, b_1) .. (a_n, b_n) -- b is then strictly descending --
+ * with a_0 = r1, a_{n+1} = +inf, b_{n+1} = r2.  n <= IBO_EHVI_MAX_FRONT after that (nfront itself is not limited).
+ * With (mu_k, s2_k) what ibo_acq_sweep returns for obj[k] with IBO_ACQ_NONE at the call's clamp_lo, sigma_k = sqrt(s2_k):
+ *   psi_k(t) = sigma_k phi(u) + (mu_k - t) Phi(u),  u = (mu_k - t) / sigma_k        (EI over t with parm 0; psi_1(+inf) = 0, never evaluated)
+ *   d_i      = psi_1(a_i) - psi_1(a_{i+1}), and 0 where that is negative              i = 0 .. n
+ *   EHVI(x)  = sum_i d_i psi_2(b_{i+1})                                              i ascending, plain fp64, no fused multiply-add
+ * (the improvement split into the n + 1 vertical strips between neighbouring a's; an empty front: EI_1(r1) EI_2(r2)).  Phi and phi in the
+ * call's erf_mode.  A NaN (a NaN candidate coordinate) stays a NaN and never wins the arg-max.
+ * Every entry computes a candidate's value the same way: the two plain sweeps into device scratch, then one kernel (ehvi.hip) with one
+ * candidate per lane that walks the strips in order.  The kernel adds nothing of its own to the bits: they are a function of the
+ * candidate's (mu_k, s2_k) and the canonical front.  ibo_acq_sweep picks its kernels by the size of the launch, and its routes agree with
+ * each other to rounding only; so a short launch is padded here (candidates at the origin, nobody reads their results) to the size class of
+ * the call's chunk -- min(M, the chunk): up to 4096 the small-batch kernels (launches of up to 128 candidates run as 160), above that the
+ * large-batch kernel (a tail of up to 4096 runs as 4097).  Within a class the sweep, a host batch, the gradient entry's value and the value
+ * DIRECT reports agree bit for bit, whatever M, the candidate's place and "ehvi_chunk" are; between the classes, and for a model whose
+ * inputs keep it off the dot form, to rounding.
+ *
+ * Errors, all four entries, in this order: IBO_ERR_NO_DEVICE without a device; IBO_ERR_ARG for a NULL obj, obj[0] or obj[1], handles on
+ * different devices, nfront < 0, a NULL front_host with nfront > 0, a NULL ref, M < 1, a NULL point array, an unknown erf_mode, every
+ * output NULL, a non-finite ref, a NaN or an infinity in front_host, more than IBO_EHVI_MAX_FRONT points left after canonicalisation;
+ * IBO_ERR_STATE if a handle is not fitted; IBO_ERR_ARG if the handles differ in D.
+ */
+#define IBO_EHVI_MAX_FRONT 1024
+
+/*
+ * The sweep: cand_dev (M x D, DEVICE) and the exclusion balls, index_base and arg-max rule of ibo_acq_sweep -- NaN values and excluded
+ * candidates never win, the largest value wins, the lowest index wins ties, best_idx = -1 and best_val = -inf when nothing is admissible.
+ * val_dev: optional DEVICE output, M doubles.  Cost: the two plain sweeps plus 2 (n + 1) Gaussian cdf / pdf pairs per candidate; 32 bytes
+ * of device scratch per candidate, at most 1 GiB (more candidates run in chunks), returned before the call returns.  Blocking.
+ */
+int ibo_ehvi_sweep(ibo_gp_t *const *obj, int nfront, const double *front_host, const double *ref,
+                   int64_t M, const double *cand_dev, int erf_mode, double clamp_lo,
+                   int n_excl, const double *excl_host, double excl_radius, int64_t index_base,
+                   double *val_dev, double *best_val, int64_t *best_idx);
+
+/* The same values for points on the HOST (Q_host: M x D) into val_host: the points are uploaded and go through the sweep's route. */
+int ibo_ehvi_batch(ibo_gp_t *const *obj, int nfront, const double *front_host, const double *ref,
+                   int64_t M, const double *Q_host, int erf_mode, double clamp_lo, double *val_host);
+
+/*
+ * ibo_ehvi_batch's value (val_host, bit for bit) and its gradient with respect to the query point (grad_host: M x D row-major).  The
+ * kernel's second variant also sums, over the strips in the same order,
+ *   G_mu1 = sum (Phi(u_1,i) - Phi(u_1,i+1)) psi_2(b_{i+1})      G_sigma1 = sum (phi(u_1,i) - phi(u_1,i+1)) psi_2(b_{i+1})     (0 where d_i was clamped)
+ *   G_mu2 = sum d_i Phi(u_2,i+1)                                G_sigma2 = sum d_i phi(u_2,i+1)
+ * and the host applies the chain rule to ibo_acq_grad_batch's (dmu_k, ds2_k) per handle, k = 0 then 1:
+ *   grad EHVI = sum_k G_mu_k dmu_k + G_sigma_k ds2_k / (2 sigma_k)                  (ds2_k is 0 where handle k's clip is active)
+ * Either output may be NULL, not both.  The analytic gradient: with IBO_ERF_NR it differs from the derivative of the returned values by
+ * about 1e-6 relative (see ibo_acq_grad_batch).
+ */
+int ibo_ehvi_grad_batch(ibo_gp_t *const *obj, int nfront, const double *front_host, const double *ref,
+                        int64_t M, const double *Q_host, int erf_mode, double clamp_lo, double *val_host, double *grad_host);
+
+/*
+ * ibo_direct_max on EHVI: the same DIRECT, options and batched schedule, every batch of sample points evaluated as ibo_ehvi_batch does.
+ * opt = the maximum, optx[D] its location, nsamples optional (not all three NULL).  IBO_ERR_ARG also for NULL bounds or D other than
+ * the models'.
+ */
+int ibo_ehvi_direct_max(ibo_gp_t *const *obj, int nfront, const double *front_host, const double *ref,
+                        int D, const double *lb, const double *ub, int erf_mode, double clamp_lo,
+                        int maxiter, int maxtime, int maxsample, int compat,
+                        double *opt, double *optx, int64_t *nsamples);
+
+/* With ibo_set_option("ehvi_timing", 1) every ibo_ehvi_* call of this thread waits after each launch of the scan kernel and adds its
+ * device time (HIP events around that launch alone, not the per-model sweeps) to *ms.  reset != 0 clears the sum after it is read; ms may
+ * be NULL.  A diagnostic: the option is process-wide, the sum is per thread. */
+int ibo_ehvi_scan_ms(double *ms, int reset);
 
 /* ---------------------------------------------------------------- knowledge gradient */
 /*
