@@ -18,7 +18,8 @@ The value of a batch -- Monte-Carlo parallel EI with pending points and a greedy
 sweepQEI, maximizeQEI, jointQEI, proposeBatch.
 Two objectives -- the expected hypervolume improvement over a Pareto front (multiobjective.py, imported as a submodule like
 constrained.py): sweepEHVI, maximizeEHVI, ExpectedHypervolumeImprovement, paretoFront, hypervolume, observedFront.
-Posterior draws as functions -- Thompson sampling over whole candidate arrays (pathwise.py): PosteriorPaths, spectralDraws.
+Posterior draws as functions -- Thompson sampling over whole candidate arrays (pathwise.py): PosteriorPaths, spectralDraws;
+with .gradient / .negf_grad (ibo_paths_grad_batch), .maximize(polish=True) and .maxima, every path's maximum by a lock-step ascent.
 
 The default maximize* path is the reference's cdirectGP -> acqmaxGP -> DIRECT
 (ego/acquisition/__init__.py:307-447, cpp/optimizeGP.cpp:262-349) with the tree

@@ -16,7 +16,7 @@ sampling -- each member is the arg-max of one joint posterior draw over a candid
 set (GaussianProcess.sample_posterior), under the same distance rule.
 
 thompsonSweepGallery: the same walk over the arg-maxes of pathwise draws (pathwise.PosteriorPaths), swept once over a candidate
-array of any length -- sample_posterior stops at 16384 points.
+array of any length -- sample_posterior stops at 16384 points; polish=True refines every arg-max on its path's exact gradient first.
 """
 from copy import deepcopy
 
@@ -176,22 +176,36 @@ def thompsonGallery(GP, candidates, N, seed=None, draws=None, noise=True):
     return gallery
 
 
-def thompsonSweepGallery(GP, candidates, N, seed=None, paths=None, n_features=2048):
+def thompsonSweepGallery(GP, candidates, N, seed=None, paths=None, n_features=2048, polish=False, bounds=None):
     """thompsonGallery for candidate arrays of any length: `paths` (default 8 N, at most 256) pathwise posterior draws
     (PosteriorPaths(GP, paths, n_features, seed)) are swept ONCE over the candidates -- an (M, D) ndarray or a _lib.DeviceArray
     already in HBM -- and their arg-maxes are walked in order exactly as thompsonGallery walks its draws: a path's first maximiser
     (NaN never wins) joins the gallery when it is farther than MIN_SEPARATION from every member.  Returns a list of candidate rows,
-    shorter than N only when the paths run out first.  The draws are of the latent function (thompsonGallery's noise=False)."""
+    shorter than N only when the paths run out first.  The draws are of the latent function (thompsonGallery's noise=False).
+    polish=True (needs `bounds`): every arg-max is first ascended on its path's exact gradient inside the box
+    (PosteriorPaths.maxima), so the members are the paths' maximisers and no longer rows of the candidate array."""
     from .pathwise import PosteriorPaths, MAX_PATHS
+    if polish and bounds is None:
+        raise ValueError("polish=True needs the box to ascend in: bounds")
     paths = min(8 * int(N), MAX_PATHS) if paths is None else int(paths)
     dev = isinstance(candidates, _lib.DeviceArray)
     C = candidates if dev else np.atleast_2d(np.asarray(candidates, dtype=float))
     P = PosteriorPaths(GP, n_paths=paths, n_features=n_features, seed=seed)
     try:
-        idx = P.sweep(C)["best_idx"]
+        if polish:
+            vals, X = P.maxima(bounds, candidates=C, polish=True)
+        else:
+            idx = P.sweep(C)["best_idx"]
     finally:
         P.close()
     gallery = []
+    if polish:
+        for v, x in zip(vals, X):
+            if len(gallery) >= N:
+                break
+            if np.isfinite(v) and _separated(x, gallery):
+                gallery.append(np.array(x))
+        return gallery
     for k in idx:
         if len(gallery) >= N:
             break

@@ -10,6 +10,9 @@ index_base, or handed to DIRECT.  The reference has nothing like it.
 
     spectralDraws(kernel, D, n_features, n_paths, N, eps_var, seed) -> (omega, phase, w, eps)
     PosteriorPaths(GP, n_paths=8, n_features=2048, seed=None)   .values(X) .sweep(candidates) .maximize(bounds, path) .coef() .close()
+        .gradient(X, paths=None) -> (values, gradients)   .negf_grad(x, path) -> (-value, -gradient)   (ibo_paths_grad_batch)
+        .maximize(..., polish=True): a bounded L-BFGS-B finish from DIRECT's point on the exact gradient
+        .maxima(bounds, candidates=None, polish=True) -> (vals (S,), X (S, D)): every path's maximum, ascended in lock-step
 
 Conventions of the Python classes: k and k* with the kernel's own sf2; mu is GP.posterior's mean, the mean prior included.  The
 paths are draws of the LATENT function (sample_posterior(noise=False)); their covariance matches posterior_cov(noise=False) off the
@@ -17,7 +20,7 @@ diagonal and sf2 - |v|^2 on it, with an error of the random features that falls 
 is a snapshot on the device: it stays what it is when the model gets more data, loses some or is deleted.  A value is the same bits
 from values, sweep and maximize.  Everything is computed by libibo_hip (ibo_paths_*).
 
-Not provided: gradients with respect to x, exclusion balls, PrefGaussianProcess and models with an augmented factor
+Not provided: exclusion balls, PrefGaussianProcess and models with an augmented factor
 (NotImplementedError: the matrix they were factored from differs from K by more than a diagonal).
 """
 import ctypes
@@ -25,9 +28,11 @@ import ctypes
 import numpy as np
 
 from .. import _lib
+from ..utils.latinhypercube import lhcSample
 
 MAX_PATHS = 256           # IBO_PATHS_MAX_PATHS
 MAX_FEATURES = 16384      # IBO_PATHS_MAX_FEATURES
+MAXIMA_CANDIDATES = 4096  # maxima's default starts: the arg-maxes of a sweep over this many latin-hypercube points
 
 
 def spectralDraws(kernel, D, n_features, n_paths, N, eps_var, seed=None):
@@ -82,6 +87,7 @@ class PosteriorPaths(object):
             raise ValueError("1 + noise - sf2 = %g < 0: the model's diagonal is below its kernel's, no path has this posterior" % eps_var)
         self.omega, self.phase, self.w, self.eps = spectralDraws(GP.kernel, D, n_features, n_paths, N, eps_var, seed)
         self.S, self.F, self.N, self.D = int(n_paths), int(n_features), N, D
+        self.seed = seed
         self.device = GP._dev.device if GP._dev is not None else _lib.default_device()
         GP._push_prior()
         h = ctypes.c_void_p()
@@ -125,18 +131,128 @@ class PosteriorPaths(object):
             res["values"] = vals.to_host()
         return res
 
-    def maximize(self, bounds, path=0, maxiter=50, maxtime=30, maxsample=10000, compat=False):
-        """Maximise one path over the box `bounds` with DIRECT on the GPU objective (ibo_paths_direct_max) -> (opt, optx);
-        opt is values(optx)[path], bit for bit."""
+    def gradient(self, X, paths=None):
+        """values and gradients with respect to x at the points X ((M, D), or (D,) for one point), one ibo_paths_grad_batch call:
+        (S, M) and (S, M, D) for every path, or -- with `paths` an int array of length M -- (M,) and (M, D): path paths[i] at point i.
+        The values are values(X)'s, bit for bit."""
+        Q = self._points(X, "X")
+        M = len(Q)
+        if paths is None:
+            po, val, grad = None, np.empty((self.S, M)), np.empty((self.S, M, self.D))
+        else:
+            po = np.ascontiguousarray(np.asarray(paths).reshape(-1), dtype=np.intc)
+            if len(po) != M or not np.array_equal(po, np.asarray(paths).reshape(-1)):
+                raise ValueError("paths must be %d integers, one per point" % M)
+            if np.any(po < 0) or np.any(po >= self.S):
+                raise ValueError("a path outside [0, %d)" % self.S)
+            val, grad = np.empty(M), np.empty((M, self.D))
+        _lib.check(_lib.lib.ibo_paths_grad_batch(self._handle(), M, _lib.dp(Q), None if po is None else po.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                 _lib.dp(val), _lib.dp(grad)))
+        return val, grad
+
+    def negf_grad(self, x, path=0):
+        """(-value, -gradient) of one path at one point, for scipy.optimize.minimize(jac=True)"""
+        if not 0 <= int(path) < self.S:
+            raise ValueError("path %r outside [0, %d)" % (path, self.S))
+        v, g = self.gradient(np.asarray(x, dtype=float).reshape(1, self.D), paths=[int(path)])
+        return -v[0], -g[0]
+
+    def _box(self, bounds):
         lb = _lib.f64([b[0] for b in bounds]); ub = _lib.f64([b[1] for b in bounds])
         if len(lb) != self.D:
             raise ValueError("bounds have %d dimensions, the paths have %d" % (len(lb), self.D))
+        return lb, ub
+
+    def maximize(self, bounds, path=0, maxiter=50, maxtime=30, maxsample=10000, compat=False, polish=False):
+        """Maximise one path over the box `bounds` with DIRECT on the GPU objective (ibo_paths_direct_max) -> (opt, optx);
+        opt is values(optx)[path], bit for bit.  polish=True: bounded L-BFGS-B from DIRECT's point on negf_grad, at most
+        POLISH_MAXITER iterations; the end point is re-evaluated with values and kept only when strictly better."""
+        lb, ub = self._box(bounds)
         if not 0 <= int(path) < self.S:
             raise ValueError("path %r outside [0, %d)" % (path, self.S))
         opt = ctypes.c_double(); optx = np.empty(self.D); ns = ctypes.c_int64()
         _lib.check(_lib.lib.ibo_paths_direct_max(self._handle(), int(path), self.D, _lib.dp(lb), _lib.dp(ub), int(maxiter), int(maxtime),
                                                  int(maxsample), 1 if compat else 0, ctypes.byref(opt), _lib.dp(optx), ctypes.byref(ns)))
+        if not polish:
+            return opt.value, optx
+        from scipy.optimize import minimize
+        from . import POLISH_MAXITER
+        res = minimize(lambda x: self.negf_grad(np.clip(x, lb, ub), path), np.clip(optx, lb, ub), jac=True, method='L-BFGS-B',
+                       bounds=list(zip(lb, ub)), options=dict(maxiter=POLISH_MAXITER, ftol=1e-15, gtol=1e-12))
+        x = _lib.f64(np.clip(res.x, lb, ub))
+        val = self.values(x)[int(path), 0]
+        if val > opt.value:
+            return float(val), x
         return opt.value, optx
+
+    def _ascend(self, X0, bounds):
+        """Every path s ascended from its own start X0[s] inside the box, all S in lock-step: projected gradient steps with a
+        Barzilai-Borwein length and backtracking, each iteration ONE ibo_paths_grad_batch call on the S trial points (path s at
+        point s), at most POLISH_MAXITER of them.  A trial point is accepted when its value is strictly greater; a path whose
+        step is refused halves it.  Returns (vals (S,), X (S, D)).  The end point is re-evaluated with values and replaces the
+        start only when it is strictly better and its projected gradient is not larger than the start's; a start that is not finite
+        stays as it is, with the value NaN."""
+        from . import POLISH_MAXITER
+        lb, ub = self._box(bounds)
+        X0 = _lib.f64(np.asarray(X0, dtype=float).reshape(self.S, self.D))
+        own = np.arange(self.S)
+        live = np.all(np.isfinite(X0), axis=1)
+        x = np.where(live[:, None], np.clip(X0, lb, ub), lb[None, :])             # (a dead path rides along at a corner, unread)
+
+        def projected(x, g):                                                      # the gradient without what points out of the box
+            return np.where(((x <= lb) & (g < 0)) | ((x >= ub) & (g > 0)), 0.0, g)
+
+        f, g = self.gradient(x, paths=own)
+        live &= np.isfinite(f) & np.all(np.isfinite(g), axis=1)
+        g = np.where(live[:, None], g, 0.0)                                       # (a dead path does not move)
+        x0, f0, pg0 = x.copy(), f.copy(), np.linalg.norm(projected(x, g), axis=1)
+        diag = float(np.linalg.norm(ub - lb))
+
+        def capped(step, g):                                                      # no step longer than the box
+            gn = np.linalg.norm(g, axis=1)
+            return np.where(gn > 0, np.minimum(step, diag / np.where(gn > 0, gn, 1.0)), 0.0)
+
+        step = capped(np.full(self.S, np.inf), g) * .05                           # a first move of 5% of the box's diagonal
+        for _ in range(POLISH_MAXITER - 1):
+            xt = np.clip(x + step[:, None] * g, lb, ub)
+            ft, gt = self.gradient(xt, paths=own)
+            ok = live & (ft > f) & np.all(np.isfinite(gt), axis=1)
+            dx, dg = xt - x, gt - g
+            sy = -np.sum(dx * dg, axis=1)                                         # (> 0 where the path is concave along the step)
+            bb = np.where(sy > 0, np.sum(dx * dx, axis=1) / np.where(sy > 0, sy, 1.0), 2.0 * step)
+            x = np.where(ok[:, None], xt, x); f = np.where(ok, ft, f); g = np.where(ok[:, None], gt, g)
+            step = capped(np.where(ok, bb, .5 * step), g)
+        x = _lib.f64(x)
+        val = self.values(x)[own, own]
+        pg = np.linalg.norm(projected(x, g), axis=1)
+        keep = live & (val > f0) & (pg <= pg0)
+        dead = ~np.all(np.isfinite(X0), axis=1)
+        X = np.where(keep[:, None], x, np.where(dead[:, None], X0, x0))
+        return np.where(keep, val, np.where(dead, np.nan, f0)), X
+
+    def maxima(self, bounds, candidates=None, polish=True):
+        """(vals (S,), X (S, D)): every path's maximum over the box.  The starts are the per-path arg-maxes of one sweep over
+        `candidates` (an (M, D) ndarray or a _lib.DeviceArray; default: a seeded latin hypercube of MAXIMA_CANDIDATES points in
+        `bounds`); polish=True ascends all S from there in lock-step (_ascend).  vals[s] is values(X[s])[s], bit for bit, and never
+        below the sweep's; a path whose sweep had no finite value returns (-inf, a row of NaN)."""
+        lb, ub = self._box(bounds)
+        if candidates is None:
+            candidates = np.array(lhcSample([list(b) for b in zip(lb, ub)], MAXIMA_CANDIDATES, seed=0 if self.seed is None else self.seed))
+        dev = isinstance(candidates, _lib.DeviceArray)
+        C = candidates if dev else self._points(candidates, "candidates")
+        r = self.sweep(C)
+        vals, X = np.array(r["best_val"]), np.full((self.S, self.D), np.nan)
+        for s, k in enumerate(r["best_idx"]):
+            if k >= 0:
+                X[s] = C.view_rows(int(k), int(k) + 1).to_host()[0] if dev else C[int(k)]
+            else:
+                vals[s] = -np.inf
+        if not polish or not np.any(r["best_idx"] >= 0):
+            return vals, X
+        pv, pX = self._ascend(X, bounds)
+        found = r["best_idx"] >= 0
+        better = found & (pv > vals)
+        return np.where(better, pv, vals), np.where(better[:, None], pX, X)
 
     def coef(self):
         """(S, F + N): per path the feature weights w_s, then the kernel weights c_s, as the device holds them"""

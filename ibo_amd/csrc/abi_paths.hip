@@ -1,4 +1,4 @@
-// abi_paths.hip -- pathwise posterior draws behind the C ABI: ibo_paths_create / destroy / info / coef / sweep / batch / direct_max
+// abi_paths.hip -- pathwise posterior draws behind the C ABI: ibo_paths_create / destroy / info / coef / sweep / batch / grad_batch / direct_max
 // (kernels: paths.hip; V = U W^T by cov.hip's triangular launcher).
 //
 // A path object is a SNAPSHOT on the device: the model's rows, kernel parameters, prior arrays, the spectral draws and the coefficient
@@ -19,6 +19,8 @@ struct ibo_paths {
     DevBuf<double> X, omega, phase, coef, pmeans, pbeta, plowerb, pwidth;
     DevBuf<double> cand, vals, pv, resv;              // scratch of the evaluation entries, kept between calls (DIRECT's many batches)
     DevBuf<int64_t> pi, resi;
+    DevBuf<double> grad, pick;                        // ibo_paths_grad_batch: a chunk's gradients, its values picked by path_of
+    DevBuf<int> pof;
 };
 
 namespace {
@@ -30,6 +32,7 @@ void paths_free(ibo_paths *p)
     g_pool_quiet = true;
     p->X.release(); p->omega.release(); p->phase.release(); p->coef.release(); p->pmeans.release(); p->pbeta.release(); p->plowerb.release();
     p->pwidth.release(); p->cand.release(); p->vals.release(); p->pv.release(); p->resv.release(); p->pi.release(); p->resi.release();
+    p->grad.release(); p->pick.release(); p->pof.release();
     g_pool_quiet = false;
     if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
@@ -212,6 +215,49 @@ extern "C" int ibo_paths_batch(ibo_paths_t *p, int64_t M, const double *Q_host, 
     if (!p || !Q_host || !values_host) return fail(IBO_ERR_ARG, "NULL argument");
     if (M < 1) return fail(IBO_ERR_ARG, "M=%lld", (long long)M);
     return paths_eval_host(p, M, Q_host, -1, values_host);
+}
+
+extern "C" int ibo_paths_grad_batch(ibo_paths_t *p, int64_t M, const double *Q_host, const int *path_of, double *values_host,
+                                    double *grads_host)
+{
+    IBO_TRY(use_device(p ? p->device : 0));
+    if (!p || !Q_host || !grads_host) return fail(IBO_ERR_ARG, "NULL argument");
+    if (M < 1) return fail(IBO_ERR_ARG, "M=%lld", (long long)M);
+    if (path_of)
+        for (int64_t i = 0; i < M; i++)
+            if (path_of[i] < 0 || path_of[i] >= p->S) return fail(IBO_ERR_ARG, "path_of[%lld]=%d outside [0, %d)", (long long)i, path_of[i], p->S);
+    const size_t D = (size_t)p->D, S = (size_t)p->S, rows = path_of ? 1 : S;
+    // pieces by bytes (2^24 doubles of values and gradients) and by "paths_chunk": a point's bits do not depend on its piece
+    const int64_t mb = std::min<int64_t>(std::min(M, paths_chunk_len()), std::max<int64_t>(256, ((int64_t)1 << 24) / (int64_t)(S * (D + 1))));
+    IBO_TRY(p->cand.ensure((size_t)mb * D)); IBO_TRY(p->grad.ensure(rows * (size_t)mb * D));
+    if (values_host) IBO_TRY(p->vals.ensure(S * (size_t)mb));
+    if (path_of) { IBO_TRY(p->pof.ensure((size_t)mb)); if (values_host) IBO_TRY(p->pick.ensure((size_t)mb)); }
+    for (int64_t c0 = 0; c0 < M; c0 += mb) {
+        const int64_t m = std::min(M - c0, mb);
+        HIP_TRY(hipMemcpyAsync(p->cand.p, Q_host + (size_t)c0 * D, sizeof(double) * (size_t)m * D, hipMemcpyHostToDevice, p->stream));
+        if (path_of) HIP_TRY(hipMemcpyAsync(p->pof.p, path_of + c0, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, p->stream));
+        PathsGradArgs ga;
+        ga.a = paths_args(p);
+        if (values_host) {                            // paths_tile_kernel itself: the bits of ibo_paths_batch
+            PathsArgs a = ga.a;
+            a.values = p->vals.p; a.ldv = (size_t)mb;
+            IBO_TRY(paths_run(p, a, m, p->cand.p));
+            if (path_of) {
+                KERNEL_TRY(launch_paths_pick(p->vals.p, (size_t)mb, p->pof.p, (int)m, p->pick.p, p->stream));
+                HIP_TRY(hipMemcpyAsync(values_host + c0, p->pick.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, p->stream));
+            } else {
+                HIP_TRY(hipMemcpy2DAsync(values_host + c0, sizeof(double) * (size_t)M, p->vals.p, sizeof(double) * (size_t)mb,
+                                         sizeof(double) * (size_t)m, S, hipMemcpyDeviceToHost, p->stream));
+            }
+        }
+        ga.a.cand = p->cand.p; ga.a.m = (int)m;
+        ga.path_of = path_of ? p->pof.p : nullptr; ga.grads = p->grad.p; ga.ldg = (size_t)mb; ga.goff = 0;
+        KERNEL_TRY(launch_paths_grad_tile(ga, p->stream));
+        HIP_TRY(hipMemcpy2DAsync(grads_host + (size_t)c0 * D, sizeof(double) * (size_t)M * D, p->grad.p, sizeof(double) * (size_t)mb * D,
+                                 sizeof(double) * (size_t)m * D, rows, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+    }
+    return IBO_OK;
 }
 
 extern "C" int ibo_paths_direct_max(ibo_paths_t *p, int path, int D, const double *lb, const double *ub, int maxiter, int maxtime,

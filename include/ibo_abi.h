@@ -54,7 +54,9 @@ extern "C" {
                              * + ibo_qei_sweep, ibo_qei_batch, ibo_qei_direct_max, ibo_qei_stage_ms (Monte-Carlo parallel expected improvement with pending
                              * points) and the options "qei_chunk", "qei_timing": added within 8, nothing else changed;
                              * + ibo_ehvi_sweep, ibo_ehvi_batch, ibo_ehvi_grad_batch, ibo_ehvi_direct_max (the expected hypervolume improvement of two
-                             * objectives over a Pareto front), ibo_ehvi_scan_ms and the options "ehvi_chunk", "ehvi_timing": added within 8, nothing else changed */
+                             * objectives over a Pareto front), ibo_ehvi_scan_ms and the options "ehvi_chunk", "ehvi_timing": added within 8, nothing else changed;
+                             * + ibo_paths_grad_batch (values and gradients of the pathwise draws with respect to x; "paths_chunk" bounds its pieces too):
+                             * added within 8, nothing else changed */
 
 /* status codes */
 #define IBO_OK              0
@@ -764,7 +766,13 @@ int ibo_qei_stage_ms(double *ms, int reset);
  * Cost: creation N^2 S + 2 N F S; evaluation 2 (Fp + Np32) Sp flops per candidate on the fp64 MFMA pipe plus about 10 D + 45 vector
  * instructions per (candidate, feature) and 3 D + 40 per (candidate, model row), generated once per tile of 64 (63 with a mean prior)
  * paths.  Device memory: (Fp + Np32) x Sp doubles of coefficients (Fp, Np32: F, N rounded up to 32; Sp: 64 per tile of paths).
- * Not provided: gradients with respect to x, exclusion balls, preference / augmented models (A - K is not diagonal there), the RCCL
+ * Gradients (ibo_paths_grad_batch): d path_s / dx_d = sum_j -amp sin(omega_j . x + b_j) omega_jd w_sj + sum_i h_i w_d (x_d - X_id) c_si
+ * (h_i as ibo_acq_grad_batch's: -k, -3 sf2 e^-r, -(5/3) sf2 (1 + r) e^-r; finite at r = 0), with a mean prior dm_d (1 - k*.a1) + g_sd -
+ * m d(k*.a1)/dx_d.  The derivative of the generated piece is generated the same way and contracted with the same coefficients, one
+ * accumulator per (point, path, d) in the values' k order: a gradient's bits depend on the object and the point alone, not on M, the
+ * point's place, the pieces a call is cut into, nor on path_of.  A NaN coordinate gives NaN gradients for that point only.  Cost per
+ * point: the factor (sine or h_i) once per k, then per dimension one multiplication per k and the values' 2 (Fp + Np32) Sp flops.
+ * Not provided: exclusion balls, preference / augmented models (A - K is not diagonal there), the RCCL
  * exchange.
  * IBO_ERR_NO_DEVICE without a device (checked first); IBO_ERR_ARG for NULLs, sizes outside the limits, M < 1, every output NULL,
  * `path` out of range or D other than the object's; IBO_ERR_STATE for an unfitted handle (or one fitted from libego's inverse).
@@ -786,6 +794,11 @@ int ibo_paths_sweep(ibo_paths_t *p, int64_t M, const double *cand_dev, int64_t i
                     double *values_dev, double *best_val, int64_t *best_idx);
 /* M host points: values_host (S x M path-major) */
 int ibo_paths_batch(ibo_paths_t *p, int64_t M, const double *Q_host, double *values_host);
+/* M host points: values (optional) and gradients with respect to x.  path_of optional (M ints, each in [0, S)):
+ *   path_of == NULL: values_host S x M path-major,     grads_host S x M x D
+ *   path_of != NULL: values_host M (path path_of[i] at point i), grads_host M x D
+ * The values are ibo_paths_batch's, bit for bit.  IBO_ERR_ARG for M < 1, a NULL Q_host or grads_host, or a path index out of range. */
+int ibo_paths_grad_batch(ibo_paths_t *p, int64_t M, const double *Q_host, const int *path_of, double *values_host, double *grads_host);
 /* ibo_direct_max on ONE path: the same DIRECT, options and batched schedule; every batch evaluated as ibo_paths_batch evaluates that
  * path.  opt = the maximum, optx[D] its location, nsamples optional (not all three NULL). */
 int ibo_paths_direct_max(ibo_paths_t *p, int path, int D, const double *lb, const double *ub, int maxiter, int maxtime,
