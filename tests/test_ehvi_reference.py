@@ -131,6 +131,28 @@ def cdf_pdf_long(erf_mode, z):
     return L(.5) * (1 + np.where(x >= 0, ans, -ans)), np.exp(-(z * z / 2)) * L(0.398942)
 
 
+def sum_long(mu1, s21, mu2, s22, front, ref, erf_mode):
+    """er.from_posterior's value with the strips summed in 80-bit arithmetic from the same float64 (mu, s2, front)"""
+    L = np.longdouble
+    a, b = er.canonical(front, ref)
+    n, M = len(a), len(mu1)
+    sig1, sig2 = np.sqrt(s21).astype(L), np.sqrt(s22).astype(L)          # (the float64 sigmas: the kernel's inputs to the walk)
+
+    def psi(mu, sig, t):
+        dm = mu.astype(L) - L(t)
+        cdf, pdf = cdf_pdf_long(erf_mode, dm / sig)
+        return sig * pdf + dm * cdf
+
+    prev = psi(mu1, sig1, ref[0])
+    val = np.zeros(M, dtype=L)
+    for i in range(n + 1):
+        nxt = psi(mu1, sig1, a[i]) if i < n else np.zeros(M, dtype=L)
+        d = prev - nxt
+        val = val + np.where(d < 0, 0, d) * psi(mu2, sig2, b[i] if i < n else ref[1])
+        prev = nxt
+    return val
+
+
 @pytest.mark.parametrize("erf_mode", ERFS)
 @pytest.mark.parametrize("n", [0, 2, 7, 65])
 def test_the_sum_in_long_double(erf_mode, n):
@@ -145,20 +167,7 @@ def test_the_sum_in_long_double(erf_mode, n):
     mu1, mu2 = REF[0] + rs.rand(M) * 2 - .3, REF[1] + rs.rand(M) * 2 - .3
     s21, s22 = rs.rand(M) * .3 + 1e-3, rs.rand(M) * .3 + 1e-3
     r = er.from_posterior(mu1, s21, mu2, s22, F, REF, erf_mode)
-    sig1, sig2 = np.sqrt(s21).astype(L), np.sqrt(s22).astype(L)          # (the float64 sigmas: the kernel's inputs to the walk)
-
-    def psi(mu, sig, t):
-        dm = mu.astype(L) - L(t)
-        cdf, pdf = cdf_pdf_long(erf_mode, dm / sig)
-        return sig * pdf + dm * cdf
-
-    prev = psi(mu1, sig1, REF[0])
-    val = np.zeros(M, dtype=L)
-    for i in range(n + 1):
-        nxt = psi(mu1, sig1, a[i]) if i < n else np.zeros(M, dtype=L)
-        d = prev - nxt
-        val = val + np.where(d < 0, 0, d) * psi(mu2, sig2, b[i] if i < n else REF[1])
-        prev = nxt
+    val = sum_long(mu1, s21, mu2, s22, F, REF, erf_mode)
     err = np.abs(r["val"].astype(L) - val).astype(float)
     print("n=%d erf=%d: worst |err| / S = %.2e" % (n, erf_mode, np.max(err / r["S"])))
     assert np.all(err <= 1e-12 * r["S"])

@@ -352,3 +352,98 @@ def test_reference_cannot_factor_and_neither_can_the_product(ibo, capsys):
     with pytest.raises(np.linalg.LinAlgError):
         GP.addPreferences(prefs)
     assert capsys.readouterr().out.count("adding regularizer") == 11
+
+
+def test_newer_acquisitions_across_an_observation_point_and_more_preferences(ibo):
+    """One preference model through addPreferences -> addObservationPoint -> addPreferences, with the knowledge gradient, q-EI and the
+    constrained sweep read at every stage.  A preference GP is no plain fit (its factor is that of R + C^-1), so it stays out of
+    tests/test_gpu_acquisition_sequences.py; what holds for it is what the families' own files pin on an unchanged model:
+      after addPreferences   KG and q-EI are the compositions of their own pieces (1e-12 of scale), their means and variances the
+                             posterior's (1e-6 / 1e-9); the constrained sweep is the composition of the library's own per-model sweeps
+                             (rtol 1e-12, atol 1e-15), its arg-max the first maximiser of its values
+      after addObservationPoint   the classes refuse (ValueError: covariances from one factor, means from another) -- objects made before
+                             the call and new ones; the handle itself is untouched: the raw entries return the bits they returned before
+                             and are again the compositions of their pieces, the variance that of ibo_posterior_batch on the handle;
+                             the constrained sweep, which reads the handle as sweep() does, returns its earlier bits as well
+      after more preferences (new points: the model is refactored, the augmented factor dropped) the objects made at the start work
+                             again, follow the model, and every check of the first stage holds on the new model."""
+    import kg_reference as kr
+    import qei_reference as qr
+    from ibo_amd import DeviceArray, _lib
+    from ibo_amd.acquisition import KnowledgeGradient, ParallelEI, sweep
+    from ibo_amd.acquisition.constrained import Constraint, sweepConstrained
+    from ibo_amd.gaussianprocess import PrefGaussianProcess
+    from conftest import synth
+    from test_gpu_constrained import compose, own_close, pair
+    from test_gpu_knowledge_gradient import kg_call
+    from test_gpu_qei import compose_close, qei_call
+    rs = np.random.RandomState(3)
+    D = 4
+    pts = rs.rand(60, D)
+    f = lambda x: -np.sum((x - .4) ** 2)
+    prefs = [(pts[2 * i], pts[2 * i + 1], 0) if f(pts[2 * i]) > f(pts[2 * i + 1]) else (pts[2 * i + 1], pts[2 * i], 0) for i in range(30)]
+    GP = PrefGaussianProcess(our_kernel("ard", [.6] * D))
+    GP.addPreferences(prefs[:20])
+    Xc, _ = synth(62, 30, D)
+    GPc, _ = pair("m5", [.6, .9], Xc, Xc[:, 0] + Xc[:, 1])
+    A, Q, P = rs.rand(16, D), rs.rand(30, D), qr.pending_points(pts, 3)
+    C = rs.rand(1000, D)
+    dc = DeviceArray.from_host(C)
+    Z = qr.samples(64, 4)
+    con = [Constraint(GPc, upper=.9)]
+    kg, qei = KnowledgeGradient(GP, A), ParallelEI(GP, P, Z=Z)
+
+    def own_posterior(X):
+        X = _lib.f64(X)
+        mu, s2 = np.empty(len(X)), np.empty(len(X))
+        _lib.check(_lib.lib.ibo_posterior_batch(GP._handle(), len(X), _lib.dp(X), 1e-7, _lib.dp(mu), _lib.dp(s2)))
+        return mu, s2
+
+    def raw(what):
+        """the three entries on the handle as it is, each against the composition of the library's own pieces"""
+        h = GP._handle()
+        g = kg_call(_lib, h, A, Q, 1)
+        k, scale = kr.compose(g["mu_ref"], g["mu"], g["s2"], g["b"], GP.noise, True)
+        assert np.all(np.abs(g["kg"] - k) <= 1e-12 * scale) and np.max(g["kg"]) > 0, what
+        np.testing.assert_allclose(g["mu_ref"], own_posterior(A)[0], rtol=1e-6, atol=1e-9, err_msg=what)
+        np.testing.assert_allclose(g["s2"], own_posterior(Q)[1], rtol=1e-6, err_msg=what)
+        q = qei_call(_lib, h, P, Z, Q, xi=0.0)
+        maxy = ctypes.c_double()
+        _lib.check(_lib.lib.ibo_gp_info(h, None, None, None, ctypes.byref(maxy)))
+        compose_close(q, Z, maxy.value, what + " q-EI")
+        assert np.max(q["qei"]) > 0
+        np.testing.assert_allclose(q["mu_pend"], own_posterior(P)[0], rtol=1e-6, atol=1e-9, err_msg=what)
+        np.testing.assert_allclose(q["s2"], own_posterior(Q)[1], rtol=1e-6, err_msg=what)
+        r = sweepConstrained(GP, con, dc, acq='ei', xi=.01, ymax=maxy.value, outputs=("acq", "pof", "val"))
+        pm = [sweep(GP, dc, acq='ei', xi=.01, ymax=maxy.value, outputs=("mu", "s2", "acq")), sweep(GPc, dc, outputs=("mu", "s2"))]
+        val, pof = compose(pm, [(1, .9, 1)])
+        assert np.array_equal(r["acq"], pm[0]["acq"]), what
+        own_close(r["val"], val); own_close(r["pof"], pof)
+        assert r["best_idx"] == int(np.argmax(r["val"])) and r["best_val"] == np.max(r["val"]) and np.ptp(pof) > .3 and r["best_val"] > 0, what
+        return dict(kg=g["kg"], b=g["b"], qei=q["qei"], c=q["c"], val=r["val"], pof=r["pof"])
+
+    def classes(what):
+        """the Python objects made at the start return the raw entries' bits, and the posterior is the model's own"""
+        h = GP._handle()
+        assert np.array_equal(kg.values(Q), kg_call(_lib, h, A, Q, 1, slopes=False)["kg"]), what
+        assert np.array_equal(qei.values(Q), qei_call(_lib, h, P, Z, Q, xi=0.0, pieces=False)["qei"]), what
+        np.testing.assert_allclose(kg.slopes(Q)[0], GP.posteriors(A)[0], rtol=1e-6, atol=1e-9, err_msg=what)
+        np.testing.assert_allclose(qei.pieces(Q)[3], GP.posteriors(Q)[1], rtol=1e-6, err_msg=what)
+
+    first = raw("after addPreferences")
+    classes("after addPreferences")
+    GP.addObservationPoint(rs.rand(D))
+    for call in (lambda: kg.values(Q), lambda: qei.values(Q), lambda: KnowledgeGradient(GP, A), lambda: ParallelEI(GP, P, Z=Z)):
+        with pytest.raises(ValueError):
+            call()
+    second = raw("after addObservationPoint")
+    for k in first:
+        assert np.array_equal(first[k], second[k]), k
+    assert not np.allclose(GP.posteriors(Q)[1], own_posterior(Q)[1], rtol=1e-6)      # the augmented variance IS in force for the posterior
+    n0 = len(GP.X)
+    GP.addPreferences(prefs[20:])
+    assert len(GP.X) == n0 + 20 and GP._augdev is None
+    third = raw("after more preferences")
+    classes("after more preferences")
+    for k in first:                                  # (the constraint model was left alone: its factor of the product has not moved)
+        assert np.array_equal(first[k], third[k]) == (k == "pof"), k
