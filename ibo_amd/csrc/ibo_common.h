@@ -76,7 +76,8 @@ __device__ __forceinline__ double cov_from_z(double z, double sf2)
 // costs 7-13 pipe cycles (tools/mfma_f64_peak), so instruction count is sweep time.
 //   t = y log2(e) + 1.5*2^52 puts n = rint(y log2 e) in the low mantissa bits of t;
 //   r = y - n ln2 (two-term Cody-Waite);  degree-10 near-minimax polynomial on
-//   |r| <= ln2/2 (max relative error 4.4e-16, fitted at Chebyshev nodes);
+//   |r| <= ln2/2 (max relative error 4.4e-16, fitted at Chebyshev nodes; 4.5e-16 with the
+//   roundings of its evaluation: tests/kstar_reference.py restates it against mpmath);
 //   2^n by an integer add into the exponent field.  Valid for -708 <= y <= 709;
 //   smaller y is clamped (result 3e-308 instead of a denormal or 0).
 __device__ __forceinline__ double exp_fast(double y)

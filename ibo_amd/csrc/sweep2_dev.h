@@ -27,7 +27,10 @@ __device__ __forceinline__ double s2_hi(const v4u_t &v) { return __hiloint2doubl
 //   t = y 2048/ln2 + 1.5 2^52 puts n = rint(y 2048/ln2) in the low mantissa bits of t; r = y - n ln2/2048, |r| <=
 //   1.7e-4 (r^4/24 < 4e-17); j = n mod 2048 indexes the table and v_ldexp_f64 applies n div 2048, flushing to zero
 //   what underflows.  One FMA forms r: the rounding of ln2/2048 costs |n| 2.7e-20 relative -- 2.4e-15 at y = -30
-//   where k* is already 1e-13, 5.6e-14 at the underflow threshold.  Relative error < 5e-16 for |y| < 10.
+//   where k* is already 1e-13, 5.6e-14 at the underflow threshold (the worst case of that rounding; the constant as written is off by 1.13e-20: 3.4e-17 |y|).
+//   Relative error <= 6e-16 + 3.4e-17 |y|: up to 6.4e-16 for |y| < 10 (reached near 10; not the < 5e-16 this comment once claimed), 1.4e-15 at
+//   |y| = 35 -- the operation-by-operation restatement of tests/kstar_reference.py against mpmath; tests/test_gpu_kstar_probe.py holds
+//   the device to 1e-15 (1 + |y|) over every table entry, both signs of n and the whole range down to underflow.
 //   Needs |y| < 7e5 (n must fit 32 bits): the kernel's prologue bounds the scaled candidates so that it holds.
 __device__ __forceinline__ double s2_exp(double y, const double *tab)
 {
