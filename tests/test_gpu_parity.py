@@ -1449,7 +1449,8 @@ def test_super_panel_order_has_the_bits_of_the_step_by_step_order(ibo):
 def test_nlml_gradient_against_the_oracle_every_family(ibo):
     """dnlml (csrc/assemble.hip nlml_grad_fast_kernel: the pairs' coordinates shared over a thread's 4 x 4 pairs, one short loop per
     derivative, lower tiles counted twice) against the oracle's value and gradient (ego/gaussianprocess/trainhyper.py:47-95): SE-ARD in
-    2, 5 and 20 dimensions, SE-iso with signal variance, Matern-3/2, Matern-5/2, plain SE-iso"""
+    2, 5 and 20 dimensions, SE-iso with signal variance, Matern-3/2, Matern-5/2, plain SE-iso
+    (every component against its own bar, 1e-15 max(cond, 1e6) (|T1_h| + |T2_h|), and long-double truth: tests/test_gpu_nlml.py)"""
     import oracle.oracle as orc
     from ibo_amd.gaussianprocess import kernel as K
     from ibo_amd.gaussianprocess.trainhyper import marginalLikelihood
