@@ -5,9 +5,9 @@ The library is the product's ONLY compute path: if it is missing this module
 raises at import, and every compute call raises IBOError(IBO_ERR_NO_DEVICE)
 when no MI355X is visible.  Nothing here falls back to NumPy.
 
-Every symbol of the header is bound below and listed in EXPORTED (88 of them: tests/test_cpu_host.py holds the two lists to
+Every symbol of the header is bound below and listed in EXPORTED (98 of them: tests/test_cpu_host.py holds the two lists to
 the header and to the library), the ibo_qei_* entries of the parallel expected improvement and the ibo_ehvi_* entries of the
-two-objective hypervolume improvement among them.
+two-objective hypervolume improvement and the ibo_ggp_* entries of a GP observed with gradients among them.
 """
 import ctypes
 import os
@@ -141,6 +141,19 @@ _sig("ibo_paths_sweep", c_int, _PATHS, c_int64, c_void_p, c_int64, c_void_p, _DP
 _sig("ibo_paths_batch", c_int, _PATHS, c_int64, _DP, _DP)
 _sig("ibo_paths_grad_batch", c_int, _PATHS, c_int64, _DP, POINTER(c_int), _DP, _DP)
 _sig("ibo_paths_direct_max", c_int, _PATHS, c_int, c_int, _DP, _DP, c_int, c_int, c_int, c_int, _DP, _DP, POINTER(c_int64))
+_GGP = c_void_p                                                            # ibo_ggp_t *
+_sig("ibo_ggp_create", c_int, c_int, POINTER(_GGP))
+_sig("ibo_ggp_destroy", c_int, _GGP)
+_sig("ibo_ggp_info", c_int, _GGP, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), _DP)
+_sig("ibo_ggp_fit", c_int, _GGP, c_int, c_int, c_int, _DP, _DP, _DP, _DP, c_int, c_double, c_double, _DP, POINTER(c_int))
+_sig("ibo_ggp_get_R", c_int, _GGP, _DP)
+_sig("ibo_ggp_get_L", c_int, _GGP, _DP)
+_sig("ibo_ggp_acq_batch", c_int, _GGP, c_int64, _DP, c_int, c_double, c_int, c_double, c_double, _DP, _DP, _DP)
+_sig("ibo_ggp_acq_sweep", c_int, _GGP, c_int64, c_void_p, c_int, c_double, c_int, c_double, c_double, c_int64,
+     c_void_p, c_void_p, c_void_p, _DP, POINTER(c_int64))
+_sig("ibo_ggp_direct_max", c_int, _GGP, c_int, _DP, _DP, c_int, c_double, c_int, c_double, c_int, c_int, c_int, c_int,
+     _DP, _DP, POINTER(c_int64))
+_sig("ibo_ggp_stage_ms", c_int, _DP, c_int)
 _sig("ibo_direct_host", c_int, OBJECTIVE, c_int, _DP, _DP, c_int, c_int, c_int, c_int, _DP, _DP, POINTER(c_int64))
 _sig("ibo_nlml_grid", c_int, c_int, c_int, c_int, c_int, _DP, _DP, c_int, _DP, c_int, _DP, c_double, _DP)
 _sig("ibo_nlml_grad", c_int, c_int, c_int, c_int, c_int, _DP, _DP, _DP, c_int, c_double, c_double, c_int,
@@ -167,7 +180,9 @@ EXPORTED = ["ibo_abi_version", "ibo_last_error", "ibo_device_count", "ibo_device
             "ibo_device_synchronize", "ibo_dev_generation", "ibo_gp_create", "ibo_gp_destroy", "ibo_gp_fit", "ibo_gp_fit_with_matrix",
             "ibo_gp_extend", "ibo_gp_reserve", "ibo_gp_remove", "ibo_pref_begin", "ibo_pref_rinv_mul", "ibo_pref_newton_step", "ibo_pref_finish", "ibo_gp_set_y", "ibo_gp_set_kstar_sf2", "ibo_gp_set_prior", "ibo_gp_get_R", "ibo_gp_get_L",
             "ibo_gp_get_W", "ibo_gp_info", "ibo_gp_last_fit_ms", "ibo_cov_matrix", "ibo_spd_solve", "ibo_spd_inverse", "ibo_posterior_batch",
-            "ibo_acq_sweep", "ibo_acq_batch", "ibo_acq_grad_batch", "ibo_posterior_cov", "ibo_posterior_sample", "ibo_acq_sweep_incremental", "ibo_sweep_state_info", "ibo_sweep_state_levels", "ibo_last_sweep_kernel_ms", "ibo_direct_max", "ibo_cacq_sweep", "ibo_cacq_batch", "ibo_cacq_grad_batch", "ibo_cacq_direct_max", "ibo_ehvi_sweep", "ibo_ehvi_batch", "ibo_ehvi_grad_batch", "ibo_ehvi_direct_max", "ibo_ehvi_scan_ms", "ibo_kg_sweep", "ibo_kg_batch", "ibo_kg_direct_max", "ibo_kg_stage_ms", "ibo_qei_sweep", "ibo_qei_batch", "ibo_qei_direct_max", "ibo_qei_stage_ms", "ibo_paths_create", "ibo_paths_destroy", "ibo_paths_info", "ibo_paths_coef", "ibo_paths_sweep", "ibo_paths_batch", "ibo_paths_grad_batch", "ibo_paths_direct_max", "ibo_direct_host", "ibo_nlml_grid", "ibo_nlml_grad", "ibo_gp_loo", "ibo_loo_grad",
+            "ibo_acq_sweep", "ibo_acq_batch", "ibo_acq_grad_batch", "ibo_posterior_cov", "ibo_posterior_sample", "ibo_acq_sweep_incremental", "ibo_sweep_state_info", "ibo_sweep_state_levels", "ibo_last_sweep_kernel_ms", "ibo_direct_max", "ibo_cacq_sweep", "ibo_cacq_batch", "ibo_cacq_grad_batch", "ibo_cacq_direct_max", "ibo_ehvi_sweep", "ibo_ehvi_batch", "ibo_ehvi_grad_batch", "ibo_ehvi_direct_max", "ibo_ehvi_scan_ms", "ibo_kg_sweep", "ibo_kg_batch", "ibo_kg_direct_max", "ibo_kg_stage_ms", "ibo_qei_sweep", "ibo_qei_batch", "ibo_qei_direct_max", "ibo_qei_stage_ms", "ibo_paths_create", "ibo_paths_destroy", "ibo_paths_info", "ibo_paths_coef", "ibo_paths_sweep", "ibo_paths_batch", "ibo_paths_grad_batch", "ibo_paths_direct_max",
+            "ibo_ggp_create", "ibo_ggp_destroy", "ibo_ggp_info", "ibo_ggp_fit", "ibo_ggp_get_R", "ibo_ggp_get_L", "ibo_ggp_acq_batch", "ibo_ggp_acq_sweep",
+            "ibo_ggp_direct_max", "ibo_ggp_stage_ms", "ibo_direct_host", "ibo_nlml_grid", "ibo_nlml_grad", "ibo_gp_loo", "ibo_loo_grad",
             "ibo_comm_get_unique_id", "ibo_comm_init", "ibo_comm_destroy", "ibo_comm_count", "ibo_comm_argmax", "ibo_comm_allreduce_sum", "ibo_acq_sweep_exchange", "ibo_comm_barrier",
             "acqmaxGP", "direct", "logCDFs"]
 

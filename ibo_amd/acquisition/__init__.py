@@ -41,6 +41,7 @@ def _acq_gradient(GP, X, acq, parm, ymax):
     """values and gradients (M, D) of an acquisition at the points X with the Python classes' conventions (NR erf, clamp
     [1e-7, 10]): one ibo_acq_grad_batch call, or -- with an augmented factor in force -- the chain rule on the host from
     posterior_gradient, as GaussianProcess._eval forms the values there"""
+    GP._no_gradient("gradient / negf_grad of an acquisition")
     Q = _lib.f64(np.atleast_2d(np.asarray(X, dtype=float)))
     M, D = Q.shape
     if GP._augdev is not None:
@@ -174,6 +175,13 @@ def cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc=None, xi=-1, b
     lb = _lib.f64([b[0] for b in bounds]); ub = _lib.f64([b[1] for b in bounds])
     D = len(lb)
     opt = ctypes.c_double(); optx = np.empty(D); ns = ctypes.c_int64()
+    if model.G is not None:
+        # a model observed with gradients: the same DIRECT on ibo_ggp_direct_max, libm erf and the native clamp as here, but the
+        # model's own signal variance throughout (libego has no gradient models to be compatible with)
+        _lib.check(_lib.lib.ibo_ggp_direct_max(model._gdev.h, D, _lib.dp(lb), _lib.dp(ub), _ACQ[acqfunc], float(parm), _lib.ERF_LIBM,
+                                               _lib.CLAMP_NATIVE, int(maxiter), int(maxtime), int(maxsample), 1 if compat else 0,
+                                               ctypes.byref(opt), _lib.dp(optx), ctypes.byref(ns)))
+        return (opt.value, optx, ns.value) if return_samples else (opt.value, optx)
     h = model._handle()
     model._push_prior()
     _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(h, sf2_native))
@@ -200,6 +208,7 @@ def _polish(model, bounds, acqfunc, parm, opt, optx):
     [1e-8, 10], the same parm; one ibo_acq_grad_batch call per evaluation), bounded to the box and at most POLISH_MAXITER
     iterations.  The end point is re-evaluated with ibo_acq_batch and returned only if it is strictly better than DIRECT's."""
     from scipy.optimize import minimize
+    model._no_gradient("polish=True")
     lb = _lib.f64([b[0] for b in bounds]); ub = _lib.f64([b[1] for b in bounds])
     D = len(lb)
     code = _ACQ[acqfunc]
@@ -239,6 +248,8 @@ def maximizeUCB(model, bounds, delta=0.1, scale=0.2, useCDIRECT=True, maxiter=50
         opt, optx = direct(ucb.negf, bounds, maxiter=maxiter, maxtime=maxtime, maxsample=maxsample)
         return -opt, optx
     if isinstance(model, GaussianProcess):
+        if polish:
+            model._no_gradient("maximizeUCB(polish=True)")
         opt, optx = cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='ucb', delta=delta, scale=scale,
                               **kwargs)
         if polish:
@@ -255,6 +266,8 @@ def maximizePI(model, bounds, xi=0.01, maxiter=50, maxtime=30, maxsample=10000, 
         opt, optx = direct(pi.negf, bounds, maxiter=maxiter, maxtime=maxtime, maxsample=maxsample)
         return -opt, optx
     if isinstance(model, GaussianProcess):
+        if polish:
+            model._no_gradient("maximizePI(polish=True)")
         opt, optx = cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='pi', xi=xi, **kwargs)
         if polish:
             return _polish(model, bounds, 'pi', xi, opt, optx)
@@ -270,6 +283,8 @@ def maximizeEI(model, bounds, useCDIRECT=True, xi=0.01, maxiter=50, maxtime=30, 
         opt, optx = direct(ei.negf, bounds, maxiter=maxiter, maxtime=maxtime, maxsample=maxsample)
         return -opt, optx
     if isinstance(model, GaussianProcess):
+        if polish:
+            model._no_gradient("maximizeEI(polish=True)")
         opt, optx = cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='ei', xi=xi, **kwargs)
         if polish:
             return _polish(model, bounds, 'ei', xi, opt, optx)
@@ -295,7 +310,12 @@ def sweep(model, candidates, acq='ei', xi=0.01, delta=0.1, scale=0.2, parm=None,
                  arg-max goes from the sweep's output words into the all-reduce buffer without visiting the host; the result then
                  also carries global_val, global_idx, global_x, global_rank (identical on every rank).  No `outputs` with it.
     Returns dict(best_val, best_idx, kernel_ms, [mu], [s2], [acq]); first maximiser wins ties.
+    A model observed with gradients (G=) takes ibo_ggp_acq_sweep: the same arguments and result (kernel_ms is the whole call's device
+    time), the model's own signal variance in both modes, and NotImplementedError for exclude=, incremental= and exchange=.
     """
+    if model.G is not None:
+        return _sweep_gradient(model, candidates, acq, xi, delta, scale, parm, native, ymax, exclude, index_base, outputs, NA,
+                               incremental, exchange)
     if isinstance(candidates, _lib.DeviceArray):
         cand = candidates
     else:
@@ -346,6 +366,38 @@ def sweep(model, candidates, acq='ei', xi=0.01, delta=0.1, scale=0.2, parm=None,
     res = dict(best_val=bv.value, best_idx=bi.value, kernel_ms=ms.value, kernel=name.value.decode())
     if glob is not None:
         res.update(glob)
+    for k, v in outs.items():
+        res[k] = v.to_host()
+    return res
+
+
+def _sweep_gradient(model, candidates, acq, xi, delta, scale, parm, native, ymax, exclude, index_base, outputs, NA, incremental,
+                    exchange):
+    """sweep() on a model observed with gradients (ibo_ggp_acq_sweep)"""
+    if exclude is not None and len(exclude) > 0:
+        model._no_gradient("sweep(exclude=)")
+    if incremental:
+        model._no_gradient("sweep(incremental=)")
+    if exchange is not None:
+        model._no_gradient("sweep(exchange=)")
+    dev = model._gdev.device
+    cand = candidates if isinstance(candidates, _lib.DeviceArray) else _lib.DeviceArray.from_host(np.atleast_2d(candidates), dev)
+    M = cand.shape[0]
+    if parm is None:
+        if acq == 'ucb':
+            nd = NA if NA is not None else cand.shape[1]
+            parm = _ucb_parm(model, [None] * nd, delta, scale) if native else float(np.sqrt(scale * UCB(model, nd, delta, scale).sBeta))
+        else:
+            parm = xi
+    outs = {k: _lib.DeviceArray((M,), dev) for k in outputs}
+    bv = ctypes.c_double(); bi = ctypes.c_int64()
+    t0 = _lib.gpu_time_ms(dev)
+    _lib.check(_lib.lib.ibo_ggp_acq_sweep(
+        model._gdev.h, M, cand.ptr, _ACQ[acq], float(parm), _lib.ERF_LIBM if native else _lib.ERF_NR,
+        _lib.CLAMP_NATIVE if native else _lib.CLAMP_PY, float('nan') if ymax is None else float(ymax), int(index_base),
+        outs["mu"].ptr if "mu" in outs else None, outs["s2"].ptr if "s2" in outs else None,
+        outs["acq"].ptr if "acq" in outs else None, ctypes.byref(bv), ctypes.byref(bi)))
+    res = dict(best_val=bv.value, best_idx=bi.value, kernel_ms=_lib.gpu_time_ms(dev) - t0, kernel="gradobs row pipeline")
     for k, v in outs.items():
         res[k] = v.to_host()
     return res

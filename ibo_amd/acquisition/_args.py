@@ -4,11 +4,18 @@ import numpy as np
 from .. import _lib
 
 
+def _no_gradient(GP, what):
+    """refuse `what` on a model observed with gradients (GaussianProcess(G=)); anything without a G attribute passes"""
+    if getattr(GP, "G", None) is not None:
+        GP._no_gradient(what)
+
+
 def _points(GP, P, what, noun):
     """an (M, D) float64 matrix of points of the model's dimension; a 1-D sequence is ONE point (D coordinates), as everywhere else.
     noun: what the refusal of an augmented factor calls the acquisition"""
     if len(GP.X) == 0:
         raise ValueError("model has no data")
+    _no_gradient(GP, "the %s" % noun)
     if getattr(GP, "_augdev", None) is not None:
         raise ValueError("the %s is not defined on an augmented factor (addObservationPoint): its covariances would "
                          "come from one factor and its means from another" % noun)

@@ -29,7 +29,7 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from . import POLISH_MAXITER
+from . import POLISH_MAXITER, _args
 
 _CACQ = {'ei': _lib.ACQ_EI, 'pi': _lib.ACQ_PI, 'pof': _lib.ACQ_NONE}
 MAX_CONSTRAINTS = 8          # IBO_CACQ_MAX_CON
@@ -58,6 +58,7 @@ def _pack(constraints):
     for c in constraints:
         if len(c.GP.X) == 0:
             raise ValueError("a constraint model has no data")
+        _args._no_gradient(c.GP, "a constrained acquisition (constraint model)")
         c.GP._push_prior()
     con = (ctypes.c_void_p * max(n, 1))(*[c.GP._handle() for c in constraints])
     thresh = _lib.f64([c.thresh for c in constraints] or [0.0])
@@ -131,6 +132,7 @@ def sweepConstrained(model, constraints, candidates, acq='ei', xi=0.01, native=T
     maximiser wins ties, best_idx = -1 when everything is excluded.
     """
     constraints = list(constraints)
+    _args._no_gradient(model, "sweepConstrained")
     if isinstance(candidates, _lib.DeviceArray):
         cand = candidates
     else:
@@ -164,6 +166,7 @@ class _Constrained(object):
     _acq = 'ei'
 
     def __init__(self, GP, constraints, xi=.01, ymax=None, **kwargs):
+        _args._no_gradient(GP, "a constrained acquisition (ConstrainedEI / ConstrainedPI / ProbFeasible)")
         self.GP = GP
         self.constraints = list(constraints)
         self.xi = xi
@@ -227,6 +230,7 @@ def _maximize(model, constraints, bounds, acq, xi, maxiter, maxtime, maxsample, 
     constraints = list(constraints)
     if len(model.X) == 0:
         raise ValueError("model has no data")
+    _args._no_gradient(model, "maximizeCEI / maximizeCPI")
     acq, ym = _incumbent(model, constraints, acq, ymax)
     lb = _lib.f64([b[0] for b in bounds]); ub = _lib.f64([b[1] for b in bounds])
     D = len(lb)

@@ -24,7 +24,7 @@ import numpy as np
 
 from ..gaussianprocess import GaussianProcess
 from ..utils.latinhypercube import lhcSample
-from . import EI, maximizeEI, sweep
+from . import EI, maximizeEI, sweep, _args
 from .. import _lib
 
 
@@ -103,6 +103,7 @@ def fastUCBGallery(GP, bounds, N, useBest=True, samples=300, useCDIRECT=True, ca
     maxiter / maxsample   the DIRECT step's budgets (the reference's maximizeEI defaults)
     trace                 a list that receives one dict per round: the DIRECT proposal (opt, optx), the sweep's
                           (value, global index), which proposal won, the sweep kernel and the kept state's (tiles, complete)"""
+    _args._no_gradient(GP, "fastUCBGallery (its rounds add hallucinated observations, which have no slopes)")
     gallery, model = _start(GP, bounds, useBest, rounds=N)
     # a fixed candidate array is swept every round while the model grows by one hallucinated point: it goes to
     # HBM once, and from the second round on the device folds the model's new row into the per-candidate state it

@@ -28,7 +28,7 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from . import POLISH_MAXITER
+from . import POLISH_MAXITER, _args
 from .constrained import _kstar_native
 
 MAX_FRONT = 1024             # IBO_EHVI_MAX_FRONT
@@ -67,6 +67,7 @@ def _pair(models):
     for m in models:
         if len(m.X) == 0:
             raise ValueError("an objective model has no data")
+        _args._no_gradient(m, "the expected hypervolume improvement")
     return models
 
 

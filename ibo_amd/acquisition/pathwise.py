@@ -29,6 +29,7 @@ import numpy as np
 
 from .. import _lib
 from ..utils.latinhypercube import lhcSample
+from . import _args
 
 MAX_PATHS = 256           # IBO_PATHS_MAX_PATHS
 MAX_FEATURES = 16384      # IBO_PATHS_MAX_FEATURES
@@ -80,6 +81,7 @@ class PosteriorPaths(object):
             raise NotImplementedError("pathwise draws on an augmented factor (addObservationPoint)")
         if len(GP.X) == 0:
             raise ValueError("model has no data")
+        _args._no_gradient(GP, "pathwise posterior draws (PosteriorPaths)")
         N, D = np.asarray(GP.X).shape
         sf2 = GP.kernel._ibo_spec()[2]
         eps_var = 1.0 + float(GP.noise) - sf2

@@ -11,8 +11,9 @@
 //   abi_kg.hip      the knowledge gradient (ibo_kg_*)
 //   abi_paths.hip   pathwise posterior draws (ibo_paths_*)
 //   abi_qei.hip     the Monte-Carlo parallel expected improvement (ibo_qei_*)
-//   abi_rows.hip    the row pipeline of the two above: chunk, scratch, stage clock, host batch, device sweep (abi_rows.h)
-//                   (these eight are the evaluation units: what they share among themselves is in abi_eval.h)
+//   abi_gradobs.hip the GP observed with gradients (ibo_ggp_*): its own handle around a P-row frame, the row pipeline with its own K*
+//   abi_rows.hip    the row pipeline of the three above: chunk, scratch, stage clock, host batch, device sweep (abi_rows.h)
+//                   (these nine are the evaluation units: what they share among themselves is in abi_eval.h)
 //   abi_nlml.hip    marginal-likelihood grid and gradient, ibo_trim
 //   abi_legacy.hip  libego's symbols (acqmaxGP, direct, logCDFs) and ibo_direct_host
 // There is no CPU fallback anywhere behind this header: without a gfx950 device every compute entry point returns IBO_ERR_NO_DEVICE.
@@ -57,6 +58,7 @@ extern std::atomic<int> g_cacq_chunk;                // abi_cacq.hip: candidates
 extern std::atomic<int> g_ehvi_chunk, g_ehvi_timing; // abi_ehvi.hip: candidates per chunk of the ibo_ehvi_* entries (0: by bytes); HIP events around the scan kernel
 extern std::atomic<int> g_kg_chunk, g_kg_timing;     // abi_kg.hip: candidates per chunk (0: by bytes); per-stage HIP events
 extern std::atomic<int> g_qei_chunk, g_qei_timing;   // abi_qei.hip: candidates per chunk (0: by bytes); per-stage HIP events
+extern std::atomic<int> g_ggp_chunk, g_ggp_timing;   // abi_gradobs.hip: candidates per chunk of the ibo_ggp_* entries (0: by bytes); per-stage HIP events
 extern std::atomic<int> g_paths_chunk;               // abi_paths.hip: candidates per launch of the ibo_paths_* entries (0: 2^21)
 extern std::mutex g_dev_mu[16];             // serialises the per-device workspaces of ibo_nlml_grid / ibo_nlml_grad / ibo_trim
 extern std::atomic<size_t> g_pool_limit;

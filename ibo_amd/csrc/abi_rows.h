@@ -23,6 +23,8 @@ struct StageClock {
 
 // the stages after the row kernel: the cross launch, mark(4), the last kernel into out, mark(5)
 typedef std::function<int(int m, int mp, const double *cand, double *out)> rows_tail_t;
+// K* of a chunk by another kernel than launch_cov_kstar (abi_gradobs.hip: the rows are values AND derivatives): m points at pts -> kt, mp x Npad
+typedef std::function<int(const double *pts, int m, int mp, double *kt, hipStream_t s)> rows_kstar_t;
 
 struct RowPipeline {
     ibo_gp *g = nullptr;
@@ -32,6 +34,7 @@ struct RowPipeline {
     bool keep_q = false;                             // the row kernel's |v|^2 is kept (in q)
     StageClock clock;
     rows_tail_t tail;
+    rows_kstar_t kstar;                              // empty: launch_cov_kstar on the handle's points
     ScopedBuf<double> cand, kt, vt, mu, q, s2, cross, val;     // one chunk
     // chunk_opt: the unit's chunk option; the chunk is bounded by Npad and by cross_width doubles per candidate
     int begin(ibo_gp *g, double clamp_lo, int chunk_opt, size_t cross_width, size_t ldx, bool keep_q, bool timing, double *ms);

@@ -58,7 +58,8 @@ int RowPipeline::chunk(int m, const double *pts, double *out)
     const int N = g->N, Np = g->Npad, mp = round_up(m, IBO_COV_TILE);
     hipStream_t s = g->stream;
     IBO_TRY(clock.mark(0));
-    KERNEL_TRY(launch_cov_kstar(g->kp, g->Xp.p, N, Np, g->DP, pts, m, mp, kt.p, s));
+    if (kstar) IBO_TRY(kstar(pts, m, mp, kt.p, s));
+    else KERNEL_TRY(launch_cov_kstar(g->kp, g->Xp.p, N, Np, g->DP, pts, m, mp, kt.p, s));
     IBO_TRY(clock.mark(1));
     KERNEL_TRY(launch_cov_tri(kt.p, (size_t)Np, g->W.p, (size_t)Np, N, mp, Np, vt.p, (size_t)Np, s));
     IBO_TRY(clock.mark(2));

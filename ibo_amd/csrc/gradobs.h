@@ -1,0 +1,27 @@
+// gradobs.h -- the derivative covariance of a GP observed with gradients (gradobs.hip) and what the ABI unit (abi_gradobs.hip) hands it.
+// Row-major everywhere, 64-bit offsets.
+//
+// Rows are POINT-MAJOR: row i (D + 1) is the value at x_i, rows i (D + 1) + d (d = 1 .. D) are df/dx_d at x_i; P = N (D + 1).
+// With u = x - x' (x the row's point, x' the column's), t_d = w_d u_d and three factors per point pair,
+//   SE          k = sf2 exp(-z / 2)               g1 = k                       g2 = k
+//   Matern-3/2  k = sf2 (1 + r) exp(-r)           g1 = 3 sf2 exp(-r)           g2 = 3 g1 / r   (0 at r = 0)
+//   Matern-5/2  k = sf2 (1 + r + r^2/3) exp(-r)   g1 = 5/3 sf2 (1 + r) exp(-r) g2 = 25/3 sf2 exp(-r)
+// (z = sum_d w_d u_d^2; r = sqrt(3 z), sqrt(5 z)), the (D + 1) x (D + 1) block of the pair is
+//   [ k           g1 t_e                          ]        (value, d/dx'_e)
+//   [ -g1 t_d     g1 w_d delta_de - g2 (t_d t_e)  ]        (d/dx_d, d2/dx_d dx'_e)
+// t_d t_e is formed first, so the entry (a, b) of the pair (i, j) and the entry (b, a) of the pair (j, i) are the same bits.
+#pragma once
+#include "ibo_common.h"
+
+// A in the identity-padded frame factor_invert takes: Np x Np (ld Np), A[r][c] for r, c < P = N (D + 1) from the blocks above with the
+// diagonal rule -- 1 + noise on a value row, g1(0) w_d + gnoise[d - 1] on derivative row d -- and the identity on the rows and columns
+// [P, Np).  X: N x D (device), gnoise: D (device).  Every element of the frame is written, both triangles.
+int launch_gradobs_assemble(const KParams &kp, const double *X, int N, double noise, const double *gnoise, double *A, int Np,
+                            hipStream_t s);
+// Kt[c][j (D + 1)] = k(q_c, x_j), Kt[c][j (D + 1) + d] = dk(q_c, x_j) / dx_j,d = g1 t_d (u = q_c - x_j) for c < m, j < N; 0 elsewhere in
+// the mp x Pp block (ld Pp): the layout launch_cov_tri reads.  Q: m x D (device).  mp <= 65535.
+int launch_gradobs_kstar(const KParams &kp, const double *X, int N, int Pp, const double *Q, int m, int mp, double *Kt, hipStream_t s);
+// acq[i] = the acquisition (acq_value_dev: EI / PI / UCB in either erf flavour; IBO_ACQ_NONE: mu) from mu[i] and s2[i], i < m; mu_out /
+// s2_out (optional) receive copies of mu / s2
+int launch_gradobs_acq(int acq, int erf_mode, double ymax, double parm, const double *mu, const double *s2, int m, double *out,
+                       double *mu_out, double *s2_out, hipStream_t s);

@@ -3,7 +3,7 @@ Gaussian-process models with the reference's API (ego/gaussianprocess/__init__.p
 on the MI355X backend.
 
     GaussianProcess(kernel, X=None, Y=None, prior=None, noise=.1, gnoise=1e-4, G=None)
-        .addData(X, Y)  .removeData(indices)  .posterior(x, getvar=True)  .posteriors(X)  .mu(x)  .negmu(x)
+        .addData(X, Y, G=None)  .removeData(indices)  .posterior(x, getvar=True)  .posteriors(X)  .mu(x)  .negmu(x)
         .getYfromX(qx)  .done(x)   attributes X, Y, R, L, noise, kernel, prior, ...
     PrefGaussianProcess(kernel, prefs=None, **kw)
         .addPreferences(prefs)  .addObservationPoint(x)   attributes preferences, C
@@ -69,6 +69,31 @@ class _DeviceGP(object):
         self.close()
 
 
+class _DeviceGGP(object):
+    """owner of one ibo_ggp_t handle: a model observed with gradients"""
+
+    def __init__(self, device=None):
+        self.device = _lib.default_device() if device is None else device
+        h = ctypes.c_void_p()
+        _lib.check(_lib.lib.ibo_ggp_create(self.device, ctypes.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            try:
+                _lib.lib.ibo_ggp_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+_GRADIENT_WHY = ("the model is observed with gradients (G=): it has N (D + 1) rows of values and derivatives, and only posterior, "
+                 "posteriors, mu, negmu, R, L, EI / PI / UCB, acquisition.sweep and maximizeEI / PI / UCB are built for it")
+
+
 class GaussianProcess(object):
 
     def __init__(self, kernel, X=None, Y=None, prior=None, noise=.1, gnoise=1e-4, G=None, device=None, reserve_rows=0):
@@ -91,11 +116,11 @@ class GaussianProcess(object):
         self.name = 'GP'
         self.starttime = time()
 
-        if G is not None:
-            raise NotImplementedError("gradient observations are dead code in the reference "
-                                      "(covWithGradients is never defined) and are not supported")
+        self._gdev = None           # _DeviceGGP: the model's device handle once it holds gradient observations
+        if G is not None and X is None:
+            raise ValueError("G= comes with X= and Y=")
         if X is not None:
-            self.addData(X, Y)
+            self.addData(X, Y, G)
 
         self.augR = None
         self.augL = None
@@ -104,8 +129,61 @@ class GaussianProcess(object):
         self.selected = None
         self.endtime = None
 
+    # ------------------------------------------------------------------ gradient observations
+    def _no_gradient(self, what):
+        """refuse `what` on a model observed with gradients"""
+        if self.G is not None:
+            raise NotImplementedError("%s: not available, %s" % (what, _GRADIENT_WHY))
+
+    def _fit_gradient(self, X, Y, G):
+        """fit a NEW gradient handle from all the data (ibo_ggp_fit) and swap it in only when that succeeded: a matrix that does not
+        factor leaves the previous model in place"""
+        if self.prior is not None:
+            raise NotImplementedError("a mean prior together with gradient observations (G=): the derivative rows would need the "
+                                      "prior's gradient, which the device does not subtract")
+        ktype, hyper, sf2, _ = self.kernel._ibo_spec()
+        N, D = X.shape
+        gn = np.asarray(self.gnoise, dtype=float).reshape(-1)
+        gn = _lib.f64(np.tile(gn, D) if len(gn) == 1 else gn)
+        if len(gn) != D:
+            raise ValueError("gnoise has %d entries, the data %d dimensions" % (len(gn), D))
+        dev = _DeviceGGP(self._device)
+        Xc, Yc, Gc = _lib.f64(X), _lib.f64(Y), _lib.f64(G)
+        info = ctypes.c_int(0)
+        rc = _lib.lib.ibo_ggp_fit(dev.h, ktype, N, D, _lib.dp(Xc), _lib.dp(Yc), _lib.dp(Gc), _lib.dp(hyper), len(hyper), sf2,
+                                  float(self.noise), _lib.dp(gn), ctypes.byref(info))
+        if rc != _lib.OK:
+            dev.close()
+        _lib.check(rc)
+        old, self._gdev = self._gdev, dev
+        if old is not None:
+            old.close()
+        self._cache = {}
+
+    def _add_gradient_data(self, X, Y, G):
+        G = np.array(G, dtype=float, ndmin=2)
+        if G.shape != X.shape:
+            raise ValueError("G has shape %s, X has %s: one partial derivative per coordinate of every point" % (G.shape, X.shape))
+        if len(self.gnoise) == 1:
+            self.gnoise = np.tile(self.gnoise, X.shape[1])
+        first = len(self.X) == 0
+        allX = np.copy(X) if first else np.r_[self.X, X]
+        allY = np.copy(Y) if first else np.r_[self.Y, Y]
+        allG = np.copy(G) if first else np.r_[self.G, G]
+        self._fit_gradient(allX, allY, allG)         # (raises before anything of the model changes)
+        self.X, self.Y, self.G = allX, allY, allG
+
+    def _ggp_eval(self, Q, acq, parm, erf_mode, clamp_lo, want, ymax):
+        M = len(Q)
+        res = {k: np.empty(M) for k in want}
+        ptr = lambda k: _lib.dp(res[k]) if k in res else None
+        _lib.check(_lib.lib.ibo_ggp_acq_batch(self._gdev.h, M, _lib.dp(Q), acq, float(parm), erf_mode, clamp_lo,
+                                              float('nan') if ymax is None else float(ymax), ptr("mu"), ptr("s2"), ptr("acq")))
+        return res
+
     # ------------------------------------------------------------------ device plumbing
     def _handle(self):
+        self._no_gradient("this call (it takes the model's ibo_gp_t handle)")
         if self._dev is None:
             self._dev = _DeviceGP(self._device)
             if self._reserve_rows:
@@ -175,10 +253,15 @@ class GaussianProcess(object):
 
     def _get_matrix(self, name):
         if name not in self._cache:
-            N = len(self.X)
-            out = np.empty((N, N))
-            fn = getattr(_lib.lib, "ibo_gp_get_" + name)
-            _lib.check(fn(self._handle(), _lib.dp(out)))
+            if self.G is not None:                   # P x P, point-major rows of values and derivatives
+                P = self.X.shape[0] * (self.X.shape[1] + 1)
+                out = np.empty((P, P))
+                _lib.check(getattr(_lib.lib, "ibo_ggp_get_" + name)(self._gdev.h, _lib.dp(out)))
+            else:
+                N = len(self.X)
+                out = np.empty((N, N))
+                fn = getattr(_lib.lib, "ibo_gp_get_" + name)
+                _lib.check(fn(self._handle(), _lib.dp(out)))
             self._cache[name] = out
         return self._cache[name]
 
@@ -211,8 +294,12 @@ class GaussianProcess(object):
         """host points in, host arrays out, through the device sweep (PCIe-inclusive)"""
         Q = _lib.f64(np.atleast_2d(Q))
         M, D = Q.shape
+        if self.G is not None:
+            res = self._ggp_eval(Q, acq, parm, erf_mode, clamp_lo, want, ymax)
+        else:
+            res = None
         self._push_prior()
-        if self._augdev is not None and acq != _lib.ACQ_NONE:
+        if res is None and self._augdev is not None and acq != _lib.ACQ_NONE:
             # augmented variance in force (addObservationPoint): mean and variance come from two
             # factors, so the acquisition is formed from them as the reference's classes do
             # (ego/acquisition/__init__.py:68-71,107-110,150-164), per point on the host
@@ -229,10 +316,11 @@ class GaussianProcess(object):
                 else:
                     val = yd * CDF(Z) + sig * PDF(Z)
             return {"mu": mu, "s2": s2, "acq": val, "best_val": float(np.max(val)), "best_idx": int(np.argmax(val))}
-        res = {k: np.empty(M) for k in want}
-        ptr = lambda k: _lib.dp(res[k]) if k in res else None
-        _lib.check(_lib.lib.ibo_acq_batch(self._handle(), M, _lib.dp(Q), acq, float(parm), erf_mode, clamp_lo,
-                                          float('nan') if ymax is None else float(ymax), ptr("mu"), ptr("s2"), ptr("acq")))
+        if res is None:
+            res = {k: np.empty(M) for k in want}
+            ptr = lambda k: _lib.dp(res[k]) if k in res else None
+            _lib.check(_lib.lib.ibo_acq_batch(self._handle(), M, _lib.dp(Q), acq, float(parm), erf_mode, clamp_lo,
+                                              float('nan') if ymax is None else float(ymax), ptr("mu"), ptr("s2"), ptr("acq")))
         if "acq" in res:                             # first maximiser, NaNs never win: what the device arg-max does
             score = np.where(np.isnan(res["acq"]), -np.inf, res["acq"])
             k = int(np.argmax(score))
@@ -255,6 +343,9 @@ class GaussianProcess(object):
     def _posterior_arrays(self, Q, getvar=True):
         Q = _lib.f64(np.atleast_2d(Q))
         M = len(Q)
+        if self.G is not None:
+            res = self._ggp_eval(Q, _lib.ACQ_NONE, 0.0, _lib.ERF_NR, _lib.CLAMP_PY, ("mu", "s2") if getvar else ("mu",), None)
+            return res["mu"], res.get("s2")
         self._push_prior()
         mu = np.empty(M)
         s2 = np.empty(M) if getvar else None
@@ -272,6 +363,7 @@ class GaussianProcess(object):
         [1e-7, 10]) and its gradients with respect to the point, (M, D) each (ibo_acq_grad_batch).  ds2 is 0 where the clamp
         is active.  An empty model gives the prior's mean and its gradient (0 without a prior), s2 = 1 and ds2 = 0; with an
         augmented factor in force (addObservationPoint) s2 and ds2 come from it, as in `posteriors`."""
+        self._no_gradient("posterior_gradient")
         Q = np.asarray(X, dtype=float)
         single = Q.ndim == 1
         Q = _lib.f64(np.atleast_2d(Q))
@@ -300,6 +392,7 @@ class GaussianProcess(object):
         of `posteriors` before its clamp) or, with noise=False, 1 - |v_a|^2 (the latent function's).  Unclipped and exactly
         symmetric.  With an augmented factor in force (addObservationPoint) Sigma comes from it, mu from the model.  An empty
         model gives the prior's mean (0 without a prior) and K(X, X) with a unit diagonal."""
+        self._no_gradient("posterior_cov")
         Q = _lib.f64(np.atleast_2d(np.asarray(X, dtype=float)))
         M, D = Q.shape
         S = np.empty((M, M))
@@ -319,6 +412,7 @@ class GaussianProcess(object):
         return mu, S
 
     def _loo(self, want_pred, want_score):
+        self._no_gradient("loo / loo_score")
         if len(self.X) == 0:
             raise ValueError("leave-one-out predictions need at least one observation")
         self._push_prior()
@@ -348,6 +442,7 @@ class GaussianProcess(object):
         `posterior_cov` (factored on the device, ibo_posterior_sample) and z from np.random.default_rng(seed): the same seed gives
         the same draws.  A covariance that does not factor is retried with sf2 * (1e-12, 1e-10, 1e-8, 1e-6) on its diagonal, then
         numpy.linalg.LinAlgError.  An empty model raises ValueError."""
+        self._no_gradient("sample_posterior")
         if len(self.X) == 0:
             raise ValueError("sample_posterior needs a model with data")
         Q = _lib.f64(np.atleast_2d(np.asarray(X, dtype=float)))
@@ -406,12 +501,18 @@ class GaussianProcess(object):
     def addData(self, X, Y, G=None):
         """append observations (:267-308).  X (N,D) or (D,); Y vector or scalar.  A fitted model is extended
         as the reference does -- z = L^-1 m, d = chol(r - z^T z), here with W = L^-1 on the device (ibo_gp_extend,
-        O(N^2) per point); the first batch, large batches and a model whose row padding is full are (re)fitted."""
-        if G is not None:
-            raise NotImplementedError("gradient observations are not supported")
+        O(N^2) per point); the first batch, large batches and a model whose row padding is full are (re)fitted.
+        With G ((N, D) or (D,): the partial derivatives at every point) the model is observed with gradients: all the data are fitted
+        afresh as one N (D + 1)-row model (ibo_ggp_fit; no in-place extension), and a matrix that does not factor leaves the model as
+        it was.  A model takes G with every call or with none: ValueError otherwise."""
         X = np.array(X, dtype=float, ndmin=2)
         Y = np.array(Y, dtype=float, ndmin=1).flatten()
         assert len(Y) == len(X), 'wrong number of Y-observations given'
+        if (G is None) != (self.G is None) and len(self.X) > 0:
+            raise ValueError("this model %s gradient observations: every addData call of one model comes with G, or none does"
+                             % ("holds" if G is None else "was built without"))
+        if G is not None:
+            return self._add_gradient_data(X, Y, G)
         if len(self.X) == 0 and len(self.gnoise) == 1:
             self.gnoise = np.tile(self.gnoise, X.shape[1])
         oldX, oldY = self.X, self.Y
@@ -459,6 +560,7 @@ class GaussianProcess(object):
         update of the trailing factor and of W = L^-1, O(N^2) per row) while at most REMOVE_MAX rows go and kernel and noise are those of
         the fit, else the remaining data are refitted.  IndexError for a row that does not exist, ValueError for a row named twice or
         when no row would be left: the model is unchanged then.  _route ("device" / "refit") forces one route (tests)."""
+        self._no_gradient("removeData")
         import operator
         N = len(self.X)
         rows = []
@@ -514,9 +616,9 @@ class GaussianProcess(object):
 
     def __deepcopy__(self, memo):
         from copy import deepcopy
-        g = GaussianProcess(deepcopy(self.kernel, memo), prior=self.prior, noise=self.noise, device=self._device)
+        g = GaussianProcess(deepcopy(self.kernel, memo), prior=self.prior, noise=self.noise, gnoise=np.copy(self.gnoise), device=self._device)
         if len(self.X):
-            g.addData(self.X.copy(), self.Y.copy())
+            g.addData(self.X.copy(), self.Y.copy(), None if self.G is None else self.G.copy())
         return g
 
 
@@ -524,6 +626,9 @@ class PrefGaussianProcess(GaussianProcess):
     """GP trained on pairwise preferences (ego/gaussianprocess/__init__.py:331-527)."""
 
     def __init__(self, kernel, prefs=None, **kwargs):
+        if kwargs.get("G") is not None:
+            raise NotImplementedError("PrefGaussianProcess with gradient observations (G=): its targets are a MAP over preferences, "
+                                      "not observed values and slopes")
         super(PrefGaussianProcess, self).__init__(kernel, **kwargs)
         self.preferences = []
         self.C = None
@@ -822,6 +927,8 @@ class PrefGaussianProcess(GaussianProcess):
         self.augL = Lh
 
     def addData(self, X, Y, G=None):
+        if G is not None:
+            raise NotImplementedError("PrefGaussianProcess with gradient observations (G=)")
         if getattr(self, "preferences", None) is None:      # called from the base constructor
             return GaussianProcess.addData(self, X, Y, G)
         raise NotImplementedError("can't (yet) add explicit ratings to preference GP")

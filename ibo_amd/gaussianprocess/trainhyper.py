@@ -19,6 +19,13 @@ from numpy.linalg import LinAlgError
 from .. import _lib
 
 
+def _no_gradient_data(G, what):
+    """hyper-parameter learning is built for value observations: the likelihoods of an N (D + 1)-row gradient model are not"""
+    if G is not None:
+        raise NotImplementedError("%s with gradient observations (G=): hyper-parameter learning on gradient data is not available -- "
+                                  "the likelihood kernels factor K(X, X) of the values alone" % what)
+
+
 def _spec_rows(kernels):
     specs = [k._ibo_spec() for k in kernels]
     ktype = specs[0][0]
@@ -27,9 +34,10 @@ def _spec_rows(kernels):
     return ktype, thetas, sf2
 
 
-def nlml_values(kernels, X, Y, noise=1e-3, device=None, spec=None):
+def nlml_values(kernels, X, Y, noise=1e-3, device=None, spec=None, G=None):
     """NLML for a list of kernel objects of one class (a theta grid); NaN where K is not PD.
-    spec: (ktype, rows, sf2) as Kernel._ibo_spec_rows gives them, instead of the objects."""
+    spec: (ktype, rows, sf2) as Kernel._ibo_spec_rows gives them, instead of the objects.  G: refused (NotImplementedError)."""
+    _no_gradient_data(G, "nlml_values")
     X = _lib.rows(X); Y = _lib.f64(Y)
     N, D = X.shape
     ktype, thetas, sf2 = _spec_rows(kernels) if spec is None else spec
@@ -40,16 +48,18 @@ def nlml_values(kernels, X, Y, noise=1e-3, device=None, spec=None):
     return out
 
 
-def nlml_grid(Kernel, thetas, X, Y, noise=1e-3, device=None):
-    """NLML at every row of `thetas` (hyper-parameters, NOT logs); returns (values, argmin)."""
+def nlml_grid(Kernel, thetas, X, Y, noise=1e-3, device=None, G=None):
+    """NLML at every row of `thetas` (hyper-parameters, NOT logs); returns (values, argmin).  G: refused (NotImplementedError)."""
+    _no_gradient_data(G, "nlml_grid")
     vals = nlml_values(None, X, Y, noise, device, spec=Kernel._ibo_spec_rows(thetas))
     return vals, int(np.nanargmin(vals))
 
 
-def marginalLikelihood(kernel, X, Y, nhyper, computeGradient=True, useCholesky=True, noise=1e-3):
+def marginalLikelihood(kernel, X, Y, nhyper, computeGradient=True, useCholesky=True, noise=1e-3, G=None):
     """negative log marginal likelihood and (optionally) its partial derivatives w.r.t.
     each log hyper-parameter (trainhyper.py:47-95).  useCholesky is accepted for
-    signature compatibility; the device path always factors."""
+    signature compatibility; the device path always factors.  G: refused (NotImplementedError)."""
+    _no_gradient_data(G, "marginalLikelihood")
     NX = len(X)
     assert NX == len(Y)
     if not computeGradient:
@@ -124,12 +134,13 @@ def dnlml(loghyper, kernel, X, Y):
 
 
 # ---------------------------------------------------------------------------------------- leave-one-out cross-validation
-def looLikelihood(kernel, X, Y, nhyper, computeGradient=True, noise=1e-3, predictions=False):
+def looLikelihood(kernel, X, Y, nhyper, computeGradient=True, noise=1e-3, predictions=False, G=None):
     """the leave-one-out objective  sum_i [log(s2_-i) / 2 + (Y_i - mu_-i)^2 / (2 s2_-i) + log(2 pi) / 2]  of K = covMatrix + noise I
     (to be minimised, like marginalLikelihood) and, with computeGradient, its partial derivatives w.r.t. each log hyper-parameter:
     `value` or `(value, grad)`.  predictions=True appends (mu_-i, s2_-i), the leave-one-out predictions at this theta, as a
-    last element.  LinAlgError when K is not positive definite."""
+    last element.  LinAlgError when K is not positive definite.  G: refused (NotImplementedError)."""
     import ctypes
+    _no_gradient_data(G, "looLikelihood")
     assert len(X) == len(Y)
     Xa = _lib.rows(X); Ya = _lib.f64(Y)
     N, D = Xa.shape

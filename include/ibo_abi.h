@@ -56,7 +56,10 @@ extern "C" {
                              * + ibo_ehvi_sweep, ibo_ehvi_batch, ibo_ehvi_grad_batch, ibo_ehvi_direct_max (the expected hypervolume improvement of two
                              * objectives over a Pareto front), ibo_ehvi_scan_ms and the options "ehvi_chunk", "ehvi_timing": added within 8, nothing else changed;
                              * + ibo_paths_grad_batch (values and gradients of the pathwise draws with respect to x; "paths_chunk" bounds its pieces too):
-                             * added within 8, nothing else changed */
+                             * added within 8, nothing else changed;
+                             * + ibo_ggp_create, ibo_ggp_destroy, ibo_ggp_info, ibo_ggp_fit, ibo_ggp_get_R, ibo_ggp_get_L, ibo_ggp_acq_batch, ibo_ggp_acq_sweep,
+                             * ibo_ggp_direct_max, ibo_ggp_stage_ms (a GP observed with gradients, on a handle type of its own) and the options "ggp_chunk",
+                             * "ggp_timing": added within 8, nothing else changed */
 
 /* status codes */
 #define IBO_OK              0
@@ -108,7 +111,7 @@ int         ibo_selftest_mfma(int device, double *max_abs_err);
  * gradients.  DIRECT's small batches and the copies are not event-timed and not in it.  bench.py reports it as gpu_kernel_s_total
  * so that a line can be related to an outside observer's busy-GPU samples. */
 int         ibo_gpu_time_ms(int device, double *ms);
-/* The twenty option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
+/* The twenty-two option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
  * Functional:  "legacy_exact" 1/0 -- acqmaxGP in libego's operation order (default) or on the MFMA sweep kernels (see acqmaxGP);
  *   "nlml_batch" B -- matrices per batched factorisation in ibo_nlml_grid (0: as many as 12 GB hold; the values do not depend on it);
  *   "pool_limit_mb" n -- the per-device free list of recycled buffers (ibo_trim);
@@ -127,8 +130,9 @@ int         ibo_gpu_time_ms(int device, double *ms);
  *   0: by bytes, 2^30 / (16 (ncon + 1)) -- identical bits);  "paths_chunk" m (candidates per launch of the ibo_paths_* entries, rounded up to
  *   256, 0: 2^21 -- identical bits);  "qei_chunk" m (candidates per chunk of the ibo_qei_* entries, rounded up to 256, 0: by bytes --
  *   identical bits);  "ehvi_chunk" m (candidates per chunk of the ibo_ehvi_* entries, rounded up to 256, 0: by bytes, 2^25 -- identical bits
- *   among chunks of up to 4096 and among larger ones, see the ibo_ehvi_* entries).
- * Diagnostic:  "kg_timing" 1/0 (see ibo_kg_stage_ms);  "qei_timing" 1/0 (see ibo_qei_stage_ms);  "ehvi_timing" 1/0 (see ibo_ehvi_scan_ms).
+ *   among chunks of up to 4096 and among larger ones, see the ibo_ehvi_* entries);  "ggp_chunk" m (candidates per chunk of the ibo_ggp_* entries,
+ *   rounded up to 256, 0: by bytes -- identical bits).
+ * Diagnostic:  "ggp_timing" 1/0 (see ibo_ggp_stage_ms);  "kg_timing" 1/0 (see ibo_kg_stage_ms);  "qei_timing" 1/0 (see ibo_qei_stage_ms);  "ehvi_timing" 1/0 (see ibo_ehvi_scan_ms).
  * Env: IBO_SWEEP_IMPL=gemv|mfma, IBO_DOT_FORM, IBO_POOL_LIMIT_MB, IBO_HOST_THREADS (the legacy symbol's host crew), IBO_DEVICE (legacy symbols),
  *   IBO_NLML_GROUPS=1..4 (sub-batches of an ibo_nlml_grid batch, each on its own stream; 2; the values do not depend on it).
  * Threading (the reference's library keeps its whole model in process-wide statics, cpp/optimizeGP.cpp:36-55,240-259, and is not
@@ -803,6 +807,66 @@ int ibo_paths_grad_batch(ibo_paths_t *p, int64_t M, const double *Q_host, const 
  * path.  opt = the maximum, optx[D] its location, nsamples optional (not all three NULL). */
 int ibo_paths_direct_max(ibo_paths_t *p, int path, int D, const double *lb, const double *ub, int maxiter, int maxtime,
                          int maxsample, int compat, double *opt, double *optx, int64_t *nsamples);
+
+/* ---------------------------------------------------------------- gradient observations */
+/*
+ * A GP observed with gradients: at each of N points the value Y_i AND the D partial derivatives G_i (what the reference's constructor
+ * advertises as G= and never finished: ego/gaussianprocess/__init__.py:198-206 calls a covWithGradients that does not exist).  The model
+ * has P = N (D + 1) rows in POINT-MAJOR order, as the reference interleaves them: row i (D + 1) is the value at x_i, rows i (D + 1) + d
+ * (d = 1 .. D) are df/dx_d at x_i.  With u = x - x' (x the row's point, x' the column's) the (D + 1) x (D + 1) block of a pair is
+ *     [ k           dk/dx'_e        ]          dk/dx'_e = -dk/dx_e
+ *     [ dk/dx_d     d2k/dx_d dx'_e  ]
+ *   SE (w_d = 1/theta_d^2)          k = sf2 exp(-sum w_d u_d^2 / 2);  dk/dx_d = -w_d u_d k;  d2k = (w_d delta_de - w_d u_d w_e u_e) k
+ *   Matern-3/2 (z = sqrt 3 r/theta) k = sf2 (1 + z) e^-z;  dk/dx_d = -sf2 c u_d e^-z, c = 3/theta^2;  d2k = sf2 c e^-z (delta_de - sqrt 3 u_d u_e / (theta r)),
+ *                                   the second term 0 at r = 0
+ *   Matern-5/2 (s = sqrt 5 r/theta) k = sf2 e^-s (1 + s + s^2/3);  dk/dx_d = -sf2 c (1 + s) e^-s u_d, c = 5/(3 theta^2);
+ *                                   d2k = sf2 c e^-s ((1 + s) delta_de - (5/theta^2) u_d u_e)
+ * Diagonal: a value row keeps ibo_gp_fit's rule, 1 + noise; derivative row d gets d2k/dx_d dx'_d (0) + gnoise[d - 1].
+ * Posterior at q: k*(q) has the entries k(q, x_i) and dk(q, x_i)/dx_i,d; mu = k*^T A^-1 [Y; G] (interleaved), s2 = (1 + noise) - |W k*|^2
+ * clipped to [clamp_lo, 10], W = L^-1; EI / PI / UCB from (mu, s2) by the formula of every sweep, in both erf flavours.  ymax NaN: max(Y),
+ * over the values only.  ONE signal variance throughout (no ibo_gp_set_kstar_sf2: libego has no gradient models); no mean prior.
+ * The handle is its own type: no ibo_gp_* / ibo_acq_* entry accepts it.  One handle belongs to one thread at a time.
+ * The means are dot products over the k* rows (the row kernel of the knowledge gradient: lane l over the rows l, l + 64, .., then a fixed
+ * butterfly).  A candidate's bits depend on the model and its coordinates and on nothing else: not on M, its place, the chunking
+ * (ibo_set_option("ggp_chunk", m): candidates per chunk, rounded up to 256; 0: by bytes, 256 MiB of K*), nor on the entry.
+ * Cost: the fit is one P-row factorisation on the route of a plain fit of P rows; a candidate costs P^2 flops for V^T = K* W^T on the fp64
+ * MFMA pipe plus one exp per data point.  Device scratch per chunk: K* and V^T, mc Ppad doubles each, returned before the call returns.
+ * Errors: IBO_ERR_NO_DEVICE without a device (checked first); IBO_ERR_ARG for NULLs, M < 1, an unknown acq / erf_mode, every output NULL;
+ * IBO_ERR_STATE before a successful fit.
+ */
+typedef struct ibo_ggp ibo_ggp_t;
+#define IBO_GGP_MAX_ROWS 8192        /* P = N (D + 1) at most: the largest frame this unit's scratch (one 512 MiB frame for ibo_ggp_get_R) and
+                                      * all three fit routes -- pipelined, super-panels from 4096 rows, two-level from 6656 -- are sized for */
+int ibo_ggp_create(int device, ibo_ggp_t **out);
+int ibo_ggp_destroy(ibo_ggp_t *h);
+/* any of the outputs may be NULL; P = N (D + 1); max_y: the largest observed value */
+int ibo_ggp_info(ibo_ggp_t *h, int *N, int *D, int *P, int *device, double *max_y);
+/* X: N x D, Y: N, G: N x D (G[i][d] = df/dx_d at x_i), gnoise: D, all host.  hyper / nhyper / sf2 / noise as ibo_gp_fit.  IBO_ERR_NOT_PD
+ * with the 1-based failing pivot in *info (optional), as ibo_gp_fit: the handle is then UNFITTED.  IBO_ERR_ARG for N (D + 1) >
+ * IBO_GGP_MAX_ROWS, N < 1, D outside 1 .. 64. */
+int ibo_ggp_fit(ibo_ggp_t *h, int ktype, int N, int D, const double *X_host, const double *Y_host, const double *G_host /* N x D */,
+                const double *hyper_host, int nhyper, double sf2, double noise, const double *gnoise_host /* D */, int *info);
+/* P x P row-major, point-major rows.  R is A as factored (assembled again by the fit's kernel: the same bits); L its Cholesky factor */
+int ibo_ggp_get_R(ibo_ggp_t *h, double *R_host);
+int ibo_ggp_get_L(ibo_ggp_t *h, double *L_host);
+/* ibo_acq_batch's arguments: host points in (Q_host: M x D), any of mu / s2 / acq out (not all NULL) */
+int ibo_ggp_acq_batch(ibo_ggp_t *h, int64_t M, const double *Q_host, int acq, double parm, int erf_mode,
+                      double clamp_lo, double ymax, double *mu_host, double *s2_host, double *acq_host);
+/* Device candidates (cand_dev: M x D); optional DEVICE outputs (M doubles each); best_val / best_idx (host, optional) under the arg-max rule
+ * of ibo_acq_sweep: the largest value wins, the lowest index wins ties, NaN never wins, index_base is added; -inf and -1 when no value is
+ * a number.  No exclusion balls, no kept state, no exchange. */
+int ibo_ggp_acq_sweep(ibo_ggp_t *h, int64_t M, const double *cand_dev, int acq, double parm, int erf_mode,
+                      double clamp_lo, double ymax, int64_t index_base,
+                      double *mu_dev, double *s2_dev, double *acq_dev, double *best_val, int64_t *best_idx);
+/* ibo_direct_max on the gradient model: the same DIRECT, options and batched schedule, every batch evaluated as ibo_ggp_acq_batch does
+ * (ymax = max(Y)).  IBO_ERR_ARG also for IBO_ACQ_NONE, NULL bounds or D other than the model's. */
+int ibo_ggp_direct_max(ibo_ggp_t *h, int D, const double *lb, const double *ub, int acq, double parm, int erf_mode,
+                       double clamp_lo, int maxiter, int maxtime, int maxsample, int compat,
+                       double *opt, double *optx, int64_t *nsamples);
+/* ibo_kg_stage_ms for the ibo_ggp_* entries, under ibo_set_option("ggp_timing", 1): [0] the assembly of A, [1] K*, [2] V^T = K* W^T,
+ * [3] the row kernel, [4] unused (0), [5] the acquisition, [6] factor-and-invert, [7] the alpha vectors. */
+#define IBO_GGP_STAGES 8
+int ibo_ggp_stage_ms(double *ms, int reset);
 
 /* DIRECT minimisation of a HOST callback with the reference's semantics
  * (cpp/direct.cpp:329; what ego.utils.optimize.cdirect wraps), plus the sample
