@@ -70,7 +70,10 @@ int RowPipeline::chunk(int m, const double *pts, double *out)
     IBO_TRY(tail(m, mp, pts, out));
     if (clock.on) {
         HIP_TRY(hipStreamSynchronize(s));
-        for (int k = 0; k < 5; k++) IBO_TRY(clock.account(k, k + 1, ST_KSTAR + k));
+        for (int k = 0; k < 5; k++) {
+            if (ST_KSTAR + k == ST_CROSS && !ldx) continue;      // no cross block, no cross launch: the gap between two marks is no stage (the slot stays 0)
+            IBO_TRY(clock.account(k, k + 1, ST_KSTAR + k));
+        }
     }
     return IBO_OK;
 }

@@ -1,6 +1,7 @@
 """
-A GP observed with gradients (csrc/gradobs.h, ibo_ggp_* in include/ibo_abi.h) restated in NumPy, for tests/test_gpu_gradobs.py; pinned
-to mpmath differentiation of the kernels' defining formulas, to the oracle and to long double by tests/test_gradobs_reference.py.
+A GP observed with gradients (csrc/gradobs.h, ibo_ggp_* in include/ibo_abi.h) restated in NumPy, for tests/test_gpu_gradobs.py (CASES)
+and tests/test_gpu_gradobs_routes.py (EDGE_CASES); pinned to mpmath differentiation of the kernels' defining formulas, to the oracle
+and to long double by tests/test_gradobs_reference.py.
 
 Rows are point-major: row i (D + 1) is the value at x_i, rows i (D + 1) + d (d = 1 .. D) are df/dx_d at x_i; P = N (D + 1).  For an
 oracle.Kern (w_d = 1 / theta_d^2, sf2 = sf2_py), u = x - x' (x the row's point, x' the column's), z = sum_d w_d u_d^2, t_d = w_d u_d:
@@ -41,6 +42,28 @@ CASES = [
 CASE_NAMES = [c[0] for c in CASES]
 QUERY_COUNTS = (1, 63, 64, 65, 130)
 GNOISE = 1e-4                     # the constructor's default, tiled to D
+
+# (name, oracle kind, hyper, N, D, noise, gnoise -- a number or one entry per dimension --, coincident pair or None): the cases of
+# tests/test_gpu_gradobs_routes.py.  A case of more than BIG_ROWS rows is BIG: never cached, held to float64, and admissible only with
+# cond_upper <= 1e6 (tests/test_gradobs_reference.py asserts it), where the bars' factor 1e-15 max(cond, 1e6) is its floor 1e-9.
+BIG_ROWS = 2000
+EDGE_CASES = [
+    ("ard_257x1", "ard", [0.5], 257, 1, 0.1, 1e-4, None),                          # P = 514: the second k* block holds one point and the pad
+    ("m5_300x2", "m5", [0.5, 0.9], 300, 2, 0.1, 1e-4, None),                       # P = 900: the k* block border falls inside a store pass
+    ("m3_513x1", "m3", [0.6, 0.9], 513, 1, 0.1, 0.02, (2, 400)),                   # P = 1026: three k* blocks, r = 0 across blocks
+    ("ard_60x3_gn", "ard", [0.5, 0.7, 0.6], 60, 3, 0.1, [1e-4, 3e-3, 0.05], None), # a gnoise of its own per dimension
+    ("sviso_20x2", "sviso", [0.6, 0.9], 20, 2, 0.1, 1e-4, None),                   # SE with sf2 = 0.81
+    ("se_3x64", "iso", [4.0], 3, 64, 0.1, 1e-4, None),                             # D = IBO_DMAX
+    ("ard_525x3", "ard", [0.5, 0.7, 0.6], 525, 3, 0.1, 0.05, None),                # P = 2100: 33 block columns, for the forced routes
+    ("ard_1008x3", "ard", [0.5, 0.7, 0.6], 1008, 3, 0.1, 0.05, None),              # P = 4032: 63 block columns, the last pipelined fit
+    ("ard_1009x3", "ard", [0.5, 0.7, 0.6], 1009, 3, 0.1, 0.05, None),              # P = 4036, Npad 4096: the first fit in super-panels
+    ("m5_1648x3", "m5", [0.5, 0.9], 1648, 3, 0.1, 0.05, None),                     # P = 6592: 103 block columns, the last in super-panels
+    ("m3_1649x3", "m3", [0.6, 0.9], 1649, 3, 0.1, 0.05, None),                     # P = 6596, Npad 6656: the first two-level fit
+    ("iso_2048x3", "iso", [0.6], 2048, 3, 0.1, 0.05, None),                        # P = 8192 = IBO_GGP_MAX_ROWS
+]
+EDGE_NAMES = [c[0] for c in EDGE_CASES]
+SMALL_EDGE_NAMES = [c[0] for c in EDGE_CASES if c[3] * (c[4] + 1) <= BIG_ROWS]
+BIG_NAMES = [c[0] for c in EDGE_CASES if c[3] * (c[4] + 1) > BIG_ROWS]
 
 
 def weights(kern, D):
@@ -100,6 +123,24 @@ def matrix(kern, X, noise, gnoise, dt=np.float64):
     return A
 
 
+def cond_upper(kern, X, noise, gnoise):
+    """|A|_inf / min(1 + noise - sf2, min_d gnoise_d) >= cond_2(A).  A is the derivative covariance C (positive semi-definite, value
+    diagonal sf2) plus the diagonal (1 + noise - sf2, gnoise_1 .. gnoise_D) per point, so lambda_min(A) >= the smallest entry of that
+    diagonal (sf2 <= 1 + noise is required), and lambda_max(A) <= |A|_inf for a symmetric matrix.  Row sums in slabs of points: never
+    more than a slab of A at a time."""
+    X = np.asarray(X, dtype=np.float64)
+    N, D = X.shape
+    gn = tile_gnoise(gnoise, D)
+    assert kern.sf2_py <= 1.0 + noise, "cond_upper needs sf2 <= 1 + noise"
+    extra = np.concatenate([[1.0 + noise - kern.sf2_py], gn])           # what the diagonal rule adds to C's (positive) diagonal
+    assert np.all(extra > 0.0)
+    worst = 0.0
+    for i0 in range(0, N, 64):
+        rows = np.sum(np.abs(blocks(kern, X[i0:i0 + 64], X)), axis=(1, 3)) + extra[None, :]
+        worst = max(worst, float(np.max(rows)))
+    return worst / float(np.min(extra))
+
+
 def kstar(kern, X, Q, dt=np.float64):
     """(M, P): row c holds k(q_c, x_i) and dk(q_c, x_i) / dx_i,d, point-major"""
     B = blocks(kern, Q, X, dt)
@@ -146,7 +187,8 @@ def backward_ld(L, B):
 
 
 def fit(kern, X, Y, G, noise, gnoise, longdouble=False):
-    """dict(A, L, alpha, cond, N, D, P, kern, X, noise, dt): the factored model.  cond: cond_2 of the float64 A."""
+    """dict(A, L, alpha, cond, N, D, P, kern, X, noise, dt): the factored model.  cond: cond_2 of the float64 A; of more than BIG_ROWS
+    rows: cond_upper, in place of an SVD of up to 8192 rows."""
     import scipy.linalg as sl
     dt = np.longdouble if longdouble else np.float64
     X = np.asarray(X, dtype=np.float64)
@@ -159,7 +201,7 @@ def fit(kern, X, Y, G, noise, gnoise, longdouble=False):
     else:
         L = np.linalg.cholesky(A)
         alpha = sl.solve_triangular(L, sl.solve_triangular(L, y, lower=True), lower=True, trans="T")
-    cond = float(np.linalg.cond(np.asarray(A, dtype=np.float64)))
+    cond = cond_upper(kern, X, noise, gnoise) if len(A) > BIG_ROWS else float(np.linalg.cond(np.asarray(A, dtype=np.float64)))
     return dict(A=A, L=L, alpha=alpha, cond=cond, N=N, D=D, P=N * (D + 1), kern=kern, X=X, noise=float(noise), dt=dt,
                 maxY=float(np.max(Y)))
 
@@ -231,27 +273,54 @@ def queries(X, M, seed=7):
     return Q
 
 
-@functools.lru_cache(maxsize=None)
-def case(name):
-    """dict(name, kern, X, Y, G, noise, gnoise) of a listed case"""
-    name, kind, hyper, N, D, noise, twin = CASES[CASE_NAMES.index(name)]
-    X = points(N, D, 100 + CASE_NAMES.index(name))
+def is_big(name):
+    return name in BIG_NAMES
+
+
+def _make_case(name):
+    if name in CASE_NAMES:
+        name, kind, hyper, N, D, noise, twin = CASES[CASE_NAMES.index(name)]
+        gnoise, seed = GNOISE, 100 + CASE_NAMES.index(name)
+    else:
+        name, kind, hyper, N, D, noise, gnoise, twin = EDGE_CASES[EDGE_NAMES.index(name)]
+        seed = 200 + EDGE_NAMES.index(name)
+    X = points(N, D, seed)
     if twin is not None:
         X[twin[1]] = X[twin[0]]
     Y, G = objective(X)
     for a in (X, Y, G):
         a.setflags(write=False)
-    return dict(name=name, kern=orc.Kern(kind, hyper), X=X, Y=Y, G=G, noise=noise, gnoise=tile_gnoise(GNOISE, D))
+    return dict(name=name, kern=orc.Kern(kind, hyper), X=X, Y=Y, G=G, noise=noise, gnoise=tile_gnoise(gnoise, D))
 
 
-@functools.lru_cache(maxsize=None)
-def case_model(name, longdouble=False):
-    """the factored reference model of a listed case, computed once"""
+_cached_case = functools.lru_cache(maxsize=None)(_make_case)
+
+
+def case(name):
+    """dict(name, kern, X, Y, G, noise, gnoise) of a case of either list; a big one is made anew on every call"""
+    return _make_case(name) if is_big(name) else _cached_case(name)
+
+
+def _make_model(name, longdouble=False):
     c = case(name)
     return fit(c["kern"], c["X"], c["Y"], c["G"], c["noise"], c["gnoise"], longdouble)
 
 
+_cached_model = functools.lru_cache(maxsize=None)(_make_model)
+
+
+def case_model(name, longdouble=False):
+    """the factored reference model of a case of either list; computed once, except a big one: float64 and made anew on every call"""
+    if is_big(name):
+        assert not longdouble
+        return _make_model(name, False)
+    return _cached_model(name, longdouble)
+
+
 def reference_model(name):
-    """the model the device is held to: long double wherever cond_2 > 1e6"""
+    """the model the device is held to: long double wherever cond_2 > 1e6; a big case: float64 under cond_upper <= 1e6"""
     m = case_model(name, False)
+    if is_big(name):
+        assert m["cond"] <= 1e6, "%s is not admissible: cond_upper %.3g" % (name, m["cond"])
+        return m
     return case_model(name, True) if m["cond"] > 1e6 else m

@@ -182,6 +182,99 @@ def test_the_case_list_holds_what_was_asked_for():
     assert gr.QUERY_COUNTS == (1, 63, 64, 65, 130)
 
 
+# ---------------------------------------------------------------------------- the second case list: a gnoise per dimension, big cases
+EDGE_P = {"ard_257x1": 514, "m5_300x2": 900, "m3_513x1": 1026, "ard_60x3_gn": 240, "sviso_20x2": 60, "se_3x64": 195, "ard_525x3": 2100,
+          "ard_1008x3": 4032, "ard_1009x3": 4036, "m5_1648x3": 6592, "m3_1649x3": 6596, "iso_2048x3": 8192}
+
+
+def test_the_edge_case_list_holds_what_was_asked_for():
+    assert sorted(EDGE_P) == sorted(gr.EDGE_NAMES) and not set(gr.EDGE_NAMES) & set(gr.CASE_NAMES)
+    assert sorted(gr.SMALL_EDGE_NAMES + gr.BIG_NAMES) == sorted(gr.EDGE_NAMES)
+    assert gr.BIG_NAMES == [n for n in gr.EDGE_NAMES if EDGE_P[n] > 2000]
+    for name in gr.SMALL_EDGE_NAMES:
+        c = gr.case(name)
+        N, D = c["X"].shape
+        assert N * (D + 1) == EDGE_P[name] and c["gnoise"].shape == (D,)
+        assert np.max(np.abs(c["X"])) <= 1.0 and np.max(np.abs(c["Y"])) <= 1.0 and np.max(np.abs(c["G"])) <= 1.0
+        assert gr.case(name) is c                                   # small: made once
+    assert np.array_equal(gr.case("ard_60x3_gn")["gnoise"], [1e-4, 3e-3, 0.05])
+    assert np.all(gr.case("m3_513x1")["gnoise"] == 0.02)
+    c = gr.case("m3_513x1")
+    assert np.array_equal(c["X"][2], c["X"][400])
+    assert abs(gr.case("sviso_20x2")["kern"].sf2_py - 0.81) < 1e-15 and gr.case("sviso_20x2")["kern"].ktype == orc.K_SE_ISO
+    assert gr.case("se_3x64")["X"].shape == (3, 64)
+    big = gr.case("ard_525x3")
+    assert gr.is_big("ard_525x3") and gr.case("ard_525x3") is not big and np.array_equal(gr.case("ard_525x3")["X"], big["X"])
+    assert all(np.all(gr.case(n)["gnoise"] == 0.05) for n in ("ard_525x3", "ard_1009x3"))
+    # the listed cases are what they were: the same seeds, the default gnoise
+    assert np.array_equal(gr.case("ard_13x4")["X"], gr.points(13, 4, 103)) and np.all(gr.case("ard_13x4")["gnoise"] == 1e-4)
+
+
+def test_a_vector_gnoise_lands_on_its_own_derivative_rows_and_nowhere_else():
+    """matrix() with three distinct gnoise entries, every entry against mpmath differentiation of the kernel's defining formula plus the
+    diagonal rule: 1 + noise on a value row, the second derivative at u = 0 plus gnoise[d - 1] on derivative row d, nothing else anywhere"""
+    kind, hyper, N, D, noise = "ard", FAMILY_HYPER["ard"][:3], 3, 3, 0.1
+    gnoise = np.array([1e-4, 3e-3, 0.05])
+    kern = orc.Kern(kind, hyper)
+    X = gr.points(N, D, 31)
+    A = gr.matrix(kern, X, noise, gnoise)
+    scale = kern.sf2_py * max(1.0, float(np.max(gr.weights(kern, D))))
+    B = D + 1
+    old = mpmath.mp.dps
+    mpmath.mp.dps = 30
+    try:
+        f = mp_cov(kind, hyper, D)
+        for i in range(N):
+            for j in range(N):
+                at = [mpmath.mpf(repr(float(v))) for v in np.r_[X[i], X[j]]]
+                for a in range(B):
+                    for b in range(B):
+                        order = [0] * (2 * D)
+                        if a:
+                            order[a - 1] += 1
+                        if b:
+                            order[D + b - 1] += 1
+                        want = f(*at) if not (a or b) else mpmath.diff(f, tuple(at), tuple(order))
+                        if i == j and a == b:
+                            want = mpmath.mpf(1) + mpmath.mpf(noise) if a == 0 else want + mpmath.mpf(float(gnoise[a - 1]))
+                        err = abs(mpmath.mpf(float(A[i * B + a, j * B + b])) - want)
+                        assert err <= 1e-13 * scale, (i, j, a, b, float(err), float(want))
+    finally:
+        mpmath.mp.dps = old
+    diff = A - gr.matrix(kern, X, noise, 0.0)
+    assert np.array_equal(diff - np.diag(np.diag(diff)), np.zeros_like(A))
+    assert np.max(np.abs(np.diag(diff) - np.tile(np.r_[0.0, gnoise], N))) <= 1e-13 * scale < 0.1 * np.min(np.diff(gnoise))
+    assert np.array_equal(gr.matrix(kern, X, noise, 3e-3), gr.matrix(kern, X, noise, [3e-3] * 3))      # a number is tiled
+
+
+@pytest.mark.parametrize("name", gr.CASE_NAMES + gr.SMALL_EDGE_NAMES)
+def test_cond_upper_bounds_cond_2_on_the_small_cases(name):
+    c = gr.case(name)
+    up, cond = gr.cond_upper(c["kern"], c["X"], c["noise"], c["gnoise"]), gr.case_model(name)["cond"]
+    print("%s: cond_2 %.4g, cond_upper %.4g" % (name, cond, up))
+    assert up >= cond >= 1.0
+    A = gr.matrix(c["kern"], c["X"], c["noise"], c["gnoise"])
+    lo = min(1.0 + c["noise"] - c["kern"].sf2_py, float(np.min(c["gnoise"])))
+    assert abs(up * lo / float(np.max(np.sum(np.abs(A), axis=1))) - 1.0) < 1e-12      # the slabs' row sums are |A|_inf (summed in another order)
+
+
+def test_cond_upper_refuses_a_signal_variance_above_the_value_diagonal():
+    X = gr.points(4, 2, 1)
+    with pytest.raises(AssertionError):
+        gr.cond_upper(orc.Kern("m5", [0.5, 1.2]), X, 0.1, 1e-4)     # sf2 = 1.44 > 1.1
+
+
+@pytest.mark.parametrize("name", gr.BIG_NAMES)
+def test_every_big_case_is_admissible_in_float64(name):
+    """cond_upper <= 1e6: the bars' factor 1e-15 max(cond, 1e6) is then its floor 1e-9 and float64 the reference the rule selects"""
+    c = gr.case(name)
+    N, D = c["X"].shape
+    up = gr.cond_upper(c["kern"], c["X"], c["noise"], c["gnoise"])
+    print("%s: P %d, cond_upper %.4g" % (name, N * (D + 1), up))
+    assert N * (D + 1) == EDGE_P[name] > gr.BIG_ROWS and up <= 1e6
+    assert 1e-15 * max(up, 1e6) == 1e-9
+
+
 def test_the_acquisition_restatement_is_the_oracles():
     rs = np.random.RandomState(3)
     mu, s2 = rs.randn(50) * 0.5, rs.rand(50) + 1e-3
