@@ -8,6 +8,7 @@ misterwindupbird/IBO, behind the reference's own Python API.
     from ibo_amd.acquisition.gallery import fastUCBGallery
     from ibo_amd.acquisition.constrained import Constraint, sweepConstrained, maximizeCEI, ConstrainedEI, feasibleIncumbent
     from ibo_amd.acquisition.multiobjective import sweepEHVI, maximizeEHVI, ExpectedHypervolumeImprovement, paretoFront, hypervolume
+    from ibo_amd.acquisition.entropy import maxValueSamples, MaxValueEntropy, sweepMES, maximizeMES
     from ibo_amd.utils.optimize import direct, cdirect
     from ibo_amd.utils.latinhypercube import lhcSample
     from ibo_amd.utils.testfunctions import Hartman6, Shekel5, Synthetic, learnHyper

@@ -5,9 +5,10 @@ The library is the product's ONLY compute path: if it is missing this module
 raises at import, and every compute call raises IBOError(IBO_ERR_NO_DEVICE)
 when no MI355X is visible.  Nothing here falls back to NumPy.
 
-Every symbol of the header is bound below and listed in EXPORTED (98 of them: tests/test_cpu_host.py holds the two lists to
+Every symbol of the header is bound below and listed in EXPORTED (104 of them: tests/test_cpu_host.py holds the two lists to
 the header and to the library), the ibo_qei_* entries of the parallel expected improvement and the ibo_ehvi_* entries of the
-two-objective hypervolume improvement and the ibo_ggp_* entries of a GP observed with gradients among them.
+two-objective hypervolume improvement, the ibo_ggp_* entries of a GP observed with gradients and the ibo_mes_* entries of
+max-value entropy search among them.
 """
 import ctypes
 import os
@@ -122,6 +123,13 @@ _sig("ibo_ehvi_batch", c_int, *(_EHVI + (c_int64, _DP, c_int, c_double, _DP)))
 _sig("ibo_ehvi_grad_batch", c_int, *(_EHVI + (c_int64, _DP, c_int, c_double, _DP, _DP)))
 _sig("ibo_ehvi_direct_max", c_int, *(_EHVI + (c_int, _DP, _DP, c_int, c_double, c_int, c_int, c_int, c_int, _DP, _DP, POINTER(c_int64))))
 _sig("ibo_ehvi_scan_ms", c_int, _DP, c_int)
+_MES = (c_void_p, c_int, _DP, c_double)                                    # gp, K, ystar_host, s2_offset of the ibo_mes_* value entries
+_sig("ibo_mes_sweep", c_int, *(_MES + (c_int64, c_void_p, c_double, c_int, _DP, c_double, c_int64, c_void_p, _DP, POINTER(c_int64))))
+_sig("ibo_mes_batch", c_int, *(_MES + (c_int64, _DP, c_double, _DP)))
+_sig("ibo_mes_grad_batch", c_int, *(_MES + (c_int64, _DP, c_double, _DP, _DP)))
+_sig("ibo_mes_direct_max", c_int, *(_MES + (c_int, _DP, _DP, c_double, c_int, c_int, c_int, c_int, _DP, _DP, POINTER(c_int64))))
+_sig("ibo_mes_maxcdf", c_int, c_void_p, c_int64, c_void_p, c_int, _DP, c_double, c_double, _DP, _DP)
+_sig("ibo_mes_scan_ms", c_int, _DP, c_int)
 _KG = (c_void_p, c_int, _DP)                                               # gp, nref, ref_host of the ibo_kg_* entries
 _sig("ibo_kg_sweep", c_int, *(_KG + (c_int64, c_void_p, c_int, c_double, c_int64, c_void_p, _DP, POINTER(c_int64))))
 _sig("ibo_kg_batch", c_int, *(_KG + (c_int64, _DP, c_int, c_double, _DP, _DP, _DP, _DP, _DP)))
@@ -180,7 +188,7 @@ EXPORTED = ["ibo_abi_version", "ibo_last_error", "ibo_device_count", "ibo_device
             "ibo_device_synchronize", "ibo_dev_generation", "ibo_gp_create", "ibo_gp_destroy", "ibo_gp_fit", "ibo_gp_fit_with_matrix",
             "ibo_gp_extend", "ibo_gp_reserve", "ibo_gp_remove", "ibo_pref_begin", "ibo_pref_rinv_mul", "ibo_pref_newton_step", "ibo_pref_finish", "ibo_gp_set_y", "ibo_gp_set_kstar_sf2", "ibo_gp_set_prior", "ibo_gp_get_R", "ibo_gp_get_L",
             "ibo_gp_get_W", "ibo_gp_info", "ibo_gp_last_fit_ms", "ibo_cov_matrix", "ibo_spd_solve", "ibo_spd_inverse", "ibo_posterior_batch",
-            "ibo_acq_sweep", "ibo_acq_batch", "ibo_acq_grad_batch", "ibo_posterior_cov", "ibo_posterior_sample", "ibo_acq_sweep_incremental", "ibo_sweep_state_info", "ibo_sweep_state_levels", "ibo_last_sweep_kernel_ms", "ibo_direct_max", "ibo_cacq_sweep", "ibo_cacq_batch", "ibo_cacq_grad_batch", "ibo_cacq_direct_max", "ibo_ehvi_sweep", "ibo_ehvi_batch", "ibo_ehvi_grad_batch", "ibo_ehvi_direct_max", "ibo_ehvi_scan_ms", "ibo_kg_sweep", "ibo_kg_batch", "ibo_kg_direct_max", "ibo_kg_stage_ms", "ibo_qei_sweep", "ibo_qei_batch", "ibo_qei_direct_max", "ibo_qei_stage_ms", "ibo_paths_create", "ibo_paths_destroy", "ibo_paths_info", "ibo_paths_coef", "ibo_paths_sweep", "ibo_paths_batch", "ibo_paths_grad_batch", "ibo_paths_direct_max",
+            "ibo_acq_sweep", "ibo_acq_batch", "ibo_acq_grad_batch", "ibo_posterior_cov", "ibo_posterior_sample", "ibo_acq_sweep_incremental", "ibo_sweep_state_info", "ibo_sweep_state_levels", "ibo_last_sweep_kernel_ms", "ibo_direct_max", "ibo_cacq_sweep", "ibo_cacq_batch", "ibo_cacq_grad_batch", "ibo_cacq_direct_max", "ibo_ehvi_sweep", "ibo_ehvi_batch", "ibo_ehvi_grad_batch", "ibo_ehvi_direct_max", "ibo_ehvi_scan_ms", "ibo_mes_sweep", "ibo_mes_batch", "ibo_mes_grad_batch", "ibo_mes_direct_max", "ibo_mes_maxcdf", "ibo_mes_scan_ms", "ibo_kg_sweep", "ibo_kg_batch", "ibo_kg_direct_max", "ibo_kg_stage_ms", "ibo_qei_sweep", "ibo_qei_batch", "ibo_qei_direct_max", "ibo_qei_stage_ms", "ibo_paths_create", "ibo_paths_destroy", "ibo_paths_info", "ibo_paths_coef", "ibo_paths_sweep", "ibo_paths_batch", "ibo_paths_grad_batch", "ibo_paths_direct_max",
             "ibo_ggp_create", "ibo_ggp_destroy", "ibo_ggp_info", "ibo_ggp_fit", "ibo_ggp_get_R", "ibo_ggp_get_L", "ibo_ggp_acq_batch", "ibo_ggp_acq_sweep",
             "ibo_ggp_direct_max", "ibo_ggp_stage_ms", "ibo_direct_host", "ibo_nlml_grid", "ibo_nlml_grad", "ibo_gp_loo", "ibo_loo_grad",
             "ibo_comm_get_unique_id", "ibo_comm_init", "ibo_comm_destroy", "ibo_comm_count", "ibo_comm_argmax", "ibo_comm_allreduce_sum", "ibo_acq_sweep_exchange", "ibo_comm_barrier",

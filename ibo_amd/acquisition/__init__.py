@@ -20,6 +20,8 @@ Two objectives -- the expected hypervolume improvement over a Pareto front (mult
 constrained.py): sweepEHVI, maximizeEHVI, ExpectedHypervolumeImprovement, paretoFront, hypervolume, observedFront.
 Posterior draws as functions -- Thompson sampling over whole candidate arrays (pathwise.py): PosteriorPaths, spectralDraws;
 with .gradient / .negf_grad (ibo_paths_grad_batch), .maximize(polish=True) and .maxima, every path's maximum by a lock-step ascent.
+Max-value entropy search against samples of the maximum's value, exact (path maxima) or from a Gumbel fit that also serves a
+preference GP (entropy.py): MaxValueEntropy, maxValueSamples, sweepMES, maximizeMES, gumbelFit.
 
 The default maximize* path is the reference's cdirectGP -> acqmaxGP -> DIRECT
 (ego/acquisition/__init__.py:307-447, cpp/optimizeGP.cpp:262-349) with the tree
@@ -406,3 +408,4 @@ def _sweep_gradient(model, candidates, acq, xi, delta, scale, parm, native, ymax
 from .knowledge import KnowledgeGradient, sweepKG, maximizeKG, referenceSet          # noqa: E402,F401
 from .batch import baseSamples, ParallelEI, sweepQEI, maximizeQEI, jointQEI, proposeBatch      # noqa: E402,F401
 from .pathwise import PosteriorPaths, spectralDraws                                  # noqa: E402,F401
+from .entropy import MaxValueEntropy, maxValueSamples, sweepMES, maximizeMES, gumbelFit      # noqa: E402,F401

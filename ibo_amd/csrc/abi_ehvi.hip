@@ -51,28 +51,12 @@ static int ehvi_begin(ibo_gp_t *const *obj, int nfront, const double *front_host
     return IBO_OK;
 }
 
-// run_sweep picks its kernels by the size of the launch, and two of its routes agree to rounding only.  So that a candidate's (mu, s2) -- and
-// with them its value -- do not depend on how many candidates travel with it, a short launch is padded (with candidates at the origin, whose
-// results nobody reads) to the size class of the call's chunk `mc`:
-//   mc <= 4096  small2.hip's kernels.  Up to 128 candidates of a small model they are fused into one (launch_sweep_small: `local`, another
-//               order of the sums): such a launch runs as 160 candidates, beyond the fused form's reach for every model;
-//   mc >  4096  sweep2_kernel (choose_route): a tail of up to 4096 candidates runs as 4097.
-// (Where the dot form is not admissible run_sweep has other routes and other thresholds; there the entries agree to rounding.)
-#define EHVI_PAD_SMALL_FROM 128
-#define EHVI_PAD_SMALL_TO 160
-#define EHVI_PAD_LARGE_FROM 4096
-static int64_t ehvi_padded(int64_t m, int64_t mc)
-{
-    if (mc <= EHVI_PAD_LARGE_FROM) return m <= EHVI_PAD_SMALL_FROM ? EHVI_PAD_SMALL_TO : m;
-    return m <= EHVI_PAD_LARGE_FROM ? EHVI_PAD_LARGE_FROM + 1 : m;
-}
-
 // What a call may ask of the device pass beside the arg-max: the values, and the gradient's sums (six arrays M apart)
 struct EhviOut { double *val_dev = nullptr, *sums_dev = nullptr; double *best_val = nullptr; int64_t *best_idx = nullptr; };
 
 // The one route of every entry: per chunk the two plain sweeps -- (mu, s2) into pooled scratch, 32 bytes per candidate, no arg-max, no
 // read-back, one after the other (the same handle may be both) -- then ehvi_finish_kernel on the first model's stream.
-// cand_rows: the rows cand_dev has room for (>= M; rows from M on are the caller's padding, see ehvi_padded).
+// cand_rows: the rows cand_dev has room for (>= M; rows from M on are the caller's padding, see class_padded).
 static int ehvi_device(const EhviCall &c, int64_t M, const double *cand_dev, int64_t cand_rows, int n_excl, const double *excl_host,
                        double excl_radius, int64_t index_base, const EhviOut &o)
 {
@@ -88,7 +72,7 @@ static int ehvi_device(const EhviCall &c, int64_t M, const double *cand_dev, int
     if (g_ehvi_chunk > 0) mc = ((int64_t)g_ehvi_chunk + 255) / 256 * 256;
     if (M <= mc) mc = M;
     const int64_t nblk = (M + 255) / 256;
-    const int64_t stride = ehvi_padded(mc, mc);                // (every launch of the call fits: a tail is padded to at most mc's own size class)
+    const int64_t stride = class_padded(mc, mc);               // (every launch of the call fits: a tail is padded to at most mc's own size class)
     ScopedBuf<double> ms, pv, pad;
     ScopedBuf<int64_t> pi;
     IBO_TRY(ms.ensure(4 * (size_t)stride));
@@ -102,7 +86,7 @@ static int ehvi_device(const EhviCall &c, int64_t M, const double *cand_dev, int
     if (timing) { HIP_TRY(hipEventCreate(&ev.e0)); HIP_TRY(hipEventCreate(&ev.e1)); }
     a.ms = ms.p; a.stride = stride; a.sums_stride = M;
     for (int64_t c0 = 0; c0 < M; c0 += mc) {
-        const int64_t m = M - c0 < mc ? M - c0 : mc, mp = ehvi_padded(m, mc);
+        const int64_t m = M - c0 < mc ? M - c0 : mc, mp = class_padded(m, mc);
         SweepRequest r;
         r.M = mp; r.cand_dev = cand_dev + c0 * D; r.acq = IBO_ACQ_NONE; r.erf_mode = c.erf_mode; r.clamp_lo = c.clamp_lo;
         if (c0 + mp > cand_rows) {                              // a short launch of the caller's array: its candidates, then the padding
@@ -153,7 +137,7 @@ static int ehvi_eval_host(const EhviCall &c, int64_t M, const double *Q_host, do
 {
     const size_t m = (size_t)M;
     hipStream_t s = c.g1->stream;
-    const size_t rows = (size_t)ehvi_padded(M, M), D = (size_t)c.g1->D;       // (a short batch carries its padding: no copy on the device)
+    const size_t rows = (size_t)class_padded(M, M), D = (size_t)c.g1->D;      // (a short batch carries its padding: no copy on the device)
     ScopedBuf<double> q, out;
     IBO_TRY(q.ensure(rows * D)); IBO_TRY(out.ensure(m * (sums ? 7 : 1)));
     HIP_TRY(hipMemcpyAsync(q.p, Q_host, sizeof(double) * m * D, hipMemcpyHostToDevice, s));

@@ -1,5 +1,5 @@
-// abi_eval.h -- what the evaluation units (abi_sweep.hip, abi_batch.hip, abi_cacq.hip, abi_ehvi.hip, abi_kg.hip, abi_paths.hip, abi_qei.hip, abi_gradobs.hip, abi_rows.hip) share beyond
-// abi_internal.h: the sweep request, the host batch, and the ONE copy of the arg-max read-back, the exclusion upload, the timed span, the V^T rows and the DIRECT driver.
+// abi_eval.h -- what the evaluation units (abi_sweep.hip, abi_batch.hip, abi_cacq.hip, abi_ehvi.hip, abi_mes.hip, abi_kg.hip, abi_paths.hip, abi_qei.hip, abi_gradobs.hip, abi_rows.hip) share beyond
+// abi_internal.h: the sweep request, the host batch, and the ONE copy of the arg-max read-back, the exclusion upload, the padding of a short sweep to its size class, the timed span, the V^T rows and the DIRECT driver.
 #pragma once
 #include "abi_internal.h"
 
@@ -30,6 +30,22 @@ int read_result(ibo_gp *g, double *best_val, int64_t *best_idx);
 int argmax_readback(ibo_gp *g, const double *part_val, const int64_t *part_idx, int64_t nblk, double *best_val, int64_t *best_idx);
 // closes the span an entry opened by recording ev0: records ev1, waits for it and adds ev0 -> ev1 to the device's GPU time
 int finish_span(ibo_gp *g);
+
+// run_sweep picks its kernels by the size of the launch, and two of its routes agree to rounding only.  So that a candidate's (mu, s2) -- and
+// with them its value -- do not depend on how many candidates travel with it, a short launch is padded (with candidates at the origin, whose
+// results nobody reads) to the size class of the call's chunk `mc`:
+//   mc <= 4096  small2.hip's kernels.  Up to 128 candidates of a small model they are fused into one (launch_sweep_small: `local`, another
+//               order of the sums): such a launch runs as 160 candidates, beyond the fused form's reach for every model;
+//   mc >  4096  sweep2_kernel (choose_route): a tail of up to 4096 candidates runs as 4097.
+// (Where the dot form is not admissible run_sweep has other routes and other thresholds; there the entries agree to rounding.)
+#define CLASS_PAD_SMALL_FROM 128
+#define CLASS_PAD_SMALL_TO 160
+#define CLASS_PAD_LARGE_FROM 4096
+static inline int64_t class_padded(int64_t m, int64_t mc)
+{
+    if (mc <= CLASS_PAD_LARGE_FROM) return m <= CLASS_PAD_SMALL_FROM ? CLASS_PAD_SMALL_TO : m;
+    return m <= CLASS_PAD_LARGE_FROM ? CLASS_PAD_LARGE_FROM + 1 : m;
+}
 
 // ---- abi_batch.hip
 // host points in, host arrays out (any of mu / s2 / acq may be NULL): one sweep, or the pipelined chunks of a large batch

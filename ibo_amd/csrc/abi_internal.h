@@ -8,12 +8,13 @@
 //   abi_batch.hip   host batches, query-point gradients, joint posterior and draws, DIRECT on a GPU objective
 //   abi_cacq.hip    the constrained acquisition (ibo_cacq_*)
 //   abi_ehvi.hip    the two-objective expected hypervolume improvement (ibo_ehvi_*)
+//   abi_mes.hip     max-value entropy search and the max-value cdf (ibo_mes_*)
 //   abi_kg.hip      the knowledge gradient (ibo_kg_*)
 //   abi_paths.hip   pathwise posterior draws (ibo_paths_*)
 //   abi_qei.hip     the Monte-Carlo parallel expected improvement (ibo_qei_*)
 //   abi_gradobs.hip the GP observed with gradients (ibo_ggp_*): its own handle around a P-row frame, the row pipeline with its own K*
 //   abi_rows.hip    the row pipeline of the three above: chunk, scratch, stage clock, host batch, device sweep (abi_rows.h)
-//                   (these nine are the evaluation units: what they share among themselves is in abi_eval.h)
+//                   (these ten are the evaluation units: what they share among themselves is in abi_eval.h)
 //   abi_nlml.hip    marginal-likelihood grid and gradient, ibo_trim
 //   abi_legacy.hip  libego's symbols (acqmaxGP, direct, logCDFs) and ibo_direct_host
 // There is no CPU fallback anywhere behind this header: without a gfx950 device every compute entry point returns IBO_ERR_NO_DEVICE.
@@ -56,6 +57,7 @@ extern std::atomic<int> g_super_min_nb;        // ibo_set_option("super_min_nb",
 extern std::atomic<int> g_host_pipeline, g_fused2_min_nb, g_gallery_prune, g_nlml_batch, g_chol_left, g_dot_override, g_legacy_exact, g_force_path, g_nlml_groups;
 extern std::atomic<int> g_cacq_chunk;                // abi_cacq.hip: candidates per chunk of ibo_cacq_sweep (0: by bytes)
 extern std::atomic<int> g_ehvi_chunk, g_ehvi_timing; // abi_ehvi.hip: candidates per chunk of the ibo_ehvi_* entries (0: by bytes); HIP events around the scan kernel
+extern std::atomic<int> g_mes_chunk, g_mes_timing;   // abi_mes.hip: candidates per chunk of the ibo_mes_* entries (0: by bytes); HIP events around the scan kernels
 extern std::atomic<int> g_kg_chunk, g_kg_timing;     // abi_kg.hip: candidates per chunk (0: by bytes); per-stage HIP events
 extern std::atomic<int> g_qei_chunk, g_qei_timing;   // abi_qei.hip: candidates per chunk (0: by bytes); per-stage HIP events
 extern std::atomic<int> g_ggp_chunk, g_ggp_timing;   // abi_gradobs.hip: candidates per chunk of the ibo_ggp_* entries (0: by bytes); per-stage HIP events

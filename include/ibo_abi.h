@@ -59,7 +59,10 @@ extern "C" {
                              * added within 8, nothing else changed;
                              * + ibo_ggp_create, ibo_ggp_destroy, ibo_ggp_info, ibo_ggp_fit, ibo_ggp_get_R, ibo_ggp_get_L, ibo_ggp_acq_batch, ibo_ggp_acq_sweep,
                              * ibo_ggp_direct_max, ibo_ggp_stage_ms (a GP observed with gradients, on a handle type of its own) and the options "ggp_chunk",
-                             * "ggp_timing": added within 8, nothing else changed */
+                             * "ggp_timing": added within 8, nothing else changed;
+                             * + ibo_mes_sweep, ibo_mes_batch, ibo_mes_grad_batch, ibo_mes_direct_max, ibo_mes_maxcdf, ibo_mes_scan_ms (max-value entropy
+                             * search against samples of the maximum, and the max-value cdf over a candidate set that the Gumbel approximation of those
+                             * samples is fitted to) and the options "mes_chunk", "mes_timing": added within 8, nothing else changed */
 
 /* status codes */
 #define IBO_OK              0
@@ -111,7 +114,7 @@ int         ibo_selftest_mfma(int device, double *max_abs_err);
  * gradients.  DIRECT's small batches and the copies are not event-timed and not in it.  bench.py reports it as gpu_kernel_s_total
  * so that a line can be related to an outside observer's busy-GPU samples. */
 int         ibo_gpu_time_ms(int device, double *ms);
-/* The twenty-two option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
+/* The twenty-four option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
  * Functional:  "legacy_exact" 1/0 -- acqmaxGP in libego's operation order (default) or on the MFMA sweep kernels (see acqmaxGP);
  *   "nlml_batch" B -- matrices per batched factorisation in ibo_nlml_grid (0: as many as 12 GB hold; the values do not depend on it);
  *   "pool_limit_mb" n -- the per-device free list of recycled buffers (ibo_trim);
@@ -130,9 +133,10 @@ int         ibo_gpu_time_ms(int device, double *ms);
  *   0: by bytes, 2^30 / (16 (ncon + 1)) -- identical bits);  "paths_chunk" m (candidates per launch of the ibo_paths_* entries, rounded up to
  *   256, 0: 2^21 -- identical bits);  "qei_chunk" m (candidates per chunk of the ibo_qei_* entries, rounded up to 256, 0: by bytes --
  *   identical bits);  "ehvi_chunk" m (candidates per chunk of the ibo_ehvi_* entries, rounded up to 256, 0: by bytes, 2^25 -- identical bits
- *   among chunks of up to 4096 and among larger ones, see the ibo_ehvi_* entries);  "ggp_chunk" m (candidates per chunk of the ibo_ggp_* entries,
+ *   among chunks of up to 4096 and among larger ones, see the ibo_ehvi_* entries);  "mes_chunk" m (candidates per chunk of the ibo_mes_* entries, rounded up to 256, 0: by bytes, 2^26 -- the same
+ *   statement as "ehvi_chunk", see the ibo_mes_* entries);  "ggp_chunk" m (candidates per chunk of the ibo_ggp_* entries,
  *   rounded up to 256, 0: by bytes -- identical bits).
- * Diagnostic:  "ggp_timing" 1/0 (see ibo_ggp_stage_ms);  "kg_timing" 1/0 (see ibo_kg_stage_ms);  "qei_timing" 1/0 (see ibo_qei_stage_ms);  "ehvi_timing" 1/0 (see ibo_ehvi_scan_ms).
+ * Diagnostic:  "ggp_timing" 1/0 (see ibo_ggp_stage_ms);  "kg_timing" 1/0 (see ibo_kg_stage_ms);  "qei_timing" 1/0 (see ibo_qei_stage_ms);  "ehvi_timing" 1/0 (see ibo_ehvi_scan_ms);  "mes_timing" 1/0 (see ibo_mes_scan_ms).
  * Env: IBO_SWEEP_IMPL=gemv|mfma, IBO_DOT_FORM, IBO_POOL_LIMIT_MB, IBO_HOST_THREADS (the legacy symbol's host crew), IBO_DEVICE (legacy symbols),
  *   IBO_NLML_GROUPS=1..4 (sub-batches of an ibo_nlml_grid batch, each on its own stream; 2; the values do not depend on it).
  * Threading (the reference's library keeps its whole model in process-wide statics, cpp/optimizeGP.cpp:36-55,240-259, and is not
@@ -619,6 +623,95 @@ int ibo_ehvi_direct_max(ibo_gp_t *const *obj, int nfront, const double *front_ho
  * device time (HIP events around that launch alone, not the per-model sweeps) to *ms.  reset != 0 clears the sum after it is read; ms may
  * be NULL.  A diagnostic: the option is process-wide, the sum is per thread. */
 int ibo_ehvi_scan_ms(double *ms, int reset);
+
+/* ---------------------------------------------------------------- max-value entropy search */
+/*
+ * Max-value entropy search (MES; Wang & Jegelka 2017): how much one observation at x tells about the VALUE of the maximum, y*.  One fitted
+ * handle gp (a preference GP passes), K samples of y* (ystar_host, host memory, 1 <= K <= IBO_MES_MAX_SAMPLES -- PosteriorPaths.maxima's
+ * exact draws, or draws from ibo_mes_maxcdf's Gumbel fit), clamp_lo and s2_offset >= 0.  The reference has no counterpart.
+ *
+ * Every entry sorts y* ascending on the host, so a value's bits do not depend on the caller's order.
+ * With (mu, s2) what ibo_acq_sweep returns for gp with IBO_ACQ_NONE at the call's clamp_lo:
+ *   v       = max(s2 - s2_offset, clamp_lo),  sigma = sqrt(v),  gamma_k = (y*_k - mu) / sigma
+ *             (s2 is the predictive variance 1 + noise - |W k*|^2; the latent one is sf2 - |W k*|^2, so s2_offset = 1 + noise - sf2 asks for MES
+ *             of the latent function and 0 for MES of an observation; a latent variance clipped away is floored at clamp_lo)
+ *   MES(x)  = (1/K) sum_k h(gamma_k)                                                 k ascending, plain fp64, no fused multiply-add
+ *   h(g)    = g lambda(g) / 2 - log Phi(g),  lambda = phi / Phi
+ * -- h is the entropy of N(0, 1) minus the entropy of N(0, 1) truncated above at g.  0.5 (1 + erf) loses log Phi below g = -8 and above
+ * g = 8, so h is evaluated in a tail-safe form, the same on every route (there is no erf_mode: nothing of the reference is mirrored):
+ *   g >= 0:  q = erfc(g / sqrt 2) / 2,   lambda = phi(g) / (1 - q),       h = g lambda / 2 + (-log1p(-q))
+ *   g <  0:  e = erfcx(-g / sqrt 2),     lambda = sqrt(2 / pi) / e,       h = g lambda / 2 + (g^2 / 2 - log(e / 2))
+ *   phi(g) = exp(-(g^2 / 2)) / sqrt(2 pi)
+ * A NaN (a NaN candidate coordinate) stays a NaN and never wins the arg-max.
+ * Every entry computes a candidate's value the same way: per chunk one plain sweep into device scratch (16 bytes a candidate), then one
+ * kernel (mes.hip) with one candidate per lane that sums its K terms in order; ystar is uploaded once per call.  Short launches are
+ * padded to the two size classes exactly as the ibo_ehvi_* entries pad theirs, and the statement is the same: within a class the
+ * sweep, a host batch, the gradient entry's value and the value DIRECT reports agree bit for bit, whatever M, the candidate's place and
+ * "mes_chunk" are; between the classes, and for a model whose inputs keep it off the dot form, to rounding.
+ *
+ * Errors, the four value entries, in this order: IBO_ERR_ARG for what the samples alone decide, with or without a device -- K < 1 or
+ * K > IBO_MES_MAX_SAMPLES, a NULL ystar_host, a NaN or an infinity in it, a negative or non-finite s2_offset; IBO_ERR_NO_DEVICE without
+ * a device; IBO_ERR_ARG for a NULL gp, M < 1, a NULL point array, every output NULL; IBO_ERR_STATE if the handle is not fitted.
+ */
+#define IBO_MES_MAX_SAMPLES 1024
+#define IBO_MES_MAX_LEVELS 64
+
+/*
+ * The sweep: cand_dev (M x D, DEVICE) and the exclusion balls, index_base and arg-max rule of ibo_acq_sweep -- NaN values and excluded
+ * candidates never win, the largest value wins, the lowest index wins ties, best_idx = -1 and best_val = -inf when nothing is admissible.
+ * val_dev: optional DEVICE output, M doubles.  Cost: the plain sweep plus K terms per candidate (an erfc or erfcx, an exp or a log each);
+ * 16 bytes of device scratch per candidate, at most 1 GiB (more candidates run in chunks), returned before the call returns.  Blocking.
+ */
+int ibo_mes_sweep(ibo_gp_t *gp, int K, const double *ystar_host, double s2_offset,
+                  int64_t M, const double *cand_dev, double clamp_lo,
+                  int n_excl, const double *excl_host, double excl_radius, int64_t index_base,
+                  double *val_dev, double *best_val, int64_t *best_idx);
+
+/* The same values for points on the HOST (Q_host: M x D) into val_host: the points are uploaded and go through the sweep's route. */
+int ibo_mes_batch(ibo_gp_t *gp, int K, const double *ystar_host, double s2_offset,
+                  int64_t M, const double *Q_host, double clamp_lo, double *val_host);
+
+/*
+ * ibo_mes_batch's value (val_host, bit for bit) and its gradient with respect to the query point (grad_host: M x D row-major).  The
+ * kernel's second variant also sums, over the samples in the same order, with h'(g) = -(lambda / 2) (1 + g^2 + g lambda),
+ *   G_mu = (1/K) sum_k h'(gamma_k) (-1 / sigma)          G_sigma = (1/K) sum_k h'(gamma_k) (-gamma_k / sigma)
+ * and the host applies the chain rule to ibo_acq_grad_batch's (dmu, ds2):
+ *   grad MES = G_mu dmu + G_sigma ds2 / (2 sigma)         (ds2 is 0 where either clamp is active: the sweep's, or the floor of v)
+ * Either output may be NULL, not both.
+ */
+int ibo_mes_grad_batch(ibo_gp_t *gp, int K, const double *ystar_host, double s2_offset,
+                       int64_t M, const double *Q_host, double clamp_lo, double *val_host, double *grad_host);
+
+/*
+ * ibo_direct_max on MES: the same DIRECT, options and batched schedule, every batch of sample points evaluated as ibo_mes_batch does.
+ * opt = the maximum, optx[D] its location, nsamples optional (not all three NULL).  IBO_ERR_ARG also for NULL bounds or D other than
+ * the model's.
+ */
+int ibo_mes_direct_max(ibo_gp_t *gp, int K, const double *ystar_host, double s2_offset,
+                       int D, const double *lb, const double *ub, double clamp_lo,
+                       int maxiter, int maxtime, int maxsample, int compat,
+                       double *opt, double *optx, int64_t *nsamples);
+
+/*
+ * What the Gumbel approximation of the max-value distribution is fitted to (Wang & Jegelka 2017, section 3.1): over the candidates
+ * cand_dev (M x D, DEVICE), with (mu_i, sigma_i) as above (s2_offset, clamp_lo), for each of nlev levels t_k (lev_host, host memory,
+ * 0 <= nlev <= IBO_MES_MAX_LEVELS)
+ *   logcdf_host[k] = sum_i log Phi((t_k - mu_i) / sigma_i)          -- log P(max_i f(x_i) <= t_k) were the candidates independent
+ * (log Phi in the tail-safe form above), and the bracket stats_host[0] = max_i mu_i, stats_host[1] = max_i (mu_i + 5 sigma_i).  nlev = 0
+ * returns only the bracket (lev_host and logcdf_host may be NULL).  Candidates with a NaN posterior are skipped (in the sums and in the
+ * bracket; with none left the bracket is -inf).  One kernel sums each block of 256 candidates in a fixed tree, a second launch adds the
+ * block sums in ascending block order: the result's bits do not depend on "mes_chunk" (beyond the size classes of the plain sweep).
+ * IBO_ERR_ARG, with or without a device, for nlev out of range, a NULL lev_host or logcdf_host with nlev > 0, a NaN level (+-inf
+ * passes), a negative or non-finite s2_offset; IBO_ERR_NO_DEVICE without a device; IBO_ERR_ARG for a NULL gp, M < 1, a NULL cand_dev,
+ * a NULL stats_host; IBO_ERR_STATE if the handle is not fitted.
+ */
+int ibo_mes_maxcdf(ibo_gp_t *gp, int64_t M, const double *cand_dev, int nlev, const double *lev_host, double s2_offset, double clamp_lo,
+                   double *logcdf_host, double *stats_host);
+
+/* With ibo_set_option("mes_timing", 1) every ibo_mes_* call of this thread waits after each launch of the scan kernel (the value
+ * kernel, or ibo_mes_maxcdf's reduction) and adds its device time (HIP events around that launch alone, not the sweep) to *ms.
+ * reset != 0 clears the sum after it is read; ms may be NULL.  A diagnostic: the option is process-wide, the sum is per thread. */
+int ibo_mes_scan_ms(double *ms, int reset);
 
 /* ---------------------------------------------------------------- knowledge gradient */
 /*
