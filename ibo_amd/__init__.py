@@ -3,6 +3,7 @@ ibo_amd -- MI355X-native GP-posterior + acquisition hot path of
 misterwindupbird/IBO, behind the reference's own Python API.
 
     from ibo_amd.gaussianprocess import GaussianProcess, PrefGaussianProcess
+    from ibo_amd.gaussianprocess import SparseGaussianProcess, inducingPoints      # DTC / FITC on m inducing points
     from ibo_amd.gaussianprocess.kernel import GaussianKernel_ard, MaternKernel5, ...
     from ibo_amd.acquisition import maximizeEI, maximizePI, maximizeUCB, EI, PI, UCB, sweep
     from ibo_amd.acquisition.gallery import fastUCBGallery

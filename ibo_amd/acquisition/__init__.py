@@ -33,6 +33,7 @@ import numpy as np
 
 from .. import _lib
 from ..gaussianprocess import GaussianProcess, PrefGaussianProcess, CDF, PDF      # noqa: F401
+from ..gaussianprocess.sparse import SparseGaussianProcess
 from ..utils.optimize import direct, cdirect
 from ..utils.latinhypercube import lhcSample                                        # noqa: F401
 
@@ -176,6 +177,10 @@ def cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc=None, xi=-1, b
     _, _, sf2_py, sf2_native = model.kernel._ibo_spec()
     lb = _lib.f64([b[0] for b in bounds]); ub = _lib.f64([b[1] for b in bounds])
     D = len(lb)
+    if isinstance(model, SparseGaussianProcess):
+        # a sparse model: the same DIRECT on ibo_sgp_direct_max, the model's own signal variance throughout
+        res = model._direct(lb, ub, _ACQ[acqfunc], parm, maxiter, maxtime, maxsample, compat)
+        return res if return_samples else res[:2]
     opt = ctypes.c_double(); optx = np.empty(D); ns = ctypes.c_int64()
     if model.G is not None:
         # a model observed with gradients: the same DIRECT on ibo_ggp_direct_max, libm erf and the native clamp as here, but the
@@ -249,7 +254,7 @@ def maximizeUCB(model, bounds, delta=0.1, scale=0.2, useCDIRECT=True, maxiter=50
         # the reference forgets to forward the budgets here (:86) and raises; they are forwarded
         opt, optx = direct(ucb.negf, bounds, maxiter=maxiter, maxtime=maxtime, maxsample=maxsample)
         return -opt, optx
-    if isinstance(model, GaussianProcess):
+    if isinstance(model, (GaussianProcess, SparseGaussianProcess)):
         if polish:
             model._no_gradient("maximizeUCB(polish=True)")
         opt, optx = cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='ucb', delta=delta, scale=scale,
@@ -267,7 +272,7 @@ def maximizePI(model, bounds, xi=0.01, maxiter=50, maxtime=30, maxsample=10000, 
         pi = PI(model, xi, **kwargs)
         opt, optx = direct(pi.negf, bounds, maxiter=maxiter, maxtime=maxtime, maxsample=maxsample)
         return -opt, optx
-    if isinstance(model, GaussianProcess):
+    if isinstance(model, (GaussianProcess, SparseGaussianProcess)):
         if polish:
             model._no_gradient("maximizePI(polish=True)")
         opt, optx = cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='pi', xi=xi, **kwargs)
@@ -284,7 +289,7 @@ def maximizeEI(model, bounds, useCDIRECT=True, xi=0.01, maxiter=50, maxtime=30, 
         ei = EI(model, xi, **kwargs)
         opt, optx = direct(ei.negf, bounds, maxiter=maxiter, maxtime=maxtime, maxsample=maxsample)
         return -opt, optx
-    if isinstance(model, GaussianProcess):
+    if isinstance(model, (GaussianProcess, SparseGaussianProcess)):
         if polish:
             model._no_gradient("maximizeEI(polish=True)")
         opt, optx = cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='ei', xi=xi, **kwargs)
@@ -314,7 +319,12 @@ def sweep(model, candidates, acq='ei', xi=0.01, delta=0.1, scale=0.2, parm=None,
     Returns dict(best_val, best_idx, kernel_ms, [mu], [s2], [acq]); first maximiser wins ties.
     A model observed with gradients (G=) takes ibo_ggp_acq_sweep: the same arguments and result (kernel_ms is the whole call's device
     time), the model's own signal variance in both modes, and NotImplementedError for exclude=, incremental= and exchange=.
+    A sparse model (SparseGaussianProcess) takes ibo_sgp_acq_sweep: the same, exclude= included; NotImplementedError for incremental= and
+    exchange=.
     """
+    if isinstance(model, SparseGaussianProcess):
+        return _sweep_sparse(model, candidates, acq, xi, delta, scale, parm, native, ymax, exclude, exclude_radius, index_base, outputs, NA,
+                             incremental, exchange)
     if model.G is not None:
         return _sweep_gradient(model, candidates, acq, xi, delta, scale, parm, native, ymax, exclude, index_base, outputs, NA,
                                incremental, exchange)
@@ -371,6 +381,23 @@ def sweep(model, candidates, acq='ei', xi=0.01, delta=0.1, scale=0.2, parm=None,
     for k, v in outs.items():
         res[k] = v.to_host()
     return res
+
+
+def _sweep_sparse(model, candidates, acq, xi, delta, scale, parm, native, ymax, exclude, exclude_radius, index_base, outputs, NA, incremental,
+                  exchange):
+    """sweep() on a sparse model (ibo_sgp_acq_sweep): the same arguments and result, exclusion balls included; kernel_ms is the whole
+    call's device time"""
+    if incremental:
+        model._no_gradient("sweep(incremental=)")
+    if exchange is not None:
+        model._no_gradient("sweep(exchange=)")
+    if parm is None:
+        if acq == 'ucb':
+            nd = NA if NA is not None else (candidates.shape[1] if hasattr(candidates, "shape") else np.atleast_2d(candidates).shape[1])
+            parm = _ucb_parm(model, [None] * nd, delta, scale) if native else float(np.sqrt(scale * UCB(model, nd, delta, scale).sBeta))
+        else:
+            parm = xi
+    return model._sweep(candidates, _ACQ[acq], parm, native, ymax, exclude, exclude_radius, index_base, outputs)
 
 
 def _sweep_gradient(model, candidates, acq, xi, delta, scale, parm, native, ymax, exclude, index_base, outputs, NA, incremental,

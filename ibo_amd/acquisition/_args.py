@@ -5,8 +5,9 @@ from .. import _lib
 
 
 def _no_gradient(GP, what):
-    """refuse `what` on a model observed with gradients (GaussianProcess(G=)); anything without a G attribute passes"""
-    if getattr(GP, "G", None) is not None:
+    """refuse `what` on a model observed with gradients (GaussianProcess(G=)) and on a sparse model (SparseGaussianProcess); anything
+    without a G attribute passes"""
+    if getattr(GP, "G", None) is not None or getattr(GP, "_sparse", False):
         GP._no_gradient(what)
 
 

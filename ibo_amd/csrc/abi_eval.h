@@ -1,4 +1,4 @@
-// abi_eval.h -- what the evaluation units (abi_sweep.hip, abi_batch.hip, abi_cacq.hip, abi_ehvi.hip, abi_mes.hip, abi_kg.hip, abi_paths.hip, abi_qei.hip, abi_gradobs.hip, abi_rows.hip) share beyond
+// abi_eval.h -- what the evaluation units (abi_sweep.hip, abi_batch.hip, abi_cacq.hip, abi_ehvi.hip, abi_mes.hip, abi_kg.hip, abi_paths.hip, abi_qei.hip, abi_gradobs.hip, abi_sparse.hip, abi_rows.hip) share beyond
 // abi_internal.h: the sweep request, the host batch, and the ONE copy of the arg-max read-back, the exclusion upload, the padding of a short sweep to its size class, the timed span, the V^T rows and the DIRECT driver.
 #pragma once
 #include "abi_internal.h"

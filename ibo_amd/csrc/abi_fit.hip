@@ -119,7 +119,7 @@ int ensure_R(ibo_gp *g)
 }
 
 // What every fit starts with: the kernel's parameters, the data staged (reverse: in reverse order) and scaled, the dot form's guard ...
-static int fit_begin(ibo_gp *g, int ktype, int N, int D, const double *X, const double *Y, const double *hyper, int nhyper, double sf2,
+int fit_begin(ibo_gp *g, int ktype, int N, int D, const double *X, const double *Y, const double *hyper, int nhyper, double sf2,
                      double noise, bool reverse, KParams *kp)
 {
     IBO_TRY(use_device(g->device));

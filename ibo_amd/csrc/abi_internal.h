@@ -13,8 +13,9 @@
 //   abi_paths.hip   pathwise posterior draws (ibo_paths_*)
 //   abi_qei.hip     the Monte-Carlo parallel expected improvement (ibo_qei_*)
 //   abi_gradobs.hip the GP observed with gradients (ibo_ggp_*): its own handle around a P-row frame, the row pipeline with its own K*
+//   abi_sparse.hip  the sparse GP on inducing points (ibo_sgp_*): its own handle around two m-row frames and the kept Gram matrix
 //   abi_rows.hip    the row pipeline of the three above: chunk, scratch, stage clock, host batch, device sweep (abi_rows.h)
-//                   (these ten are the evaluation units: what they share among themselves is in abi_eval.h)
+//                   (these eleven are the evaluation units: what they share among themselves is in abi_eval.h)
 //   abi_nlml.hip    marginal-likelihood grid and gradient, ibo_trim
 //   abi_legacy.hip  libego's symbols (acqmaxGP, direct, logCDFs) and ibo_direct_host
 // There is no CPU fallback anywhere behind this header: without a gfx950 device every compute entry point returns IBO_ERR_NO_DEVICE.
@@ -61,6 +62,7 @@ extern std::atomic<int> g_mes_chunk, g_mes_timing;   // abi_mes.hip: candidates 
 extern std::atomic<int> g_kg_chunk, g_kg_timing;     // abi_kg.hip: candidates per chunk (0: by bytes); per-stage HIP events
 extern std::atomic<int> g_qei_chunk, g_qei_timing;   // abi_qei.hip: candidates per chunk (0: by bytes); per-stage HIP events
 extern std::atomic<int> g_ggp_chunk, g_ggp_timing;   // abi_gradobs.hip: candidates per chunk of the ibo_ggp_* entries (0: by bytes); per-stage HIP events
+extern std::atomic<int> g_sgp_chunk, g_sgp_timing;   // abi_sparse.hip: observations / candidates per chunk of the ibo_sgp_* entries (0: by bytes); per-stage HIP events
 extern std::atomic<int> g_paths_chunk;               // abi_paths.hip: candidates per launch of the ibo_paths_* entries (0: 2^21)
 extern std::mutex g_dev_mu[16];             // serialises the per-device workspaces of ibo_nlml_grid / ibo_nlml_grad / ibo_trim
 extern std::atomic<size_t> g_pool_limit;
@@ -182,6 +184,8 @@ uint64_t alloc_generation(int device, const void *p, size_t bytes, size_t *offse
 int ensure_pinned(ibo_gp *g, size_t need);                                                                // abi_core.hip
 int make_kparams(int ktype, int D, const double *hyper, int nhyper, double sf2, KParams *kp);             // abi_fit.hip
 int ensure_R(ibo_gp *g);                                                                                  // abi_fit.hip: R = K(X, X) + diag, formed on request
+int fit_begin(ibo_gp *g, int ktype, int N, int D, const double *X, const double *Y, const double *hyper, int nhyper, double sf2,
+              double noise, bool reverse, KParams *kp);                                                   // abi_fit.hip: what every fit starts with (the staging)
 int fit_factor(ibo_gp *g, const KParams &kp, int N, double noise, bool have_A, int *info);                // abi_fit.hip: a fit after staging (have_A: of g->A)
 int fit_from_inverse(ibo_gp *g, int ktype, int N, int D, const double *X, const double *Y,
                      const double *hyper, int nhyper, double sf2, double noise, const double *invR);      // abi_fit.hip

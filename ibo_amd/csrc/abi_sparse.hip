@@ -1,0 +1,443 @@
+// abi_sparse.hip -- a sparse GP on inducing points (DTC / FITC) behind the C ABI: ibo_sgp_* (kernels: sparse.hip; the per-frame work:
+// fit_begin / fit_factor and run_sweep).
+//
+// The handle wraps two ibo_gp frames on the m inducing points Z that no other entry ever sees:
+//   U  a plain fit with noise = jitter: L_u, W_u; its plain sweep gives s2_U = 1 + jitter - q
+//   A  staged on the same points, then fit_factor(have_A = true) on A = K~uu + G with the noise field 0 and the targets b: its alpha
+//      vector is the model's, its plain sweep gives mu = k_u^T alpha and s2_A = 1 - |W_A k_u|^2
+// and keeps G+ = [F; y~] [F; y~]^T (lower 64 x 64 tiles), ll, tt, N and the largest target.  The observations pass through in chunks and
+// are not kept.
+//   chunk of data     upload (pinned staging) -> U sweep (s2_U, unclipped) -> sgp_scaled_kuf_kernel -> sgp_gram_kernel, on the A frame's stream
+//   refactor          K~uu (the U frame's R) + G -> sgp_assemble_kernel -> fit_factor on the A frame
+//   chunk of points   U sweep, A sweep into pool scratch -> sgp_finish_kernel; launch_argmax_final for the winner
+// Host batches and DIRECT are uploaded and take the route of the sweep: the same bits within a size class of the plain sweep (class_padded).
+#include "abi_eval.h"
+#include "abi_factor.h"
+#include "sparse.h"
+
+std::atomic<int> g_sgp_chunk{0};      // ibo_set_option("sgp_chunk", n): observations / candidates per chunk (rounded up to 256); 0: by bytes
+std::atomic<int> g_sgp_timing{0};     // ibo_set_option("sgp_timing", 1): HIP events around every stage, read with ibo_sgp_stage_ms
+static thread_local double t_sgp_ms[IBO_SGP_STAGES];
+enum { SGP_ST_Q = 0, SGP_ST_GEN, SGP_ST_GRAM, SGP_ST_ASSEMBLE, SGP_ST_FACTOR, SGP_ST_SWEEPS, SGP_ST_FINISH };
+
+struct ibo_sgp {
+    ibo_gp *gu = nullptr, *ga = nullptr;     // the two m-row frames
+    int device = 0, m = 0, mp = 0, D = 0, method = IBO_SGP_FITC;
+    bool fitted = false;
+    int64_t N = 0;
+    KParams kp;
+    double noise = 0.0, jitter = 0.0, maxY = 0.0, ll = 0.0, tt = 0.0;
+    double logdet_u = 0.0, logdet_a = 0.0, wb2 = 0.0;      // 2 sum log L_ii of both factors; |W_A b|^2
+    DevBuf<double> Gp;                       // (mp + 64)^2
+    double *pin = nullptr; size_t pin_cap = 0;
+};
+
+namespace {
+
+// the diagnostic's events: made per call, a stage at a time (the stage's stream is waited for)
+struct SgpClock {
+    bool on = false;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~SgpClock() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    int make() { on = g_sgp_timing != 0; if (on) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); } return IBO_OK; }
+    int start(hipStream_t s) { if (on) HIP_TRY(hipEventRecord(e0, s)); return IBO_OK; }
+    int stop(hipStream_t s, int stage)
+    {
+        if (!on) return IBO_OK;
+        float ms = 0.f;
+        HIP_TRY(hipEventRecord(e1, s)); HIP_TRY(hipEventSynchronize(e1)); HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        t_sgp_ms[stage] += ms;
+        return IBO_OK;
+    }
+};
+
+int sgp_pinned(ibo_sgp *h, size_t need)
+{
+    if (need <= h->pin_cap) return IBO_OK;
+    if (h->pin) (void)hipHostFree(h->pin);
+    h->pin = nullptr; h->pin_cap = 0;
+    HIP_TRY(hipHostMalloc((void **)&h->pin, sizeof(double) * need, hipHostMallocDefault));
+    h->pin_cap = need;
+    return IBO_OK;
+}
+
+bool all_finite(const double *p, size_t n)
+{
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(p[i])) return false;
+    return true;
+}
+
+// observations / candidates per chunk: a multiple of 256 unless the whole call is one chunk
+int64_t sgp_chunking(int64_t n, int64_t by_bytes)
+{
+    int64_t nc = by_bytes / 256 * 256;
+    if (nc < 256) nc = 256;
+    if (g_sgp_chunk > 0) nc = ((int64_t)g_sgp_chunk + 255) / 256 * 256;
+    return n <= nc ? n : nc;
+}
+
+// n observations into G+, ll, tt, N and the largest target; chunks in ascending order on the A frame's stream
+int sgp_accumulate(ibo_sgp *h, int64_t n, const double *X, const double *Y, double *lambda_host)
+{
+    ibo_gp *gu = h->gu, *ga = h->ga;
+    hipStream_t su = gu->stream, sa = ga->stream;
+    const int D = h->D, m = h->m, mp = h->mp;
+    const int64_t nc = sgp_chunking(n, ((int64_t)256 << 20) / (8 * (int64_t)(mp + 64)));
+    const int64_t rows = class_padded(nc, nc), ldmax = (nc + 31) / 32 * 32, nblkmax = (nc + 255) / 256;
+    ScopedBuf<double> xc, yc, s2, Ft, lam, part;
+    IBO_TRY(xc.ensure((size_t)rows * D)); IBO_TRY(yc.ensure((size_t)nc)); IBO_TRY(s2.ensure((size_t)rows));
+    IBO_TRY(Ft.ensure((size_t)(mp + 64) * ldmax)); IBO_TRY(lam.ensure((size_t)nc)); IBO_TRY(part.ensure(2 * (size_t)nblkmax));
+    IBO_TRY(sgp_pinned(h, (size_t)rows * D + 2 * (size_t)nc + 2 * (size_t)nblkmax));
+    SgpClock clock;
+    IBO_TRY(clock.make());
+    for (int64_t c0 = 0; c0 < n; c0 += nc) {
+        const int64_t k = n - c0 < nc ? n - c0 : nc, kp = class_padded(k, nc), nblk = (k + 255) / 256;
+        double *px = h->pin, *py = px + (size_t)rows * D, *pl = py + nc, *pp = pl + nc;
+        memcpy(px, X + (size_t)c0 * D, sizeof(double) * (size_t)k * D);
+        memset(px + (size_t)k * D, 0, sizeof(double) * (size_t)(kp - k) * D);       // the sweep's padding to its size class: points at the origin
+        memcpy(py, Y + c0, sizeof(double) * (size_t)k);
+        for (int64_t i = 0; i < k; i++)
+            if (h->N + c0 + i == 0 || py[i] > h->maxY) h->maxY = py[i];
+        HIP_TRY(hipMemcpyAsync(xc.p, px, sizeof(double) * (size_t)kp * D, hipMemcpyHostToDevice, su));
+        HIP_TRY(hipMemcpyAsync(yc.p, py, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, su));
+        // q of the chunk: the U frame's plain sweep, nothing clipped from below (s2_U = 1 + jitter - q).  DTC's lambda does not read it;
+        // the sum tt -- the VFE bound's trace term -- does.
+        SweepRequest r;
+        r.M = kp; r.cand_dev = xc.p; r.acq = IBO_ACQ_NONE; r.clamp_lo = -1.0; r.s2_dev = s2.p;
+        IBO_TRY(clock.start(su));
+        IBO_TRY(run_sweep(gu, r));
+        IBO_TRY(clock.stop(su, SGP_ST_Q));
+        HIP_TRY(hipStreamSynchronize(su));                       // the generation runs on the A frame's stream
+        SgpKufArgs a;
+        memset(&a, 0, sizeof(a));
+        a.kp = h->kp; a.m = m; a.mp = mp; a.Z = ga->Xp.p; a.ldz = ga->DP; a.X = xc.p; a.n = (int)k; a.Y = yc.p; a.s2u = s2.p;
+        a.fitc = h->method == IBO_SGP_FITC; a.noise = h->noise; a.jitter = h->jitter; a.ld = (int)((k + 31) / 32 * 32);
+        a.Ft = Ft.p; a.lam = lam.p; a.part = part.p;
+        IBO_TRY(clock.start(sa));
+        KERNEL_TRY(launch_sgp_scaled_kuf(a, sa));
+        IBO_TRY(clock.stop(sa, SGP_ST_GEN));
+        IBO_TRY(clock.start(sa));
+        KERNEL_TRY(launch_sgp_gram(Ft.p, a.ld, mp, h->Gp.p, sa));
+        IBO_TRY(clock.stop(sa, SGP_ST_GRAM));
+        HIP_TRY(hipMemcpyAsync(pp, part.p, sizeof(double) * 2 * (size_t)nblk, hipMemcpyDeviceToHost, sa));
+        if (lambda_host) HIP_TRY(hipMemcpyAsync(pl, lam.p, sizeof(double) * (size_t)k, hipMemcpyDeviceToHost, sa));
+        HIP_TRY(hipStreamSynchronize(sa));                       // the staging and the scratch are the next chunk's
+        for (int64_t b = 0; b < nblk; b++) { h->ll += pp[b]; h->tt += pp[nblk + b]; }     // ascending blocks of 256: the chunking does not show
+        if (lambda_host) memcpy(lambda_host + c0, pl, sizeof(double) * (size_t)k);
+    }
+    h->N += n;
+    return IBO_OK;
+}
+
+// 2 sum log L_ii of a frame's factor
+int sgp_logdet(ibo_gp *g, double *out)
+{
+    std::vector<double> d((size_t)g->N);
+    HIP_TRY(hipMemcpy2D(d.data(), sizeof(double), g->L.p, sizeof(double) * ((size_t)g->Npad + 1), sizeof(double), (size_t)g->N, hipMemcpyDeviceToHost));
+    double s = 0.0;
+    for (int i = 0; i < g->N; i++) s += log(d[i]);
+    *out = 2.0 * s;
+    return IBO_OK;
+}
+
+// A = K~uu + G and b into the A frame, then its factorisation
+int sgp_refactor(ibo_sgp *h, int *info)
+{
+    ibo_gp *gu = h->gu, *ga = h->ga;
+    hipStream_t sa = ga->stream;
+    const int m = h->m, mp = h->mp;
+    SgpClock clock;
+    IBO_TRY(clock.make());
+    IBO_TRY(ensure_R(gu));
+    HIP_TRY(hipStreamSynchronize(gu->stream));
+    IBO_TRY(ga->A.ensure((size_t)m * m));
+    IBO_TRY(clock.start(sa));
+    KERNEL_TRY(launch_sgp_assemble(gu->R.p, gu->Npad, h->Gp.p, mp + 64, m, mp, ga->Npad, ga->A.p, ga->Y.p, sa));
+    IBO_TRY(clock.stop(sa, SGP_ST_ASSEMBLE));
+    ga->maxY = h->maxY;
+    ga->st_gen = 0;
+    IBO_TRY(clock.start(sa));
+    const int rc = fit_factor(ga, h->kp, m, 0.0, true, info);        // synchronises
+    if (rc == IBO_ERR_NOT_PD) return fail(IBO_ERR_NOT_PD, "A = K~uu + G is not positive definite (pivot %d)", info ? *info : -1);
+    IBO_TRY(rc);
+    IBO_TRY(clock.stop(sa, SGP_ST_FACTOR));
+    // |W_A b|^2 from launch_alpha's first product (fit_end left W_A b at the head of the frame's scratch)
+    std::vector<double> wb((size_t)m);
+    HIP_TRY(hipMemcpy(wb.data(), ga->tmp.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost));
+    double s = 0.0;
+    for (int i = 0; i < m; i++) s += wb[i] * wb[i];
+    h->wb2 = s;
+    return sgp_logdet(ga, &h->logdet_a);
+}
+
+// What the evaluating entries check alike: the device first, the arguments, the handle's state.
+int sgp_check(ibo_sgp *h, bool ptrs_ok, int64_t M, int acq, int erf_mode, bool none_ok)
+{
+    IBO_TRY(use_device(h ? h->device : 0));
+    if (!h || !ptrs_ok) return fail(IBO_ERR_ARG, "NULL argument");
+    if (M < 1) return fail(IBO_ERR_ARG, "M=%lld", (long long)M);
+    if (acq < 0 || acq > (none_ok ? IBO_ACQ_NONE : IBO_ACQ_UCB)) return fail(IBO_ERR_ARG, "unknown acquisition %d", acq);
+    if (erf_mode != IBO_ERF_LIBM && erf_mode != IBO_ERF_NR) return fail(IBO_ERR_ARG, "unknown erf flavour %d", erf_mode);
+    if (!h->fitted) return fail(IBO_ERR_STATE, "sparse model before a successful fit");
+    return IBO_OK;
+}
+
+struct SgpCall { int acq, erf_mode; double parm, clamp_lo, ymax; };
+struct SgpOut { double *mu = nullptr, *s2 = nullptr, *acq = nullptr; double *best_val = nullptr; int64_t *best_idx = nullptr; };
+
+// The one route of every evaluating entry.  cand_rows: the rows cand_dev has room for (>= M; rows from M on are the caller's padding).
+int sgp_device(ibo_sgp *h, const SgpCall &c, int64_t M, const double *cand_dev, int64_t cand_rows, int n_excl, const double *excl_host,
+               double excl_radius, int64_t index_base, const SgpOut &o)
+{
+    ibo_gp *gu = h->gu, *ga = h->ga;
+    hipStream_t su = gu->stream, sa = ga->stream;
+    const int D = h->D;
+    SgpFinishArgs a;
+    memset(&a, 0, sizeof(a));
+    a.D = D; a.noise = h->noise; a.jitter = h->jitter; a.clamp_lo = c.clamp_lo; a.ymax = c.ymax == c.ymax ? c.ymax : h->maxY; a.parm = c.parm;
+    a.acq = c.acq; a.erf_mode = c.erf_mode; a.index_base = index_base; a.excl_radius = excl_radius;
+    IBO_TRY(upload_exclusions(ga, n_excl, excl_host, &a.n_excl, &a.excl));
+    const int64_t mc = sgp_chunking(M, ((int64_t)1 << 30) / 24);
+    const int64_t stride = class_padded(mc, mc), nblk = (M + 255) / 256;
+    ScopedBuf<double> ms, pv, pad;
+    ScopedBuf<int64_t> pi;
+    IBO_TRY(ms.ensure(3 * (size_t)stride)); IBO_TRY(pv.ensure((size_t)nblk)); IBO_TRY(pi.ensure((size_t)nblk));
+    SgpClock clock;
+    IBO_TRY(clock.make());
+    a.s2u = ms.p; a.mua = ms.p + stride; a.s2a = ms.p + 2 * stride;
+    for (int64_t c0 = 0; c0 < M; c0 += mc) {
+        const int64_t k = M - c0 < mc ? M - c0 : mc, kp = class_padded(k, mc);
+        const double *rows = cand_dev + c0 * D;
+        if (c0 + kp > cand_rows) {                               // a padded copy where the padded launch does not fit into the caller's rows
+            IBO_TRY(pad.ensure((size_t)kp * D));
+            HIP_TRY(hipMemcpyAsync(pad.p, rows, sizeof(double) * (size_t)k * D, hipMemcpyDeviceToDevice, sa));
+            HIP_TRY(hipMemsetAsync(pad.p + (size_t)k * D, 0, sizeof(double) * (size_t)(kp - k) * D, sa));
+            HIP_TRY(hipStreamSynchronize(sa));                   // (the U frame reads it on its own stream)
+            rows = pad.p;
+        }
+        SweepRequest r;
+        r.M = kp; r.cand_dev = rows; r.acq = IBO_ACQ_NONE; r.clamp_lo = -1.0;     // nothing is clipped before the composition
+        r.s2_dev = ms.p;
+        IBO_TRY(clock.start(su));
+        IBO_TRY(run_sweep(gu, r));
+        HIP_TRY(hipStreamSynchronize(su));                       // the finish runs on the A frame's stream
+        r.mu_dev = ms.p + stride; r.s2_dev = ms.p + 2 * stride;
+        IBO_TRY(run_sweep(ga, r));
+        if (clock.on) { HIP_TRY(hipStreamSynchronize(sa)); IBO_TRY(clock.stop(su, SGP_ST_SWEEPS)); }
+        a.M = k; a.first = c0; a.cand = rows;
+        a.out_mu = o.mu ? o.mu + c0 : nullptr; a.out_s2 = o.s2 ? o.s2 + c0 : nullptr; a.out_acq = o.acq ? o.acq + c0 : nullptr;
+        a.part_val = pv.p + c0 / 256; a.part_idx = pi.p + c0 / 256;
+        IBO_TRY(clock.start(sa));
+        KERNEL_TRY(launch_sgp_finish(a, sa));
+        IBO_TRY(clock.stop(sa, SGP_ST_FINISH));
+        if (c0 + mc < M) HIP_TRY(hipStreamSynchronize(sa));      // the next chunk's U sweep, on the other stream, writes the same scratch
+    }
+    if (o.best_val || o.best_idx) return argmax_readback(ga, pv.p, pi.p, nblk, o.best_val, o.best_idx);
+    HIP_TRY(hipStreamSynchronize(sa));
+    return IBO_OK;
+}
+
+// Host points: uploaded, then the sweep's own route -- the device's values are the sweep's bits.
+int sgp_eval_host(ibo_sgp *h, const SgpCall &c, int64_t M, const double *Q_host, double *mu, double *s2, double *acq)
+{
+    const size_t m = (size_t)M, D = (size_t)h->D;
+    hipStream_t s = h->ga->stream;
+    const size_t rows = (size_t)class_padded(M, sgp_chunking(M, ((int64_t)1 << 30) / 24));     // (a short batch carries its padding)
+    ScopedBuf<double> q, out;
+    IBO_TRY(q.ensure(rows * D)); IBO_TRY(out.ensure(3 * m));
+    HIP_TRY(hipMemcpyAsync(q.p, Q_host, sizeof(double) * m * D, hipMemcpyHostToDevice, s));
+    if (rows > m) HIP_TRY(hipMemsetAsync(q.p + m * D, 0, sizeof(double) * (rows - m) * D, s));
+    HIP_TRY(hipStreamSynchronize(s));                            // (Q_host is the caller's pageable memory; the U frame reads q on its own stream)
+    SgpOut o;
+    o.mu = mu ? out.p : nullptr; o.s2 = s2 ? out.p + m : nullptr; o.acq = acq ? out.p + 2 * m : nullptr;
+    IBO_TRY(sgp_device(h, c, M, q.p, (int64_t)rows, 0, nullptr, 0.0, 0, o));
+    if (mu) HIP_TRY(hipMemcpyAsync(mu, out.p, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+    if (s2) HIP_TRY(hipMemcpyAsync(s2, out.p + m, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+    if (acq) HIP_TRY(hipMemcpyAsync(acq, out.p + 2 * m, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return IBO_OK;
+}
+
+}  // namespace
+
+extern "C" int ibo_sgp_create(int device, ibo_sgp_t **out)
+{
+    if (!out) return fail(IBO_ERR_ARG, "out is NULL");
+    ibo_gp *gu = nullptr, *ga = nullptr;
+    IBO_TRY(ibo_gp_create(device, &gu));
+    const int rc = ibo_gp_create(device, &ga);
+    if (rc != IBO_OK) { (void)ibo_gp_destroy(gu); return rc; }
+    ibo_sgp *h = new ibo_sgp();
+    h->gu = gu; h->ga = ga; h->device = device;
+    memset(&h->kp, 0, sizeof(h->kp));
+    *out = h;
+    return IBO_OK;
+}
+
+extern "C" int ibo_sgp_destroy(ibo_sgp_t *h)
+{
+    if (!h) return IBO_OK;
+    (void)hipSetDevice(h->device);
+    (void)hipDeviceSynchronize();
+    g_pool_quiet = true;
+    h->Gp.release();
+    g_pool_quiet = false;
+    if (h->pin) (void)hipHostFree(h->pin);
+    const int r1 = ibo_gp_destroy(h->gu), r2 = ibo_gp_destroy(h->ga);
+    delete h;
+    return r1 != IBO_OK ? r1 : r2;
+}
+
+extern "C" int ibo_sgp_fit(ibo_sgp_t *h, int ktype, int D, const double *hyper, int nhyper, double sf2, double noise, double jitter, int method,
+                           int m, const double *Z, int64_t N, const double *X, const double *Y, double *lambda_host, int *info)
+{
+    if (!h) return fail(IBO_ERR_ARG, "handle is NULL");
+    IBO_TRY(use_device(h->device));
+    if (!Z || !X || !Y) return fail(IBO_ERR_ARG, "Z/X/Y is NULL");
+    if (m < 1 || m > IBO_SGP_MAX_M) return fail(IBO_ERR_ARG, "m=%d inducing points, not 1 .. %d", m, IBO_SGP_MAX_M);
+    if (N < 1) return fail(IBO_ERR_ARG, "N=%lld", (long long)N);
+    if (method != IBO_SGP_FITC && method != IBO_SGP_DTC) return fail(IBO_ERR_ARG, "unknown method %d", method);
+    if (!(noise > 0.0) || !std::isfinite(noise)) return fail(IBO_ERR_ARG, "noise=%g", noise);
+    if (!(jitter >= 0.0) || !std::isfinite(jitter)) return fail(IBO_ERR_ARG, "jitter=%g", jitter);
+    KParams kp;
+    IBO_TRY(make_kparams(ktype, D, hyper, nhyper, sf2, &kp));
+    if (!all_finite(Z, (size_t)m * D)) return fail(IBO_ERR_ARG, "Z holds a value that is not finite");
+    if (!all_finite(X, (size_t)N * D)) return fail(IBO_ERR_ARG, "X holds a value that is not finite");
+    if (!all_finite(Y, (size_t)N)) return fail(IBO_ERR_ARG, "Y holds a value that is not finite");
+    if (info) *info = 0;
+    h->fitted = false;
+    h->m = m; h->mp = round_up(m, 64); h->D = D; h->method = method; h->kp = kp; h->noise = noise; h->jitter = jitter;
+    h->N = 0; h->ll = 0.0; h->tt = 0.0; h->maxY = 0.0;
+    const std::vector<double> zero((size_t)m, 0.0);
+    // U: a plain fit on Z with noise = jitter
+    int rc = ibo_gp_fit(h->gu, ktype, m, D, Z, zero.data(), hyper, nhyper, sf2, jitter, info);
+    if (rc == IBO_ERR_NOT_PD) return fail(IBO_ERR_NOT_PD, "K~uu = K(Z, Z) + jitter is not positive definite (pivot %d)", info ? *info : -1);
+    IBO_TRY(rc);
+    IBO_TRY(sgp_logdet(h->gu, &h->logdet_u));
+    // A: the same points staged (scaled copies, packed operands); its matrix and targets come from sgp_assemble_kernel
+    IBO_TRY(fit_begin(h->ga, ktype, m, D, Z, zero.data(), hyper, nhyper, sf2, 0.0, false, &kp));
+    const size_t gn = (size_t)(h->mp + 64) * (h->mp + 64);
+    IBO_TRY(h->Gp.ensure(gn));
+    HIP_TRY(hipMemsetAsync(h->Gp.p, 0, sizeof(double) * gn, h->ga->stream));
+    HIP_TRY(hipStreamSynchronize(h->ga->stream));               // (the staging's pinned buffer is free again)
+    IBO_TRY(sgp_accumulate(h, N, X, Y, lambda_host));
+    IBO_TRY(sgp_refactor(h, info));
+    h->fitted = true;
+    return IBO_OK;
+}
+
+extern "C" int ibo_sgp_add(ibo_sgp_t *h, int64_t n, const double *X, const double *Y, double *lambda_host, int *info)
+{
+    if (!h) return fail(IBO_ERR_ARG, "handle is NULL");
+    IBO_TRY(use_device(h->device));
+    if (!X || !Y) return fail(IBO_ERR_ARG, "X/Y is NULL");
+    if (n < 1) return fail(IBO_ERR_ARG, "n=%lld", (long long)n);
+    if (!h->fitted) return fail(IBO_ERR_STATE, "ibo_sgp_add before a successful fit");
+    if (!all_finite(X, (size_t)n * h->D)) return fail(IBO_ERR_ARG, "X holds a value that is not finite");
+    if (!all_finite(Y, (size_t)n)) return fail(IBO_ERR_ARG, "Y holds a value that is not finite");
+    if (info) *info = 0;
+    h->fitted = false;                                           // the kept sums are being rewritten: a failure leaves the handle unfitted
+    IBO_TRY(sgp_accumulate(h, n, X, Y, lambda_host));
+    IBO_TRY(sgp_refactor(h, info));
+    h->fitted = true;
+    return IBO_OK;
+}
+
+extern "C" int ibo_sgp_acq_batch(ibo_sgp_t *h, int64_t M, const double *Q_host, int acq, double parm, int erf_mode,
+                                 double clamp_lo, double ymax, double *mu_host, double *s2_host, double *acq_host)
+{
+    IBO_TRY(sgp_check(h, Q_host != nullptr, M, acq, erf_mode, true));
+    if (!mu_host && !s2_host && !acq_host) return fail(IBO_ERR_ARG, "every output is NULL");
+    const SgpCall c = {acq, erf_mode, parm, clamp_lo, ymax};
+    return sgp_eval_host(h, c, M, Q_host, mu_host, s2_host, acq_host);
+}
+
+extern "C" int ibo_sgp_acq_sweep(ibo_sgp_t *h, int64_t M, const double *cand_dev, int acq, double parm, int erf_mode, double clamp_lo, double ymax,
+                                 int n_excl, const double *excl_host, double excl_radius, int64_t index_base,
+                                 double *mu_dev, double *s2_dev, double *acq_dev, double *best_val, int64_t *best_idx)
+{
+    IBO_TRY(sgp_check(h, cand_dev != nullptr, M, acq, erf_mode, true));
+    if (!mu_dev && !s2_dev && !acq_dev && !best_val && !best_idx) return fail(IBO_ERR_ARG, "every output is NULL");
+    const SgpCall c = {acq, erf_mode, parm, clamp_lo, ymax};
+    SgpOut o;
+    o.mu = mu_dev; o.s2 = s2_dev; o.acq = acq_dev; o.best_val = best_val; o.best_idx = best_idx;
+    return sgp_device(h, c, M, cand_dev, M, n_excl, excl_host, excl_radius, index_base, o);
+}
+
+extern "C" int ibo_sgp_direct_max(ibo_sgp_t *h, int D, const double *lb, const double *ub, int acq, double parm, int erf_mode,
+                                  double clamp_lo, int maxiter, int maxtime, int maxsample, int compat,
+                                  double *opt, double *optx, int64_t *nsamples)
+{
+    IBO_TRY(sgp_check(h, lb && ub, 1, acq, erf_mode, false));
+    if (!opt && !optx && !nsamples) return fail(IBO_ERR_ARG, "every output is NULL");
+    if (D != h->D) return fail(IBO_ERR_ARG, "bounds have %d dimensions, the model has %d", D, h->D);
+    const SgpCall c = {acq, erf_mode, parm, clamp_lo, NAN};
+    const ibo::batch_eval_t value = [&](const double *pts, int n, double *vals) -> int {
+        return sgp_eval_host(h, c, n, pts, nullptr, nullptr, vals);
+    };
+    return direct_maximize(value, "sparse-model DIRECT", D, lb, ub, maxiter, maxtime, maxsample, compat, opt, optx, nsamples);
+}
+
+static int sgp_yy(ibo_sgp *h, double *yy)
+{
+    const size_t ldg = (size_t)h->mp + 64;
+    HIP_TRY(hipMemcpy(yy, h->Gp.p + (size_t)h->mp * ldg + h->mp, sizeof(double), hipMemcpyDeviceToHost));
+    return IBO_OK;
+}
+
+extern "C" int ibo_sgp_nlml(ibo_sgp_t *h, int kind, double *value)
+{
+    IBO_TRY(use_device(h ? h->device : 0));
+    if (!h || !value) return fail(IBO_ERR_ARG, "NULL argument");
+    if (kind != IBO_SGP_NLML_MODEL && kind != IBO_SGP_NLML_VFE) return fail(IBO_ERR_ARG, "unknown kind %d", kind);
+    if (!h->fitted) return fail(IBO_ERR_STATE, "marginal likelihood before a successful fit");
+    if (kind == IBO_SGP_NLML_VFE && h->method != IBO_SGP_DTC)
+        return fail(IBO_ERR_ARG, "the variational bound is the DTC value plus a trace term: the model was fitted as FITC");
+    double yy = 0.0;
+    IBO_TRY(sgp_yy(h, &yy));
+    double v = 0.5 * (h->ll + h->logdet_a - h->logdet_u + yy - h->wb2 + (double)h->N * log(2.0 * M_PI));
+    if (kind == IBO_SGP_NLML_VFE) v += h->tt / (2.0 * h->noise);
+    *value = v;
+    return IBO_OK;
+}
+
+extern "C" int ibo_sgp_get(ibo_sgp_t *h, int what, double *out)
+{
+    IBO_TRY(use_device(h ? h->device : 0));
+    if (!h || !out) return fail(IBO_ERR_ARG, "NULL argument");
+    if (!h->fitted) return fail(IBO_ERR_STATE, "ibo_sgp_get before a successful fit");
+    const int m = h->m;
+    const size_t ldg = (size_t)h->mp + 64;
+    switch (what) {
+    case IBO_SGP_GET_KUU: return ibo_gp_get_R(h->gu, out);
+    case IBO_SGP_GET_G:
+        HIP_TRY(hipMemcpy2D(out, sizeof(double) * m, h->Gp.p, sizeof(double) * ldg, sizeof(double) * m, (size_t)m, hipMemcpyDeviceToHost));
+        for (int a = 0; a < m; a++)                              // (only the lower tiles are kept)
+            for (int b = a + 1; b < m; b++) out[(size_t)a * m + b] = out[(size_t)b * m + a];
+        return IBO_OK;
+    case IBO_SGP_GET_A:
+        HIP_TRY(hipMemcpy(out, h->ga->A.p, sizeof(double) * (size_t)m * m, hipMemcpyDeviceToHost));
+        return IBO_OK;
+    case IBO_SGP_GET_LU: return ibo_gp_get_L(h->gu, out);
+    case IBO_SGP_GET_LA: return ibo_gp_get_L(h->ga, out);
+    case IBO_SGP_GET_B:
+        HIP_TRY(hipMemcpy(out, h->ga->Y.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost));
+        return IBO_OK;
+    case IBO_SGP_GET_ALPHA:
+        HIP_TRY(hipMemcpy(out, h->ga->alphaY.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost));
+        return IBO_OK;
+    case IBO_SGP_GET_YY: return sgp_yy(h, out);
+    case IBO_SGP_GET_LL: *out = h->ll; return IBO_OK;
+    case IBO_SGP_GET_TT: *out = h->tt; return IBO_OK;
+    case IBO_SGP_GET_N: *out = (double)h->N; return IBO_OK;
+    }
+    return fail(IBO_ERR_ARG, "unknown quantity %d", what);
+}
+
+extern "C" int ibo_sgp_stage_ms(double *ms, int reset)
+{
+    if (ms) memcpy(ms, t_sgp_ms, sizeof(t_sgp_ms));
+    if (reset) memset(t_sgp_ms, 0, sizeof(t_sgp_ms));
+    return IBO_OK;
+}

@@ -932,3 +932,6 @@ class PrefGaussianProcess(GaussianProcess):
         if getattr(self, "preferences", None) is None:      # called from the base constructor
             return GaussianProcess.addData(self, X, Y, G)
         raise NotImplementedError("can't (yet) add explicit ratings to preference GP")
+
+
+from .sparse import SparseGaussianProcess, inducingPoints      # noqa: E402,F401

@@ -1,0 +1,307 @@
+"""
+A sparse Gaussian process on inducing points (DTC / FITC) on the MI355X backend (ibo_sgp_*).
+
+    SparseGaussianProcess(kernel, X=None, Y=None, Z=None, m=None, noise=.1, jitter=1e-6, method='fitc', seed=None, device=None)
+        .addData(X, Y)  .posterior(x, getvar=True)  .posteriors(X)  .mu(x)  .negmu(x)  .nlml(kind=None)  .close()
+        attributes X, Y, Z, noise, kernel
+    inducingPoints(X, m, method='subset'|'kcenter', seed=None)
+
+The model is m rows whatever the number of observations: the fit is O(N m^2), a swept candidate costs two m-row sweeps, and addData
+accumulates into the device's kept Gram matrix -- O(n m^2 + m^3), no stored data on the device.  (X and Y are kept HERE, on the host, as
+the plain model's attributes are; nothing reads them after the first fit but max(Y) for the acquisition classes.)
+
+EI / PI / UCB(model).f / .negf / .values, acquisition.sweep and maximizeEI / PI / UCB work on it; everything else that takes a model
+refuses it with a NotImplementedError that names the call.
+"""
+import ctypes
+
+import numpy as np
+
+from .. import _lib
+
+_METHOD = {'fitc': 0, 'dtc': 1}
+_NLML_MODEL, _NLML_VFE = 0, 1
+_GET = dict(Kuu=0, G=1, A=2, Lu=3, LA=4, b=5, alpha=6, yy=7, ll=8, tt=9, N=10)
+
+_SPARSE_WHY = ("the model is a sparse GP on inducing points: only posterior, posteriors, mu, negmu, nlml, addData, EI / PI / UCB "
+               "(.f, .negf, .values), acquisition.sweep and maximizeEI / PI / UCB are built for it")
+
+
+def inducingPoints(X, m, method='subset', seed=None):
+    """m of the rows of X as inducing points, on the host: 'subset' a seeded random subset (in ascending row order), 'kcenter' greedy
+    farthest-point selection from a seeded first row (each further point is the row farthest from those chosen so far, the lowest row
+    winning ties)"""
+    X = np.array(X, dtype=float, ndmin=2)
+    N = len(X)
+    m = int(m)
+    if m < 1 or m > N:
+        raise ValueError("m=%d inducing points out of %d rows" % (m, N))
+    rng = np.random.RandomState(seed)
+    if method == 'subset':
+        return X[np.sort(rng.permutation(N)[:m])].copy()
+    if method == 'kcenter':
+        idx = [int(rng.randint(N))]
+        d2 = np.sum((X - X[idx[0]]) ** 2, axis=1)
+        for _ in range(m - 1):
+            k = int(np.argmax(d2))
+            idx.append(k)
+            d2 = np.minimum(d2, np.sum((X - X[k]) ** 2, axis=1))
+        return X[idx].copy()
+    raise ValueError("unknown selection method %r ('subset' or 'kcenter')" % (method,))
+
+
+class _DeviceSGP(object):
+    """owner of one ibo_sgp_t handle"""
+
+    def __init__(self, device=None):
+        self.device = _lib.default_device() if device is None else device
+        h = ctypes.c_void_p()
+        _lib.check(_lib.lib.ibo_sgp_create(self.device, ctypes.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            try:
+                _lib.lib.ibo_sgp_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+class SparseGaussianProcess(object):
+
+    _sparse = True
+
+    def __init__(self, kernel, X=None, Y=None, Z=None, m=None, noise=.1, jitter=1e-6, method='fitc', seed=None, device=None,
+                 prior=None, selection='subset'):
+        if prior is not None:
+            raise NotImplementedError("a mean prior (prior=): not available, %s" % _SPARSE_WHY)
+        if method not in _METHOD:
+            raise ValueError("unknown method %r ('fitc' or 'dtc')" % (method,))
+        if (X is None) != (Y is None):
+            raise ValueError
+        self.kernel = kernel
+        self.noise = noise
+        self.jitter = jitter
+        self.method = method
+        self.seed = seed
+        self.selection = selection
+        self.prior = None
+        self.G = None
+        self.name = 'SGP'
+        self._device = device
+        self._m = m
+        self._sdev = None
+        self._lambda = None
+        self.Z = None if Z is None else np.array(Z, dtype=float, ndmin=2)
+        self.X = np.zeros((0, 0))
+        self.Y = np.zeros((0))
+        if X is not None:
+            self.addData(X, Y)
+
+    # ------------------------------------------------------------------ refusals
+    def _no_gradient(self, what):
+        """the one refusal of everything that is not built for a sparse model (the name is the plain model's: the acquisition
+        modules ask every model this before they touch it)"""
+        raise NotImplementedError("%s: not available, %s" % (what, _SPARSE_WHY))
+
+    def _handle(self):
+        self._no_gradient("this call (it takes the model's ibo_gp_t handle)")
+
+    def removeData(self, *a, **k):
+        self._no_gradient("removeData")
+
+    def posterior_gradient(self, *a, **k):
+        self._no_gradient("posterior_gradient")
+
+    def posterior_cov(self, *a, **k):
+        self._no_gradient("posterior_cov")
+
+    def sample_posterior(self, *a, **k):
+        self._no_gradient("sample_posterior")
+
+    def loo(self, *a, **k):
+        self._no_gradient("loo")
+
+    def loo_score(self, *a, **k):
+        self._no_gradient("loo_score")
+
+    def addObservationPoint(self, *a, **k):
+        self._no_gradient("addObservationPoint")
+
+    # ------------------------------------------------------------------ device plumbing
+    @property
+    def _dev(self):
+        return self._sdev
+
+    def _fit(self, X, Y):
+        """fit a NEW handle from the data and swap it in only when that succeeded: a matrix that does not factor leaves the previous
+        model answering with its earlier bits"""
+        if self.Z is None:
+            if self._m is None:
+                raise ValueError("neither Z= nor m= was given")
+            self.Z = inducingPoints(X, min(int(self._m), len(X)), self.selection, self.seed)
+        ktype, hyper, sf2, _ = self.kernel._ibo_spec()
+        N, D = X.shape
+        if self.Z.shape[1] != D:
+            raise ValueError("Z has %d columns, the data %d" % (self.Z.shape[1], D))
+        dev = _DeviceSGP(self._device)
+        Zc, Xc, Yc = _lib.f64(self.Z), _lib.f64(X), _lib.f64(Y)
+        lam = np.empty(N)
+        info = ctypes.c_int(0)
+        rc = _lib.lib.ibo_sgp_fit(dev.h, ktype, D, _lib.dp(hyper), len(hyper), sf2, float(self.noise), float(self.jitter),
+                                  _METHOD[self.method], len(Zc), _lib.dp(Zc), N, _lib.dp(Xc), _lib.dp(Yc), _lib.dp(lam), ctypes.byref(info))
+        if rc != _lib.OK:
+            msg = _lib.lib.ibo_last_error()              # (closing the handle must not replace the message)
+            dev.close()
+            if rc == _lib.ERR_NOT_PD:
+                raise _lib.NotPositiveDefinite(rc, msg.decode("utf-8", "replace"))
+            raise _lib.IBOError(rc, msg.decode("utf-8", "replace"))
+        old, self._sdev = self._sdev, dev
+        if old is not None:
+            old.close()
+        self._lambda = lam
+
+    def addData(self, X, Y):
+        """the first data fit the model; later data are accumulated into the device's kept sums (ibo_sgp_add) and A is factored again.
+        A failed accumulation leaves the device handle unfitted: the model is then refitted from all the data on a new handle."""
+        X = np.array(X, dtype=float, ndmin=2)
+        Y = np.array(Y, dtype=float, ndmin=1).reshape(-1)
+        if len(X) != len(Y):
+            raise ValueError("X has %d rows, Y %d" % (len(X), len(Y)))
+        if not (np.all(np.isfinite(X)) and np.all(np.isfinite(Y))):
+            raise ValueError("X / Y hold a value that is not finite")
+        if self._sdev is None:
+            first = len(self.X) == 0
+            allX = np.copy(X) if first else np.r_[self.X, X]
+            allY = np.copy(Y) if first else np.r_[self.Y, Y]
+            self._fit(allX, allY)                      # (raises before anything of the model changes)
+            self.X, self.Y = allX, allY
+            return
+        if X.shape[1] != self.X.shape[1]:
+            raise ValueError("X has %d columns, the model %d" % (X.shape[1], self.X.shape[1]))
+        Xc, Yc = _lib.f64(X), _lib.f64(Y)
+        lam = np.empty(len(Xc))
+        info = ctypes.c_int(0)
+        _lib.check(_lib.lib.ibo_sgp_add(self._sdev.h, len(Xc), _lib.dp(Xc), _lib.dp(Yc), _lib.dp(lam), ctypes.byref(info)))
+        self.X, self.Y = np.r_[self.X, X], np.r_[self.Y, Y]
+        self._lambda = np.r_[self._lambda, lam]
+
+    def refit(self, Z=None, m=None):
+        """fit again from all the data, with other inducing points (Z=, or m= rows chosen anew)"""
+        if len(self.X) == 0:
+            raise ValueError("model has no data")
+        keep = self.Z, self._m
+        if Z is not None:
+            self.Z = np.array(Z, dtype=float, ndmin=2)
+        elif m is not None:
+            self.Z, self._m = None, m
+        try:
+            self._fit(self.X, self.Y)
+        except Exception:
+            self.Z, self._m = keep
+            raise
+
+    def close(self):
+        if self._sdev is not None:
+            self._sdev.close()
+            self._sdev = None
+
+    def _get(self, name):
+        """what the device model is made of (ibo_sgp_get): 'Kuu', 'G', 'A', 'Lu', 'LA' (m x m), 'b', 'alpha' (m), 'yy', 'll', 'tt', 'N'"""
+        m = len(self.Z)
+        code = _GET[name]
+        out = np.empty((m, m) if code <= 4 else (m if code <= 6 else 1))
+        _lib.check(_lib.lib.ibo_sgp_get(self._sdev.h, code, _lib.dp(out)))
+        return out if code <= 6 else float(out[0])
+
+    def _eval(self, Q, acq=_lib.ACQ_NONE, parm=0.0, erf_mode=_lib.ERF_NR, clamp_lo=_lib.CLAMP_PY, want=("mu", "s2"), ymax=None):
+        """host points in, host arrays out (ibo_sgp_acq_batch): the plain model's _eval"""
+        if self._sdev is None:
+            raise ValueError("model has no data")
+        Q = _lib.f64(np.atleast_2d(Q))
+        M = len(Q)
+        res = {k: np.empty(M) for k in want}
+        ptr = lambda k: _lib.dp(res[k]) if k in res else None
+        _lib.check(_lib.lib.ibo_sgp_acq_batch(self._sdev.h, M, _lib.dp(Q), acq, float(parm), erf_mode, clamp_lo,
+                                              float('nan') if ymax is None else float(ymax), ptr("mu"), ptr("s2"), ptr("acq")))
+        if "acq" in res:                             # first maximiser, NaNs never win: what the device arg-max does
+            score = np.where(np.isnan(res["acq"]), -np.inf, res["acq"])
+            k = int(np.argmax(score))
+            res["best_val"], res["best_idx"] = float(score[k]), k
+        return res
+
+    # ------------------------------------------------------------------ the plain model's API
+    def posterior(self, X, getvar=True):
+        """posterior mean (and variance, the noise included) at ONE point"""
+        if self._sdev is None:
+            return (0.0, 1.0) if getvar else 0.0
+        X = np.array(X, dtype=float, ndmin=2)
+        res = self._eval(X[:1], want=("mu", "s2") if getvar else ("mu",))
+        if getvar:
+            return res["mu"][0], res["s2"][0]
+        return res["mu"][0]
+
+    def posteriors(self, X):
+        """(mu, s2) arrays at the rows of X"""
+        res = self._eval(np.array(X, dtype=float, ndmin=2))
+        return res["mu"], res["s2"]
+
+    def mu(self, x):
+        return self.posterior(x, getvar=False)
+
+    def negmu(self, x):
+        return -self.mu(x)
+
+    def nlml(self, kind=None):
+        """the negative log marginal likelihood of the model as fitted (kind None, or the model's own method), or kind='vfe': Titsias'
+        bound, the DTC value plus its trace term (a 'dtc' model only).  Value only."""
+        if self._sdev is None:
+            raise ValueError("model has no data")
+        if kind is None or kind == self.method:
+            code = _NLML_MODEL
+        elif kind == 'vfe':
+            if self.method != 'dtc':
+                raise ValueError("kind='vfe' is the DTC value plus a trace term: fit the model with method='dtc'")
+            code = _NLML_VFE
+        else:
+            raise ValueError("kind=%r on a model fitted with method=%r" % (kind, self.method))
+        v = ctypes.c_double()
+        _lib.check(_lib.lib.ibo_sgp_nlml(self._sdev.h, code, ctypes.byref(v)))
+        return v.value
+
+    def _sweep(self, candidates, code, parm, native, ymax, exclude, exclude_radius, index_base, outputs):
+        """acquisition.sweep on this model (ibo_sgp_acq_sweep): the model's own signal variance in both modes"""
+        if self._sdev is None:
+            raise ValueError("model has no data")
+        dev = self._sdev.device
+        cand = candidates if isinstance(candidates, _lib.DeviceArray) else _lib.DeviceArray.from_host(np.atleast_2d(candidates), dev)
+        M = cand.shape[0]
+        outs = {k: _lib.DeviceArray((M,), dev) for k in outputs}
+        ex = None if exclude is None or len(exclude) == 0 else _lib.f64(np.atleast_2d(exclude))
+        bv = ctypes.c_double(); bi = ctypes.c_int64()
+        t0 = _lib.gpu_time_ms(dev)
+        _lib.check(_lib.lib.ibo_sgp_acq_sweep(
+            self._sdev.h, M, cand.ptr, code, float(parm), _lib.ERF_LIBM if native else _lib.ERF_NR,
+            _lib.CLAMP_NATIVE if native else _lib.CLAMP_PY, float('nan') if ymax is None else float(ymax),
+            0 if ex is None else len(ex), None if ex is None else _lib.dp(ex), float(exclude_radius), int(index_base),
+            outs["mu"].ptr if "mu" in outs else None, outs["s2"].ptr if "s2" in outs else None,
+            outs["acq"].ptr if "acq" in outs else None, ctypes.byref(bv), ctypes.byref(bi)))
+        res = dict(best_val=bv.value, best_idx=bi.value, kernel_ms=_lib.gpu_time_ms(dev) - t0, kernel="sparse two-frame sweep")
+        for k, v in outs.items():
+            res[k] = v.to_host()
+        return res
+
+    def _direct(self, lb, ub, code, parm, maxiter, maxtime, maxsample, compat):
+        """DIRECT on this model (ibo_sgp_direct_max): libm erf and the native clamp, as cdirectGP runs the plain model"""
+        if self._sdev is None:
+            raise ValueError("model has no data")
+        D = len(lb)
+        opt = ctypes.c_double(); optx = np.empty(D); ns = ctypes.c_int64()
+        _lib.check(_lib.lib.ibo_sgp_direct_max(self._sdev.h, D, _lib.dp(lb), _lib.dp(ub), code, float(parm), _lib.ERF_LIBM,
+                                               _lib.CLAMP_NATIVE, int(maxiter), int(maxtime), int(maxsample), 1 if compat else 0,
+                                               ctypes.byref(opt), _lib.dp(optx), ctypes.byref(ns)))
+        return opt.value, optx, ns.value

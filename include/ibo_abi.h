@@ -62,7 +62,10 @@ extern "C" {
                              * "ggp_timing": added within 8, nothing else changed;
                              * + ibo_mes_sweep, ibo_mes_batch, ibo_mes_grad_batch, ibo_mes_direct_max, ibo_mes_maxcdf, ibo_mes_scan_ms (max-value entropy
                              * search against samples of the maximum, and the max-value cdf over a candidate set that the Gumbel approximation of those
-                             * samples is fitted to) and the options "mes_chunk", "mes_timing": added within 8, nothing else changed */
+                             * samples is fitted to) and the options "mes_chunk", "mes_timing": added within 8, nothing else changed;
+                             * + ibo_sgp_create, ibo_sgp_destroy, ibo_sgp_fit, ibo_sgp_add, ibo_sgp_acq_batch, ibo_sgp_acq_sweep, ibo_sgp_direct_max,
+                             * ibo_sgp_nlml, ibo_sgp_get, ibo_sgp_stage_ms (a sparse GP on inducing points, DTC / FITC, on a handle type of its own) and the
+                             * options "sgp_chunk", "sgp_timing": added within 8, nothing else changed */
 
 /* status codes */
 #define IBO_OK              0
@@ -114,7 +117,7 @@ int         ibo_selftest_mfma(int device, double *max_abs_err);
  * gradients.  DIRECT's small batches and the copies are not event-timed and not in it.  bench.py reports it as gpu_kernel_s_total
  * so that a line can be related to an outside observer's busy-GPU samples. */
 int         ibo_gpu_time_ms(int device, double *ms);
-/* The twenty-four option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
+/* The twenty-six option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
  * Functional:  "legacy_exact" 1/0 -- acqmaxGP in libego's operation order (default) or on the MFMA sweep kernels (see acqmaxGP);
  *   "nlml_batch" B -- matrices per batched factorisation in ibo_nlml_grid (0: as many as 12 GB hold; the values do not depend on it);
  *   "pool_limit_mb" n -- the per-device free list of recycled buffers (ibo_trim);
@@ -135,8 +138,9 @@ int         ibo_gpu_time_ms(int device, double *ms);
  *   identical bits);  "ehvi_chunk" m (candidates per chunk of the ibo_ehvi_* entries, rounded up to 256, 0: by bytes, 2^25 -- identical bits
  *   among chunks of up to 4096 and among larger ones, see the ibo_ehvi_* entries);  "mes_chunk" m (candidates per chunk of the ibo_mes_* entries, rounded up to 256, 0: by bytes, 2^26 -- the same
  *   statement as "ehvi_chunk", see the ibo_mes_* entries);  "ggp_chunk" m (candidates per chunk of the ibo_ggp_* entries,
- *   rounded up to 256, 0: by bytes -- identical bits).
- * Diagnostic:  "ggp_timing" 1/0 (see ibo_ggp_stage_ms);  "kg_timing" 1/0 (see ibo_kg_stage_ms);  "qei_timing" 1/0 (see ibo_qei_stage_ms);  "ehvi_timing" 1/0 (see ibo_ehvi_scan_ms);  "mes_timing" 1/0 (see ibo_mes_scan_ms).
+ *   rounded up to 256, 0: by bytes -- identical bits);  "sgp_chunk" n (observations and candidates per chunk of the ibo_sgp_* entries,
+ *   rounded up to 256, 0: by bytes -- see those entries for what stays bit-identical).
+ * Diagnostic:  "sgp_timing" 1/0 (see ibo_sgp_stage_ms);  "ggp_timing" 1/0 (see ibo_ggp_stage_ms);  "kg_timing" 1/0 (see ibo_kg_stage_ms);  "qei_timing" 1/0 (see ibo_qei_stage_ms);  "ehvi_timing" 1/0 (see ibo_ehvi_scan_ms);  "mes_timing" 1/0 (see ibo_mes_scan_ms).
  * Env: IBO_SWEEP_IMPL=gemv|mfma, IBO_DOT_FORM, IBO_POOL_LIMIT_MB, IBO_HOST_THREADS (the legacy symbol's host crew), IBO_DEVICE (legacy symbols),
  *   IBO_NLML_GROUPS=1..4 (sub-batches of an ibo_nlml_grid batch, each on its own stream; 2; the values do not depend on it).
  * Threading (the reference's library keeps its whole model in process-wide statics, cpp/optimizeGP.cpp:36-55,240-259, and is not
@@ -960,6 +964,79 @@ int ibo_ggp_direct_max(ibo_ggp_t *h, int D, const double *lb, const double *ub, 
  * [3] the row kernel, [4] unused (0), [5] the acquisition, [6] factor-and-invert, [7] the alpha vectors. */
 #define IBO_GGP_STAGES 8
 int ibo_ggp_stage_ms(double *ms, int reset);
+
+/* ---------------------------------------------------------------- sparse (inducing-point) GP */
+/*
+ * A GP on m inducing points Z that stands for N >> m noisy observations (DTC / FITC): the fit is O(N m^2), and after it the data are
+ * gone -- the model is m rows whatever N was.  k carries sf2; every diagonal counts k(x, x) as 1 (ibo_gp_fit's rule); noise = sigma^2.
+ *   K~uu = K(Z, Z) with diagonal 1 + jitter = L_u L_u^T, W_u = L_u^-1;  q_i = |W_u k_u(x_i)|^2
+ *   lambda_i = noise + max(1 - q_i, 0) (IBO_SGP_FITC) or noise (IBO_SGP_DTC)
+ *   F[a][i] = k(z_a, x_i) / sqrt(lambda_i), y~_i = y_i / sqrt(lambda_i);  G = F F^T, b = F y~, yy = y~.y~, ll = sum log lambda_i,
+ *   tt = sum max(1 - q_i, 0);  A = K~uu + G = L_A L_A^T, W_A = L_A^-1, alpha = W_A^T W_A b
+ *   mu(x) = k_u(x)^T alpha;  s2(x) = noise + (1 - |W_u k_u(x)|^2) + |W_A k_u(x)|^2, summed in that order and THEN clipped to [clamp_lo, 10]
+ *   (it includes the noise, as the plain model's does);  EI / PI / UCB from (mu, s2) by the formula of every sweep, both erf flavours;
+ *   ymax NaN: the largest target among all data seen.
+ *   NLML = (ll + 2 sum log L_A,ii - 2 sum log L_u,ii + yy - |W_A b|^2 + N log 2 pi) / 2;  IBO_SGP_NLML_VFE (a DTC model only): + tt / (2 noise),
+ *   Titsias' bound.  Values only.
+ * The handle is its own type: no ibo_gp_* / ibo_acq_* entry accepts it.  It wraps two m-row frames on the points Z -- U (a plain fit with
+ * noise = jitter) and A (the factorisation of a matrix it is handed, noise field 0) -- and keeps G+, the (mp + 64)^2 lower tiles of
+ * [F; y~] [F; y~]^T (mp: m rounded up to 64).  Observations travel in chunks through pinned staging and are not kept: per chunk the U
+ * frame's plain sweep (the q_i), the generation of Ft and G+ += Ft Ft^T on the fp64 MFMA unit, the accumulators loaded from G+ and
+ * continued in ascending observation order.  So the bits of G, b and yy do not depend on the chunking (ibo_set_option("sgp_chunk", n):
+ * observations -- and candidates -- per chunk, rounded up to 256; 0: by bytes, 256 MiB of Ft): exactly for DTC; for FITC among chunks of one
+ * size class of the plain sweep that supplies q_i (up to 4096 rows and beyond, see "mes_chunk").  ll and tt are added per 256 observations
+ * in a fixed order.  ibo_sgp_add accumulates into the kept sums and refactors A: O(n m^2 + m^3).
+ * Candidates: per chunk the two frames' plain sweeps into scratch, then one streaming kernel; host batches and DIRECT are uploaded and take
+ * the same route, so a candidate's value is the same bits from batch, sweep and DIRECT within a size class (the statement of ibo_mes_*).
+ * Limits: 1 <= m <= IBO_SGP_MAX_M, D <= 64, N >= 1 (N < m is allowed).
+ * Errors: IBO_ERR_NO_DEVICE first; IBO_ERR_ARG for NULLs, sizes, non-finite X / Y / Z, noise <= 0, jitter < 0, an unknown method / kind /
+ * acq / erf_mode, every output NULL; IBO_ERR_NOT_PD with the 1-based pivot in *info and the matrix that failed (K~uu or A) in the message:
+ * the handle is then UNFITTED (also after a failed ibo_sgp_add); IBO_ERR_STATE before a successful fit.
+ */
+typedef struct ibo_sgp ibo_sgp_t;
+#define IBO_SGP_MAX_M 8192
+#define IBO_SGP_FITC 0
+#define IBO_SGP_DTC  1
+#define IBO_SGP_NLML_MODEL 0         /* the marginal likelihood of the model as fitted (FITC or DTC) */
+#define IBO_SGP_NLML_VFE   1         /* the DTC value + tt / (2 noise); IBO_ERR_ARG on a FITC model  */
+int ibo_sgp_create(int device, ibo_sgp_t **out);
+int ibo_sgp_destroy(ibo_sgp_t *h);
+/* Z: m x D, X: N x D, Y: N, all host; hyper / nhyper / sf2 as ibo_gp_fit.  lambda_host (optional): receives the N lambda_i. */
+int ibo_sgp_fit(ibo_sgp_t *h, int ktype, int D, const double *hyper_host, int nhyper, double sf2, double noise, double jitter, int method,
+                int m, const double *Z_host, int64_t N, const double *X_host, const double *Y_host, double *lambda_host, int *info);
+/* n more observations into the kept sums, then A is factored again.  The model needs no stored data. */
+int ibo_sgp_add(ibo_sgp_t *h, int64_t n, const double *X_host, const double *Y_host, double *lambda_host, int *info);
+/* ibo_acq_batch's arguments: host points in (Q_host: M x D), any of mu / s2 / acq out (not all NULL) */
+int ibo_sgp_acq_batch(ibo_sgp_t *h, int64_t M, const double *Q_host, int acq, double parm, int erf_mode,
+                      double clamp_lo, double ymax, double *mu_host, double *s2_host, double *acq_host);
+/* ibo_acq_sweep's arguments and arg-max rule: device candidates, optional DEVICE outputs, exclusion balls, index_base; best_val /
+ * best_idx on the host (optional): -inf and -1 when nothing is admissible. */
+int ibo_sgp_acq_sweep(ibo_sgp_t *h, int64_t M, const double *cand_dev, int acq, double parm, int erf_mode, double clamp_lo, double ymax,
+                      int n_excl, const double *excl_host, double excl_radius, int64_t index_base,
+                      double *mu_dev, double *s2_dev, double *acq_dev, double *best_val, int64_t *best_idx);
+/* ibo_direct_max on the sparse model: the same DIRECT, every batch evaluated as ibo_sgp_acq_batch does (ymax = the largest target).
+ * IBO_ERR_ARG also for IBO_ACQ_NONE, NULL bounds or D other than the model's. */
+int ibo_sgp_direct_max(ibo_sgp_t *h, int D, const double *lb, const double *ub, int acq, double parm, int erf_mode,
+                       double clamp_lo, int maxiter, int maxtime, int maxsample, int compat,
+                       double *opt, double *optx, int64_t *nsamples);
+int ibo_sgp_nlml(ibo_sgp_t *h, int kind, double *value);
+/* What the model is made of, for the tests.  m x m row-major: K~uu, G, A, L_u, L_A; m doubles: b, alpha; one double: yy, ll, tt, N. */
+#define IBO_SGP_GET_KUU   0
+#define IBO_SGP_GET_G     1
+#define IBO_SGP_GET_A     2
+#define IBO_SGP_GET_LU    3
+#define IBO_SGP_GET_LA    4
+#define IBO_SGP_GET_B     5
+#define IBO_SGP_GET_ALPHA 6
+#define IBO_SGP_GET_YY    7
+#define IBO_SGP_GET_LL    8
+#define IBO_SGP_GET_TT    9
+#define IBO_SGP_GET_N     10
+int ibo_sgp_get(ibo_sgp_t *h, int what, double *out_host);
+/* under ibo_set_option("sgp_timing", 1), accumulated per thread: [0] the q sweeps of the observations, [1] the generation of Ft, [2] the
+ * Gram product, [3] the assembly of A, [4] factor-and-invert with the alpha vectors, [5] the candidates' two sweeps, [6] the finish kernel. */
+#define IBO_SGP_STAGES 8
+int ibo_sgp_stage_ms(double *ms, int reset);
 
 /* DIRECT minimisation of a HOST callback with the reference's semantics
  * (cpp/direct.cpp:329; what ego.utils.optimize.cdirect wraps), plus the sample
