@@ -5,10 +5,10 @@ The library is the product's ONLY compute path: if it is missing this module
 raises at import, and every compute call raises IBOError(IBO_ERR_NO_DEVICE)
 when no MI355X is visible.  Nothing here falls back to NumPy.
 
-Every symbol of the header is bound below and listed in EXPORTED (104 of them: tests/test_cpu_host.py holds the two lists to
+Every symbol of the header is bound below and listed in EXPORTED (116 of them: tests/test_cpu_host.py holds the two lists to
 the header and to the library), the ibo_qei_* entries of the parallel expected improvement and the ibo_ehvi_* entries of the
-two-objective hypervolume improvement, the ibo_ggp_* entries of a GP observed with gradients and the ibo_mes_* entries of
-max-value entropy search among them.
+two-objective hypervolume improvement, the ibo_ggp_* entries of a GP observed with gradients, the ibo_mes_* entries of
+max-value entropy search and the ibo_sgp_* entries of the sparse GP with its likelihood gradient among them.
 """
 import ctypes
 import os
@@ -176,6 +176,9 @@ _sig("ibo_sgp_direct_max", c_int, _SGP, c_int, _DP, _DP, c_int, c_double, c_int,
 _sig("ibo_sgp_nlml", c_int, _SGP, c_int, _DP)
 _sig("ibo_sgp_get", c_int, _SGP, c_int, _DP)
 _sig("ibo_sgp_stage_ms", c_int, _DP, c_int)
+_sig("ibo_sgp_nlml_grad", c_int, c_int, c_int, c_int, _DP, c_int, c_double, c_double, c_double, c_int, c_int, _DP, c_int64, _DP, _DP,
+     c_int, POINTER(c_int), POINTER(c_int), _DP, _DP, _DP, _DP, POINTER(c_int))
+_sig("ibo_sgp_grad_stage_ms", c_int, _DP, c_int)
 _sig("ibo_direct_host", c_int, OBJECTIVE, c_int, _DP, _DP, c_int, c_int, c_int, c_int, _DP, _DP, POINTER(c_int64))
 _sig("ibo_nlml_grid", c_int, c_int, c_int, c_int, c_int, _DP, _DP, c_int, _DP, c_int, _DP, c_double, _DP)
 _sig("ibo_nlml_grad", c_int, c_int, c_int, c_int, c_int, _DP, _DP, _DP, c_int, c_double, c_double, c_int,
@@ -206,7 +209,7 @@ EXPORTED = ["ibo_abi_version", "ibo_last_error", "ibo_device_count", "ibo_device
             "ibo_ggp_create", "ibo_ggp_destroy", "ibo_ggp_info", "ibo_ggp_fit", "ibo_ggp_get_R", "ibo_ggp_get_L", "ibo_ggp_acq_batch", "ibo_ggp_acq_sweep",
             "ibo_ggp_direct_max", "ibo_ggp_stage_ms",
             "ibo_sgp_create", "ibo_sgp_destroy", "ibo_sgp_fit", "ibo_sgp_add", "ibo_sgp_acq_batch", "ibo_sgp_acq_sweep", "ibo_sgp_direct_max",
-            "ibo_sgp_nlml", "ibo_sgp_get", "ibo_sgp_stage_ms", "ibo_direct_host", "ibo_nlml_grid", "ibo_nlml_grad", "ibo_gp_loo", "ibo_loo_grad",
+            "ibo_sgp_nlml", "ibo_sgp_get", "ibo_sgp_stage_ms", "ibo_sgp_nlml_grad", "ibo_sgp_grad_stage_ms", "ibo_direct_host", "ibo_nlml_grid", "ibo_nlml_grad", "ibo_gp_loo", "ibo_loo_grad",
             "ibo_comm_get_unique_id", "ibo_comm_init", "ibo_comm_destroy", "ibo_comm_count", "ibo_comm_argmax", "ibo_comm_allreduce_sum", "ibo_acq_sweep_exchange", "ibo_comm_barrier",
             "acqmaxGP", "direct", "logCDFs"]
 

@@ -120,13 +120,13 @@ static void exec_sets_prewarm(int dev);
 // one kernel of every translation unit (each defines its ibo_touch_*): their code objects are loaded now, not in the middle of the first
 // call that needs them
 void ibo_touch_small2(); void ibo_touch_sweep(); void ibo_touch_sweep2(); void ibo_touch_linalg(); void ibo_touch_assemble(); void ibo_touch_update3();
-void ibo_touch_legacy(); void ibo_touch_comm(); void ibo_touch_cov(); void ibo_touch_cacq(); void ibo_touch_kg(); void ibo_touch_paths(); void ibo_touch_qei(); void ibo_touch_ehvi(); void ibo_touch_gradobs(); void ibo_touch_mes(); void ibo_touch_sparse();
+void ibo_touch_legacy(); void ibo_touch_comm(); void ibo_touch_cov(); void ibo_touch_cacq(); void ibo_touch_kg(); void ibo_touch_paths(); void ibo_touch_qei(); void ibo_touch_ehvi(); void ibo_touch_gradobs(); void ibo_touch_mes(); void ibo_touch_sparse(); void ibo_touch_sparse_grad();
 void ibo_touch_s2fam_FAM_SE_0(); void ibo_touch_s2fam_FAM_SE_1(); void ibo_touch_s2fam_FAM_M3_0(); void ibo_touch_s2fam_FAM_M3_1();
 void ibo_touch_s2fam_FAM_M5_0(); void ibo_touch_s2fam_FAM_M5_1();
 static void load_code_objects()
 {
     ibo_touch_small2(); ibo_touch_sweep(); ibo_touch_sweep2(); ibo_touch_linalg(); ibo_touch_assemble(); ibo_touch_update3();
-    ibo_touch_legacy(); ibo_touch_comm(); ibo_touch_cov(); ibo_touch_cacq(); ibo_touch_kg(); ibo_touch_paths(); ibo_touch_qei(); ibo_touch_ehvi(); ibo_touch_gradobs(); ibo_touch_mes(); ibo_touch_sparse();
+    ibo_touch_legacy(); ibo_touch_comm(); ibo_touch_cov(); ibo_touch_cacq(); ibo_touch_kg(); ibo_touch_paths(); ibo_touch_qei(); ibo_touch_ehvi(); ibo_touch_gradobs(); ibo_touch_mes(); ibo_touch_sparse(); ibo_touch_sparse_grad();
     ibo_touch_s2fam_FAM_SE_0(); ibo_touch_s2fam_FAM_SE_1(); ibo_touch_s2fam_FAM_M3_0(); ibo_touch_s2fam_FAM_M3_1();
     ibo_touch_s2fam_FAM_M5_0(); ibo_touch_s2fam_FAM_M5_1();
     (void)hipGetLastError();

@@ -183,6 +183,7 @@ int ibo_comm_exchange_dev(ibo_comm_t *c, hipStream_t s, const double *res_v, con
 uint64_t alloc_generation(int device, const void *p, size_t bytes, size_t *offset);                       // abi_core.hip
 int ensure_pinned(ibo_gp *g, size_t need);                                                                // abi_core.hip
 int make_kparams(int ktype, int D, const double *hyper, int nhyper, double sf2, KParams *kp);             // abi_fit.hip
+void sgp_grad_trim(int device);                                                                           // abi_sparse.hip: gives ibo_sgp_nlml_grad's private handle back (ibo_trim)
 int ensure_R(ibo_gp *g);                                                                                  // abi_fit.hip: R = K(X, X) + diag, formed on request
 int fit_begin(ibo_gp *g, int ktype, int N, int D, const double *X, const double *Y, const double *hyper, int nhyper, double sf2,
               double noise, bool reverse, KParams *kp);                                                   // abi_fit.hip: what every fit starts with (the staging)

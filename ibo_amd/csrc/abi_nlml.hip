@@ -46,6 +46,7 @@ extern "C" int ibo_trim(int device)
     gw.lpart.release(); gw.lout.release(); gw.lmu.release();
     gw.hostX.clear(); gw.hostY.clear();              // (dX / dY went back to the pool: nothing of this data is on the device any more)
     if (gw.pin) { (void)hipHostFree(gw.pin); gw.pin = nullptr; }
+    sgp_grad_trim(device);                           // (ibo_sgp_nlml_grad's private handle)
     pool_trim(device);
     return IBO_OK;
 }

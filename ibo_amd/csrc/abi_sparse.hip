@@ -11,13 +11,21 @@
 //   refactor          K~uu (the U frame's R) + G -> sgp_assemble_kernel -> fit_factor on the A frame
 //   chunk of points   U sweep, A sweep into pool scratch -> sgp_finish_kernel; launch_argmax_final for the winner
 // Host batches and DIRECT are uploaded and take the route of the sweep: the same bits within a size class of the plain sweep (class_padded).
+// ibo_sgp_nlml_grad (at the end; kernels: sparse_grad.hip) is stateless: ibo_sgp_fit on a private per-device handle, then
+//   the inverses      A^-1 = W_A^T W_A, K~uu^-1 = W_u^T W_u (launch_wtw)
+//   chunk of data     upload -> U sweep, A sweep (q, mu, a) -> sgp_grad_obs_kernel -> sgp_grad_gen_kernel -> sgp_grad_contract_kernel
+//                     -> sgp_grad_reduce_kernel; not for dtc: H += (K E) K^T (sgp_abt_kernel)
+//   after the chunks  S from A^-1, K~uu^-1, alpha and K~uu^-1 H K~uu^-1, then the contraction kernel again with Z as the observations
 #include "abi_eval.h"
 #include "abi_factor.h"
 #include "sparse.h"
+#include "sparse_grad.h"
 
 std::atomic<int> g_sgp_chunk{0};      // ibo_set_option("sgp_chunk", n): observations / candidates per chunk (rounded up to 256); 0: by bytes
 std::atomic<int> g_sgp_timing{0};     // ibo_set_option("sgp_timing", 1): HIP events around every stage, read with ibo_sgp_stage_ms
 static thread_local double t_sgp_ms[IBO_SGP_STAGES];
+static thread_local double t_sgp_grad_ms[IBO_SGP_GRAD_STAGES];
+enum { SGP_GR_FIT = 0, SGP_GR_INVERSES, SGP_GR_SWEEPS, SGP_GR_GEN, SGP_GR_CONTRACT, SGP_GR_GRAM, SGP_GR_UU, SGP_GR_REDUCE };
 enum { SGP_ST_Q = 0, SGP_ST_GEN, SGP_ST_GRAM, SGP_ST_ASSEMBLE, SGP_ST_FACTOR, SGP_ST_SWEEPS, SGP_ST_FINISH };
 
 struct ibo_sgp {
@@ -37,6 +45,7 @@ namespace {
 // the diagnostic's events: made per call, a stage at a time (the stage's stream is waited for)
 struct SgpClock {
     bool on = false;
+    double *dst = t_sgp_ms;                  // (the gradient's stages: t_sgp_grad_ms)
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ~SgpClock() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
     int make() { on = g_sgp_timing != 0; if (on) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); } return IBO_OK; }
@@ -46,7 +55,7 @@ struct SgpClock {
         if (!on) return IBO_OK;
         float ms = 0.f;
         HIP_TRY(hipEventRecord(e1, s)); HIP_TRY(hipEventSynchronize(e1)); HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        t_sgp_ms[stage] += ms;
+        dst[stage] += ms;
         return IBO_OK;
     }
 };
@@ -439,5 +448,210 @@ extern "C" int ibo_sgp_stage_ms(double *ms, int reset)
 {
     if (ms) memcpy(ms, t_sgp_ms, sizeof(t_sgp_ms));
     if (reset) memset(t_sgp_ms, 0, sizeof(t_sgp_ms));
+    return IBO_OK;
+}
+
+// ------------------------------------------------------------------------ the marginal likelihood's gradient
+// One private handle per device, kept between calls (a learning loop calls with another theta / noise / Z dozens of times) and given back
+// by ibo_trim; the caller holds g_dev_mu.
+static ibo_sgp *g_sgp_grad_handle[16];
+
+void sgp_grad_trim(int device)
+{
+    ibo_sgp *&h = g_sgp_grad_handle[device & 15];
+    if (h) { (void)ibo_sgp_destroy(h); h = nullptr; }
+}
+
+namespace {
+
+struct SgpGradTotals { std::vector<double> Z[2], L[2]; double S[2]; double csum; };
+
+// After a successful fit of h: the pass over the observations and the K~uu contraction.  tot: [0] the data's sums, [1] K~uu's.
+int sgp_grad_pass(ibo_sgp *h, int kind, int64_t N, const double *X, const double *Y, SgpGradTotals *tot)
+{
+    ibo_gp *gu = h->gu, *ga = h->ga;
+    hipStream_t su = gu->stream, sa = ga->stream;
+    const int D = h->D, m = h->m, mp = h->mp, ldi = ga->Npad;
+    if (gu->Npad != ldi || ldi < mp) return fail(IBO_ERR_STATE, "the two frames are padded to %d and %d rows for mp=%d", gu->Npad, ldi, mp);
+    const bool two = kind != SGP_GRAD_DTC;                      // a DTC objective has e = 0: no K~uu^-1 half, no signed Gram matrix
+    const int ldb = (two ? 2 : 1) * mp;
+    SgpClock clock;
+    clock.dst = t_sgp_grad_ms;
+    IBO_TRY(clock.make());
+    // the inverses: A^-1 = W_A^T W_A, K~uu^-1 = W_u^T W_u (ibo_nlml_grad's product)
+    const size_t nn = (size_t)ldi * ldi;
+    ScopedBuf<double> Ainv, Uinv, wt;
+    IBO_TRY(Ainv.ensure(nn)); IBO_TRY(Uinv.ensure(nn)); IBO_TRY(wt.ensure(nn));
+    HIP_TRY(hipStreamSynchronize(su));
+    IBO_TRY(clock.start(sa));
+    KERNEL_TRY(launch_wtw(ga->W.p, wt.p, Ainv.p, ldi, sa));
+    KERNEL_TRY(launch_wtw(gu->W.p, wt.p, Uinv.p, ldi, sa));
+    IBO_TRY(clock.stop(sa, SGP_GR_INVERSES));
+    // the chunks: the fit's chunking, so that the U sweep gives the fit's q_i bit for bit
+    const int64_t nc = sgp_chunking(N, ((int64_t)256 << 20) / (8 * (int64_t)(mp + 64)));
+    const int64_t rows = class_padded(nc, nc), ldmax = (nc + 63) / 64 * 64, nblkmax = (ldmax + 255) / 256;
+    const int rb = mp / 64;
+    // a workgroup per 64 inducing rows and strip of tiles: about 1024 workgroups, the strips as even as the tiles allow
+    const int nsmax = 1024 / rb < 1 ? 1 : 1024 / rb;
+    auto strips_for = [&](int ntiles, int *tps) { const int ns = nsmax < ntiles ? nsmax : ntiles; *tps = (ntiles + ns - 1) / ns; return (ntiles + *tps - 1) / *tps; };
+    ScopedBuf<double> xc, yc, ms, per, Bo, Kt, H, part, pc, totd;
+    IBO_TRY(xc.ensure((size_t)rows * D)); IBO_TRY(yc.ensure((size_t)nc)); IBO_TRY(ms.ensure(3 * (size_t)rows));
+    IBO_TRY(per.ensure(3 * (size_t)ldmax)); IBO_TRY(Bo.ensure((size_t)ldmax * ldb)); IBO_TRY(pc.ensure((size_t)nblkmax));
+    if (two) { IBO_TRY(Kt.ensure(2 * (size_t)mp * ldmax)); IBO_TRY(H.ensure(3 * (size_t)mp * mp)); }
+    const size_t pzn = (size_t)nsmax * mp * D, psn = (size_t)nsmax * rb;
+    IBO_TRY(part.ensure(2 * pzn + psn));
+    const size_t tn = (size_t)m * D;
+    IBO_TRY(totd.ensure(2 * (2 * tn + 1)));
+    HIP_TRY(hipMemsetAsync(totd.p, 0, sizeof(double) * 2 * (2 * tn + 1), sa));
+    if (two) HIP_TRY(hipMemsetAsync(H.p, 0, sizeof(double) * (size_t)mp * mp, sa));
+    IBO_TRY(sgp_pinned(h, (size_t)rows * D + (size_t)nc + (size_t)nblkmax));
+    double *lam = per.p, *ev = per.p + ldmax, *rv = per.p + 2 * ldmax;
+    double *partZ = part.p, *partL = part.p + pzn, *partS = part.p + 2 * pzn;
+    // the strips a launch uses, no more: its workgroups add to their own rows of partZ / partL (every entry of partS is written)
+    auto zero_partials = [&](int nstrips) -> int {
+        HIP_TRY(hipMemsetAsync(partZ, 0, sizeof(double) * (size_t)nstrips * mp * D, sa));
+        HIP_TRY(hipMemsetAsync(partL, 0, sizeof(double) * (size_t)nstrips * mp * D, sa));
+        return IBO_OK;
+    };
+    SgpGradArgs g;
+    memset(&g, 0, sizeof(g));
+    g.kp = h->kp; g.m = m; g.mp = mp; g.Z = ga->Xp.p; g.ldz = ga->DP; g.Ainv = Ainv.p; g.Uinv = Uinv.p; g.ldi = ldi; g.two = two ? 1 : 0;
+    g.Bo = Bo.p; g.ldb = ldb; g.alpha = ga->alphaY.p; g.rv = rv; g.partZ = partZ; g.partL = partL; g.partS = partS;
+    tot->csum = 0.0;
+    for (int64_t c0 = 0; c0 < N; c0 += nc) {
+        const int64_t k = N - c0 < nc ? N - c0 : nc, kp = class_padded(k, nc), nblk = (k + 255) / 256;
+        const int ld = (int)((k + 63) / 64 * 64);
+        double *px = h->pin, *py = px + (size_t)rows * D, *pp = py + nc;
+        memcpy(px, X + (size_t)c0 * D, sizeof(double) * (size_t)k * D);
+        memset(px + (size_t)k * D, 0, sizeof(double) * (size_t)(kp - k) * D);
+        memcpy(py, Y + c0, sizeof(double) * (size_t)k);
+        HIP_TRY(hipMemcpyAsync(xc.p, px, sizeof(double) * (size_t)kp * D, hipMemcpyHostToDevice, su));
+        HIP_TRY(hipMemcpyAsync(yc.p, py, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, su));
+        // the two frames' plain sweeps, as the candidate route runs them: q_i, mu_i, a_i
+        SweepRequest r;
+        r.M = kp; r.cand_dev = xc.p; r.acq = IBO_ACQ_NONE; r.clamp_lo = -1.0; r.s2_dev = ms.p;
+        IBO_TRY(clock.start(su));
+        IBO_TRY(run_sweep(gu, r));
+        HIP_TRY(hipStreamSynchronize(su));
+        r.mu_dev = ms.p + rows; r.s2_dev = ms.p + 2 * rows;
+        IBO_TRY(run_sweep(ga, r));
+        if (clock.on) { HIP_TRY(hipStreamSynchronize(sa)); IBO_TRY(clock.stop(su, SGP_GR_SWEEPS)); }
+        SgpGradObsArgs o;
+        memset(&o, 0, sizeof(o));
+        o.n = (int)k; o.ld = ld; o.kind = kind; o.noise = h->noise; o.jitter = h->jitter; o.s2u = ms.p; o.mua = ms.p + rows; o.s2a = ms.p + 2 * rows;
+        o.Y = yc.p; o.lam = lam; o.ev = ev; o.rv = rv; o.part = pc.p;
+        SgpGradGenArgs ge;
+        memset(&ge, 0, sizeof(ge));
+        ge.kp = h->kp; ge.m = m; ge.mp = mp; ge.Z = ga->Xp.p; ge.ldz = ga->DP; ge.X = xc.p; ge.n = (int)k; ge.ld = ld; ge.lam = lam; ge.ev = ev;
+        ge.two = two ? 1 : 0; ge.Bo = Bo.p; ge.ldb = ldb; ge.Kt = two ? Kt.p : nullptr; ge.KEt = two ? Kt.p + (size_t)mp * ld : nullptr;
+        IBO_TRY(clock.start(sa));
+        KERNEL_TRY(launch_sgp_grad_obs(o, sa));
+        KERNEL_TRY(launch_sgp_grad_gen(ge, sa));
+        IBO_TRY(clock.stop(sa, SGP_GR_GEN));
+        g.X = xc.p; g.ldx = D; g.n = (int)k; g.ntiles = ld / 64;
+        g.nstrips = strips_for(g.ntiles, &g.tiles_per_strip);
+        if (g.nstrips > nsmax) return fail(IBO_ERR_STATE, "%d strips, room for %d", g.nstrips, nsmax);
+        IBO_TRY(zero_partials(g.nstrips));
+        IBO_TRY(clock.start(sa));
+        KERNEL_TRY(launch_sgp_grad_contract(g, 0, sa));
+        IBO_TRY(clock.stop(sa, SGP_GR_CONTRACT));
+        IBO_TRY(clock.start(sa));
+        KERNEL_TRY(launch_sgp_grad_reduce(partZ, partL, partS, g.nstrips, m, mp, D, totd.p, totd.p + tn, totd.p + 2 * tn, sa));
+        IBO_TRY(clock.stop(sa, SGP_GR_REDUCE));
+        if (two) {                                               // H += (K E) K^T, the lower tiles, continued in ascending observation order
+            IBO_TRY(clock.start(sa));
+            KERNEL_TRY(launch_sgp_abt(ge.KEt, ld, ge.Kt, ld, H.p, mp, mp, ld, 1, 1, sa));
+            IBO_TRY(clock.stop(sa, SGP_GR_GRAM));
+        }
+        HIP_TRY(hipMemcpyAsync(pp, pc.p, sizeof(double) * (size_t)nblk, hipMemcpyDeviceToHost, sa));
+        HIP_TRY(hipStreamSynchronize(sa));
+        for (int64_t b = 0; b < nblk; b++) tot->csum += pp[b];  // ascending blocks of 256
+    }
+    // S = dNL/dK~uu, then the same contraction with Z in the role of the observations
+    IBO_TRY(clock.start(sa));
+    double *Hm = H.p, *T = two ? H.p + (size_t)mp * mp : nullptr, *M = two ? H.p + 2 * (size_t)mp * mp : nullptr;
+    if (two) {
+        KERNEL_TRY(launch_sgp_mirror(Hm, mp, mp, sa));
+        KERNEL_TRY(launch_sgp_abt(Uinv.p, ldi, Hm, mp, T, mp, mp, mp, 0, 0, sa));          // T = K~uu^-1 H     (H symmetric)
+        KERNEL_TRY(launch_sgp_abt(T, mp, Uinv.p, ldi, M, mp, mp, mp, 0, 0, sa));           // M = T K~uu^-1     (K~uu^-1 symmetric)
+    }
+    ScopedBuf<double> Sbuf;
+    IBO_TRY(Sbuf.ensure((size_t)mp * mp));
+    double *S = Sbuf.p;
+    KERNEL_TRY(launch_sgp_grad_S(Ainv.p, Uinv.p, ldi, ga->alphaY.p, M, mp, m, mp, S, sa));
+    g.X = ga->Xp.p; g.ldx = ga->DP; g.n = m; g.ntiles = rb; g.S = S; g.lds = mp;
+    g.nstrips = strips_for(g.ntiles, &g.tiles_per_strip);
+    if (g.nstrips > nsmax) return fail(IBO_ERR_STATE, "%d strips, room for %d", g.nstrips, nsmax);
+    IBO_TRY(zero_partials(g.nstrips));
+    KERNEL_TRY(launch_sgp_grad_contract(g, 1, sa));
+    double *t1 = totd.p + 2 * tn + 1;
+    KERNEL_TRY(launch_sgp_grad_reduce(partZ, partL, partS, g.nstrips, m, mp, D, t1, t1 + tn, t1 + 2 * tn, sa));
+    IBO_TRY(clock.stop(sa, SGP_GR_UU));
+    std::vector<double> host(2 * (2 * tn + 1));
+    HIP_TRY(hipMemcpyAsync(host.data(), totd.p, sizeof(double) * host.size(), hipMemcpyDeviceToHost, sa));
+    HIP_TRY(hipStreamSynchronize(sa));
+    for (int w = 0; w < 2; w++) {
+        const double *p = host.data() + (size_t)w * (2 * tn + 1);
+        tot->Z[w].assign(p, p + tn); tot->L[w].assign(p + tn, p + 2 * tn); tot->S[w] = p[2 * tn];
+    }
+    return IBO_OK;
+}
+
+}  // namespace
+
+extern "C" int ibo_sgp_nlml_grad(int device, int ktype, int D, const double *hyper, int nhyper, double sf2, double noise, double jitter, int kind,
+                                 int m, const double *Z, int64_t N, const double *X, const double *Y, int ngrad, const int *modes, const int *dims,
+                                 double *value, double *grad_hyper, double *grad_lognoise, double *grad_Z, int *info)
+{
+    IBO_TRY(use_device(device));
+    if (!hyper || !Z || !X || !Y || !value) return fail(IBO_ERR_ARG, "NULL argument");
+    if (kind != IBO_SGP_FITC && kind != IBO_SGP_DTC && kind != IBO_SGP_VFE) return fail(IBO_ERR_ARG, "unknown kind %d", kind);
+    if (ngrad < 0 || ngrad > IBO_GRAD_MAX) return fail(IBO_ERR_ARG, "ngrad=%d unsupported (0..%d)", ngrad, IBO_GRAD_MAX);
+    if (ngrad > 0 && (!modes || !dims)) return fail(IBO_ERR_ARG, "modes / dims is NULL");
+    for (int i = 0; i < ngrad; i++)
+        if (modes[i] < 0 || modes[i] > 4 || dims[i] < 0 || dims[i] >= D) return fail(IBO_ERR_ARG, "bad derivative spec");
+    std::lock_guard<std::mutex> lk(g_dev_mu[device & 15]);      // (the private handle is per device)
+    ibo_sgp *&h = g_sgp_grad_handle[device & 15];
+    if (!h) IBO_TRY(ibo_sgp_create(device, &h));
+    SgpClock clock;
+    clock.dst = t_sgp_grad_ms;
+    IBO_TRY(clock.make());
+    IBO_TRY(clock.start(h->ga->stream));
+    IBO_TRY(ibo_sgp_fit(h, ktype, D, hyper, nhyper, sf2, noise, jitter, kind == IBO_SGP_VFE ? IBO_SGP_DTC : kind, m, Z, N, X, Y, nullptr, info));
+    IBO_TRY(clock.stop(h->ga->stream, SGP_GR_FIT));
+    double v = 0.0;
+    IBO_TRY(ibo_sgp_nlml(h, kind == IBO_SGP_VFE ? IBO_SGP_NLML_VFE : IBO_SGP_NLML_MODEL, &v));
+    const bool want_hyper = ngrad > 0 && grad_hyper;
+    if (want_hyper || grad_lognoise || grad_Z) {
+        SgpGradTotals tot;
+        IBO_TRY(sgp_grad_pass(h, kind, N, X, Y, &tot));
+        const KParams &kp = h->kp;
+        // dNL/dlog l_d = -2 w_d (sum_a L[a][d]), the rows in ascending order, the data's sum and then K~uu's
+        std::vector<double> Ld((size_t)D, 0.0);
+        for (int d = 0; d < D; d++) {
+            double s0 = 0.0, s1 = 0.0;
+            for (int a = 0; a < m; a++) { s0 += tot.L[0][(size_t)a * D + d]; s1 += tot.L[1][(size_t)a * D + d]; }
+            Ld[d] = -2.0 * kp.w[d] * (s0 + s1);
+        }
+        if (want_hyper)
+            for (int i = 0; i < ngrad; i++) {
+                if (modes[i] == 0) grad_hyper[i] = Ld[dims[i]];
+                else if (modes[i] == 2) grad_hyper[i] = 2.0 * (tot.S[0] + tot.S[1]);
+                else { double s = 0.0; for (int d = 0; d < D; d++) s += Ld[d]; grad_hyper[i] = s; }      // one length scale for every dimension
+            }
+        if (grad_lognoise) *grad_lognoise = noise * (tot.csum - (kind == IBO_SGP_VFE ? h->tt / (2.0 * noise * noise) : 0.0));
+        if (grad_Z)
+            for (int a = 0; a < m; a++)
+                for (int d = 0; d < D; d++)
+                    grad_Z[(size_t)a * D + d] = 2.0 * kp.w[d] * (tot.Z[0][(size_t)a * D + d] + 2.0 * tot.Z[1][(size_t)a * D + d]);
+    }
+    *value = v;
+    return IBO_OK;
+}
+
+extern "C" int ibo_sgp_grad_stage_ms(double *ms, int reset)
+{
+    if (ms) memcpy(ms, t_sgp_grad_ms, sizeof(t_sgp_grad_ms));
+    if (reset) memset(t_sgp_grad_ms, 0, sizeof(t_sgp_grad_ms));
     return IBO_OK;
 }

@@ -3,12 +3,15 @@ A sparse Gaussian process on inducing points (DTC / FITC) on the MI355X backend 
 
     SparseGaussianProcess(kernel, X=None, Y=None, Z=None, m=None, noise=.1, jitter=1e-6, method='fitc', seed=None, device=None)
         .addData(X, Y)  .posterior(x, getvar=True)  .posteriors(X)  .mu(x)  .negmu(x)  .nlml(kind=None)  .close()
+        .nlml_gradient(kind=None, wrt=('hyper', 'noise', 'Z'))      <- the objective and its gradient at the model's parameters
+        .learn(kind=None, learn_hyper=True, learn_noise=True, learn_Z=True, maxiter=50, bounds=None)      <- L-BFGS-B on it
         attributes X, Y, Z, noise, kernel
     inducingPoints(X, m, method='subset'|'kcenter', seed=None)
 
 The model is m rows whatever the number of observations: the fit is O(N m^2), a swept candidate costs two m-row sweeps, and addData
 accumulates into the device's kept Gram matrix -- O(n m^2 + m^3), no stored data on the device.  (X and Y are kept HERE, on the host, as
-the plain model's attributes are; nothing reads them after the first fit but max(Y) for the acquisition classes.)
+the plain model's attributes are; nothing reads them after the first fit but max(Y) for the acquisition classes -- and nlml_gradient /
+learn, which stream them through ibo_sgp_nlml_grad again.)
 
 EI / PI / UCB(model).f / .negf / .values, acquisition.sweep and maximizeEI / PI / UCB work on it; everything else that takes a model
 refuses it with a NotImplementedError that names the call.
@@ -23,8 +26,50 @@ _METHOD = {'fitc': 0, 'dtc': 1}
 _NLML_MODEL, _NLML_VFE = 0, 1
 _GET = dict(Kuu=0, G=1, A=2, Lu=3, LA=4, b=5, alpha=6, yy=7, ll=8, tt=9, N=10)
 
-_SPARSE_WHY = ("the model is a sparse GP on inducing points: only posterior, posteriors, mu, negmu, nlml, addData, EI / PI / UCB "
-               "(.f, .negf, .values), acquisition.sweep and maximizeEI / PI / UCB are built for it")
+_KIND = {'fitc': 0, 'dtc': 1, 'vfe': 2}
+
+_SPARSE_WHY = ("the model is a sparse GP on inducing points: only posterior, posteriors, mu, negmu, nlml, nlml_gradient, learn, addData, "
+               "EI / PI / UCB (.f, .negf, .values), acquisition.sweep and maximizeEI / PI / UCB are built for it")
+
+
+def nlml_grad_raw(kernel, X, Y, Z, noise, jitter, kind, ngrad=None, want=('hyper', 'noise', 'Z'), device=None):
+    """ibo_sgp_nlml_grad for a kernel object: (value, dict of the gradients asked for) with respect to the LOG of the kernel's first
+    ngrad hyper-parameters (kernel._ibo_grad_spec; None: all), the log noise and the inducing points.  kind: 'fitc', 'dtc' or 'vfe'."""
+    if kind not in _KIND:
+        raise ValueError("unknown objective %r ('fitc', 'dtc' or 'vfe')" % (kind,))
+    Xc, Yc, Zc = _lib.rows(X), _lib.f64(Y), _lib.f64(np.array(Z, dtype=float, ndmin=2))
+    N, D = Xc.shape
+    if len(Yc) != N:
+        raise ValueError("X has %d rows, Y %d" % (N, len(Yc)))
+    if Zc.shape[1] != D:
+        raise ValueError("Z has %d columns, the data %d" % (Zc.shape[1], D))
+    ktype, hyper, sf2, _ = kernel._ibo_spec()
+    spec = kernel._ibo_grad_spec(D)
+    if ngrad is not None:
+        if len(spec) < ngrad:
+            raise ValueError("kernel has %d hyperparameters, %d gradients requested" % (len(spec), ngrad))
+        spec = spec[:ngrad]
+    n = len(spec) if 'hyper' in want else 0
+    modes = (ctypes.c_int * max(n, 1))(*[s[0] for s in spec[:n]])
+    dims = (ctypes.c_int * max(n, 1))(*[s[1] for s in spec[:n]])
+    gh = np.empty(n) if n else None
+    gn = ctypes.c_double() if 'noise' in want else None
+    gz = np.empty(Zc.shape) if 'Z' in want else None
+    v = ctypes.c_double()
+    info = ctypes.c_int(0)
+    _lib.check(_lib.lib.ibo_sgp_nlml_grad(_lib.default_device() if device is None else device, ktype, D, _lib.dp(hyper), len(hyper), sf2,
+                                          float(noise), float(jitter), _KIND[kind], len(Zc), _lib.dp(Zc), N, _lib.dp(Xc), _lib.dp(Yc),
+                                          n, modes, dims, ctypes.byref(v), None if gh is None else _lib.dp(gh),
+                                          None if gn is None else ctypes.cast(ctypes.byref(gn), ctypes.POINTER(ctypes.c_double)),
+                                          None if gz is None else _lib.dp(gz), ctypes.byref(info)))
+    out = {}
+    if 'hyper' in want:
+        out['hyper'] = gh if gh is not None else np.empty(0)
+    if gn is not None:
+        out['noise'] = gn.value
+    if gz is not None:
+        out['Z'] = gz
+    return v.value, out
 
 
 def inducingPoints(X, m, method='subset', seed=None):
@@ -258,7 +303,7 @@ class SparseGaussianProcess(object):
 
     def nlml(self, kind=None):
         """the negative log marginal likelihood of the model as fitted (kind None, or the model's own method), or kind='vfe': Titsias'
-        bound, the DTC value plus its trace term (a 'dtc' model only).  Value only."""
+        bound, the DTC value plus its trace term (a 'dtc' model only).  Value only: nlml_gradient gives the gradient."""
         if self._sdev is None:
             raise ValueError("model has no data")
         if kind is None or kind == self.method:
@@ -272,6 +317,88 @@ class SparseGaussianProcess(object):
         v = ctypes.c_double()
         _lib.check(_lib.lib.ibo_sgp_nlml(self._sdev.h, code, ctypes.byref(v)))
         return v.value
+
+    def _objective(self, kind):
+        if kind is None:
+            return 'vfe' if self.method == 'dtc' else self.method
+        if kind == self.method or (kind == 'vfe' and self.method == 'dtc'):
+            return kind
+        if kind == 'vfe':
+            raise ValueError("kind='vfe' is the DTC value plus a trace term: fit the model with method='dtc'")
+        raise ValueError("kind=%r on a model fitted with method=%r" % (kind, self.method))
+
+    def nlml_gradient(self, kind=None, wrt=('hyper', 'noise', 'Z')):
+        """(value, {'hyper': ..., 'noise': ..., 'Z': ...}): the sparse negative log marginal likelihood at the model's current kernel, noise,
+        Z and data, and its gradient with respect to the LOG of every kernel hyper-parameter, the log noise and every coordinate of every
+        inducing point (ibo_sgp_nlml_grad: one device call that streams the host's X and Y).  kind None: 'vfe' on a 'dtc' model, the
+        model's own objective otherwise; 'vfe' is Titsias' bound."""
+        if self._sdev is None:
+            raise ValueError("model has no data")
+        wrt = tuple(wrt)
+        for w in wrt:
+            if w not in ('hyper', 'noise', 'Z'):
+                raise ValueError("wrt holds %r ('hyper', 'noise', 'Z')" % (w,))
+        return nlml_grad_raw(self.kernel, self.X, self.Y, self.Z, self.noise, self.jitter, self._objective(kind), want=wrt,
+                             device=self._sdev.device)
+
+    def learn(self, kind=None, learn_hyper=True, learn_noise=True, learn_Z=True, maxiter=50, bounds=None):
+        """minimise the sparse marginal likelihood (kind as nlml_gradient's) over [log theta, log noise, vec Z] -- whichever of the three
+        are switched on -- by L-BFGS-B on ibo_sgp_nlml_grad: every evaluation is one device call, a point where a matrix does not factor
+        counts as +inf for the line search.  bounds: L-BFGS-B's, one (lo, hi) per variable in that order, or None.  When the search ends
+        at a finite value below the one it started from -- also when it stopped for lack of iterations -- the kernel is rebuilt as
+        kernel.__class__(exp(log theta)), noise and Z are set and the model is refitted; a failing refit leaves the model as it was.
+        Otherwise (the start does not factor, nothing lower was found) the model is not touched.  Returns the scipy result with
+        .start_value, .end_value and .applied."""
+        if self._sdev is None:
+            raise ValueError("model has no data")
+        from scipy.optimize import minimize
+        kind = self._objective(kind)
+        cls = self.kernel.__class__
+        th0 = np.log(np.asarray(self.kernel.hyperparams, dtype=float))
+        Z0 = np.array(self.Z, dtype=float)
+        nh = len(th0) if learn_hyper else 0
+        x0 = np.r_[th0[:nh], [np.log(float(self.noise))] if learn_noise else [], Z0.ravel() if learn_Z else []]
+        if len(x0) == 0:
+            raise ValueError("nothing to learn")
+        want = tuple(w for w, on in (('hyper', learn_hyper), ('noise', learn_noise), ('Z', learn_Z)) if on)
+        dev = self._sdev.device
+
+        def unpack(x):
+            o = nh
+            kern = cls(np.exp(x[:nh])) if learn_hyper else self.kernel
+            noise = float(self.noise)
+            if learn_noise:
+                noise = float(np.exp(x[o])); o += 1
+            return kern, noise, (x[o:].reshape(Z0.shape) if learn_Z else Z0)
+
+        values = []
+
+        def fg(x):
+            kern, noise, Z = unpack(x)
+            try:
+                v, g = nlml_grad_raw(kern, self.X, self.Y, Z, noise, self.jitter, kind, want=want, device=dev)
+            except _lib.NotPositiveDefinite:
+                return np.inf, np.zeros(len(x))
+            values.append(v)
+            return v, np.r_[g.get('hyper', []), [g['noise']] if learn_noise else [], g['Z'].ravel() if learn_Z else []]
+
+        res = minimize(fg, x0, jac=True, method='L-BFGS-B', bounds=bounds, options=dict(maxiter=int(maxiter)))
+        res.start_value = values[0] if values else float('nan')
+        res.end_value = float(res.fun)
+        # the point found is taken when it is an improvement, whatever stopped the search (L-BFGS-B reports success=False when it runs out
+        # of iterations); a start that does not factor, or a search that found nothing lower, leaves the model alone
+        res.applied = bool(values) and np.isfinite(res.end_value) and res.end_value < res.start_value
+        if not res.applied:
+            return res
+        kern, noise, Z = unpack(np.asarray(res.x, dtype=float))
+        keep = self.kernel, self.noise, self.Z
+        self.kernel, self.noise, self.Z = kern, noise, np.array(Z, dtype=float)
+        try:
+            self._fit(self.X, self.Y)
+        except Exception:
+            self.kernel, self.noise, self.Z = keep
+            raise
+        return res
 
     def _sweep(self, candidates, code, parm, native, ymax, exclude, exclude_radius, index_base, outputs):
         """acquisition.sweep on this model (ibo_sgp_acq_sweep): the model's own signal variance in both modes"""

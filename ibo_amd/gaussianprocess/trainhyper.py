@@ -6,12 +6,15 @@ Marginal likelihood of the GP hyper-parameters (ego/gaussianprocess/trainhyper.p
     nlml_grid(KernelClass, thetas, X, Y, noise=1e-3)      <- new: a whole theta grid in one call
     looLikelihood(kernel, X, Y, nhyper, computeGradient=True, noise=1e-3, predictions=False)      <- new: the leave-one-out objective
     nloo(loghyper, Kernel, X, Y, noise=1e-3)     dnloo(loghyper, Kernel, X, Y, noise=1e-3)
+    sparseLikelihood(kernel, X, Y, Z, nhyper, noise, jitter=1e-6, kind='vfe', computeGradient=True, gradZ=True)      <- new: the sparse
+        model's objective (FITC, DTC or Titsias' bound) with its gradient w.r.t. log theta, log noise and the inducing points
 
 The value (K assembly, Cholesky, L^-1 Y, log det) is computed on the GPU by
 ibo_nlml_grid; value + gradient for one theta by ibo_nlml_grad (K^-1 = W^T W from the device
 factorisation, then one fused kernel contracts K^-1 - alpha alpha^T with every dK/dtheta_i,
 recomputed from X on the fly).  The leave-one-out objective (Rasmussen & Williams 5.4.2), its gradient and the leave-one-out
 predictions come from ibo_loo_grad: the same sequence up to K^-1, then T = K^-1 dK/dtheta_i on the MFMA unit.
+These three factor N x N; the sparse model's likelihood on m inducing points, O(N m^2), comes from ibo_sgp_nlml_grad.
 """
 import numpy as np
 from numpy.linalg import LinAlgError
@@ -200,3 +203,21 @@ def nloo(loghyper, kernel, X, Y, noise=1e-3):
 
 def dnloo(loghyper, kernel, X, Y, noise=1e-3):
     return _loo_value_and_grad(loghyper, kernel, X, Y, noise)[1]
+
+
+# ---------------------------------------------------------------------------------------- the sparse (inducing-point) model
+def sparseLikelihood(kernel, X, Y, Z, nhyper, noise, jitter=1e-6, kind='vfe', computeGradient=True, gradZ=True):
+    """the negative log marginal likelihood of the sparse GP on the inducing points Z (kind 'fitc' or 'dtc'), or Titsias' bound
+    (kind 'vfe'), and with computeGradient its partial derivatives: `value` or `(value, grad_loghyper, grad_lognoise, grad_Z)` -- with
+    respect to the log of the kernel's first nhyper hyper-parameters, the log noise and (gradZ, else None) every coordinate of every
+    inducing point.  One device call (ibo_sgp_nlml_grad).  LinAlgError when K~uu or A is not positive definite."""
+    from .sparse import nlml_grad_raw
+    assert len(X) == len(Y)
+    want = () if not computeGradient else (('hyper', 'noise', 'Z') if gradZ else ('hyper', 'noise'))
+    try:
+        v, g = nlml_grad_raw(kernel, X, Y, Z, noise, jitter, kind, ngrad=nhyper, want=want)
+    except _lib.NotPositiveDefinite:
+        raise LinAlgError("the sparse model's matrices are not positive definite for hyperparameters %s" % (kernel.hyperparams,))
+    if not computeGradient:
+        return v
+    return v, g['hyper'], g['noise'], g.get('Z')

@@ -65,7 +65,9 @@ extern "C" {
                              * samples is fitted to) and the options "mes_chunk", "mes_timing": added within 8, nothing else changed;
                              * + ibo_sgp_create, ibo_sgp_destroy, ibo_sgp_fit, ibo_sgp_add, ibo_sgp_acq_batch, ibo_sgp_acq_sweep, ibo_sgp_direct_max,
                              * ibo_sgp_nlml, ibo_sgp_get, ibo_sgp_stage_ms (a sparse GP on inducing points, DTC / FITC, on a handle type of its own) and the
-                             * options "sgp_chunk", "sgp_timing": added within 8, nothing else changed */
+                             * options "sgp_chunk", "sgp_timing": added within 8, nothing else changed;
+                             * + ibo_sgp_nlml_grad, ibo_sgp_grad_stage_ms (the sparse marginal likelihood's gradient with respect to the log
+                             * hyper-parameters, the log noise and the inducing points, for fitc / dtc / vfe): added within 8, nothing else changed */
 
 /* status codes */
 #define IBO_OK              0
@@ -1037,6 +1039,41 @@ int ibo_sgp_get(ibo_sgp_t *h, int what, double *out_host);
  * Gram product, [3] the assembly of A, [4] factor-and-invert with the alpha vectors, [5] the candidates' two sweeps, [6] the finish kernel. */
 #define IBO_SGP_STAGES 8
 int ibo_sgp_stage_ms(double *ms, int reset);
+/*
+ * The sparse negative log marginal likelihood and its gradient for ONE theta / noise / Z, stateless like ibo_nlml_grad: a fit (ibo_sgp_fit on a
+ * private per-device handle that ibo_trim gives back) and one more pass over the data, O(N m^2) on the fp64 MFMA unit.
+ *   kind   IBO_SGP_FITC / IBO_SGP_DTC: the model's own objective (IBO_SGP_NLML_MODEL of that fit);  IBO_SGP_VFE: Titsias' bound
+ *          (IBO_SGP_NLML_VFE of a DTC fit).  *value is ibo_sgp_nlml's value for the same arguments, bit for bit.
+ *   per observation  mu_i = alpha.k_i, a_i = k_i^T A^-1 k_i, c_i = [1 / lambda_i - ((y_i - mu_i)^2 + a_i) / lambda_i^2] / 2 = dNL/dlambda_i,
+ *          e_i = c_i [1 - q_i > 0] (fitc), 0 (dtc), [1 - q_i > 0] / (2 noise) (vfe): the clamp max(1 - q, 0) is differentiated as that indicator,
+ *          taken from the device's own q_i
+ *   dNL/dK, column i   g_i = (A^-1 k_i + alpha (mu_i - y_i)) / lambda_i - 2 e_i K~uu^-1 k_i          (never stored)
+ *   dNL/dK~uu          S = (A^-1 + alpha alpha^T - K~uu^-1) / 2 + K~uu^-1 (K E K^T) K~uu^-1, off the diagonal (the diagonal is the constant 1 + jitter)
+ *   with z = sum_d w_d Delta_d^2, rho = dk/dz:
+ *   grad_Z[a][d]       2 w_d [sum_i g_ai rho_ai (Z_ad - X_id) + 2 sum_{b != a} S_ab rho_ab (Z_ad - Z_bd)]
+ *   grad_hyper[h]      modes / dims as ibo_nlml_grad's: mode 0 (the length scale of dimension dims[h]) -2 w_d [sum_ai g rho Delta_d^2 + sum_{a != b} S rho Delta_d^2];
+ *                      modes 1, 3, 4 (one length scale for every dimension) the sum of that over d, with the rho of the kernel's own family;
+ *                      mode 2 (the signal magnitude) 2 [sum g_ai k_ai + sum_{a != b} S_ab K~uu,ab].  All with respect to the LOG of the parameter.
+ *   grad_lognoise      noise (sum_i c_i - [vfe] tt / (2 noise^2))
+ * The data stream in the fit's chunks ("sgp_chunk"); per chunk the two frames' plain sweeps (q_i, mu_i, a_i), a per-observation kernel, the
+ * generation of the operands and one fused kernel: 64 x 64 tiles of g from [A^-1 | K~uu^-1] against [k_i / lambda_i | -2 e_i k_i] with the
+ * derivative epilogue applied in LDS; the signed Gram matrix K E K^T is accumulated beside it (not for dtc).  No atomics: two calls with the
+ * same arguments give the same bits; another chunking may differ within rounding.  A component's bits do not depend on which other outputs
+ * are asked for, nor on where it stands in modes / dims.
+ * 0 <= ngrad <= 65 (modes / dims may be NULL when 0); grad_hyper (ngrad), grad_lognoise (1), grad_Z (m x D row-major) are optional (NULL).
+ * Limits and errors: ibo_sgp_fit's, IBO_ERR_ARG also for an unknown kind or derivative spec.  Every error, IBO_ERR_NOT_PD (pivot in *info)
+ * among them, leaves all outputs untouched.
+ */
+#define IBO_SGP_VFE  2               /* a kind of ibo_sgp_nlml_grad only: ibo_sgp_fit does not take it */
+int ibo_sgp_nlml_grad(int device, int ktype, int D, const double *hyper_host, int nhyper, double sf2, double noise, double jitter, int kind,
+                      int m, const double *Z_host, int64_t N, const double *X_host, const double *Y_host,
+                      int ngrad, const int *modes, const int *dims,
+                      double *value, double *grad_hyper, double *grad_lognoise, double *grad_Z, int *info);
+/* under ibo_set_option("sgp_timing", 1), accumulated per thread: [0] the fit, [1] the two inverses, [2] the observations' two sweeps, [3] the
+ * per-observation kernel and the generation of the operands, [4] the fused contraction, [5] the signed Gram product, [6] S and the K~uu
+ * contraction, [7] the sums over the strips. */
+#define IBO_SGP_GRAD_STAGES 8
+int ibo_sgp_grad_stage_ms(double *ms, int reset);
 
 /* DIRECT minimisation of a HOST callback with the reference's semantics
  * (cpp/direct.cpp:329; what ego.utils.optimize.cdirect wraps), plus the sample
