@@ -207,14 +207,14 @@ def cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc=None, xi=-1, b
 gpuDirectGP = cdirectGP          # the name earlier rounds of this package used
 
 
-POLISH_MAXITER = 30
+from ._args import POLISH_MAXITER                                                 # noqa: E402,F401  (the polish step itself: _args._polish_step)
 
 
 def _polish(model, bounds, acqfunc, parm, opt, optx):
     """finish DIRECT's point with L-BFGS-B on the objective DIRECT maximised (libego's k* variance, libm erf, clamp
     [1e-8, 10], the same parm; one ibo_acq_grad_batch call per evaluation), bounded to the box and at most POLISH_MAXITER
     iterations.  The end point is re-evaluated with ibo_acq_batch and returned only if it is strictly better than DIRECT's."""
-    from scipy.optimize import minimize
+    from . import _args
     model._no_gradient("polish=True")
     lb = _lib.f64([b[0] for b in bounds]); ub = _lib.f64([b[1] for b in bounds])
     D = len(lb)
@@ -225,24 +225,21 @@ def _polish(model, bounds, acqfunc, parm, opt, optx):
     v, g = np.empty(1), np.empty((1, D))
 
     def fg(x):
-        q = _lib.f64(np.clip(x, lb, ub).reshape(1, D))
+        q = _lib.f64(x.reshape(1, D))
         _lib.check(_lib.lib.ibo_acq_grad_batch(h, 1, _lib.dp(q), code, float(parm), _lib.ERF_LIBM, _lib.CLAMP_NATIVE,
                                                float('nan'), None, None, _lib.dp(v), None, None, _lib.dp(g)))
         return -v[0], -g[0].copy()
 
+    def value_at(x):
+        _lib.check(_lib.lib.ibo_acq_batch(h, 1, _lib.dp(x), code, float(parm), _lib.ERF_LIBM, _lib.CLAMP_NATIVE,
+                                          float('nan'), None, None, _lib.dp(v)))
+        return v[0]
+
     _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(h, sf2_native))
     try:
-        res = minimize(fg, np.clip(optx, lb, ub), jac=True, method='L-BFGS-B', bounds=list(zip(lb, ub)),
-                       options=dict(maxiter=POLISH_MAXITER, ftol=1e-15, gtol=1e-12))
-        x = _lib.f64(np.clip(res.x, lb, ub))
-        val = np.empty(1)
-        _lib.check(_lib.lib.ibo_acq_batch(h, 1, _lib.dp(x), code, float(parm), _lib.ERF_LIBM, _lib.CLAMP_NATIVE,
-                                          float('nan'), None, None, _lib.dp(val)))
+        return _args._polish_step(fg, value_at, lb, ub, opt, optx)
     finally:
         _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(h, sf2_py))
-    if val[0] > opt:
-        return float(val[0]), x
-    return opt, optx
 
 
 def maximizeUCB(model, bounds, delta=0.1, scale=0.2, useCDIRECT=True, maxiter=50, maxtime=30, maxsample=10000,

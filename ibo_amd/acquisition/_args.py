@@ -1,4 +1,5 @@
-"""What knowledge.py and batch.py check alike about their arguments: points, candidate arrays, bounds."""
+"""What the acquisition modules share: the checks of their arguments (points, candidate arrays, bounds), the methods of a host-point
+acquisition class, and the polish step of the maximisers."""
 import numpy as np
 
 from .. import _lib
@@ -43,3 +44,44 @@ def _bounds(bounds, D_model):
     if len(lb) != D_model:
         raise ValueError("bounds have %d dimensions, the model has %d" % (len(lb), D_model))
     return lb, ub, len(lb)
+
+
+POLISH_MAXITER = 30
+
+
+class _HostPointAcquisition(object):
+    """What MaxValueEntropy, ExpectedHypervolumeImprovement and the constrained classes offer alike, over the subclass's
+    _call(X, grad) -> values (M,), or with grad (values, gradients (M, D)) from its *_grad_batch entry"""
+
+    def values(self, X):
+        """the value at many points at once"""
+        return self._call(X, False)
+
+    def f(self, x):
+        return self._call(x, False)[0]
+
+    def negf(self, x):
+        return -self.f(x)
+
+    def gradient(self, X):
+        """(values, gradients (M, D)) at the points X, the conventions of negf"""
+        return self._call(X, True)
+
+    def negf_grad(self, x):
+        """(negf(x), -grad f(x)): the objective and gradient scipy.optimize.minimize(jac=True) asks for"""
+        v, g = self.gradient(x)
+        return -v[0], -g[0]
+
+
+def _polish_step(fg, value_at, lb, ub, opt, optx):
+    """The polish step of every maximiser: bounded L-BFGS-B from DIRECT's point optx on fg(x) -> (-value, -gradient), x clipped to the
+    box [lb, ub] first, at most POLISH_MAXITER iterations; the end point is re-evaluated with value_at(x) and kept only when strictly
+    better than opt.  Returns (opt, optx)."""
+    from scipy.optimize import minimize
+    res = minimize(lambda x: fg(np.clip(x, lb, ub)), np.clip(optx, lb, ub), jac=True, method='L-BFGS-B', bounds=list(zip(lb, ub)),
+                   options=dict(maxiter=POLISH_MAXITER, ftol=1e-15, gtol=1e-12))
+    x = _lib.f64(np.clip(res.x, lb, ub))
+    val = value_at(x)
+    if val > opt:
+        return float(val), x
+    return opt, optx

@@ -29,7 +29,7 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from . import POLISH_MAXITER, _args
+from . import _args
 
 _CACQ = {'ei': _lib.ACQ_EI, 'pi': _lib.ACQ_PI, 'pof': _lib.ACQ_NONE}
 MAX_CONSTRAINTS = 8          # IBO_CACQ_MAX_CON
@@ -161,7 +161,7 @@ def sweepConstrained(model, constraints, candidates, acq='ei', xi=0.01, native=T
     return res
 
 
-class _Constrained(object):
+class _Constrained(_args._HostPointAcquisition):
     """the host-point classes: Python-class semantics (NR erf, clamp [1e-7, 10], the kernels' own k* variance), like EI / PI"""
     _acq = 'ei'
 
@@ -186,25 +186,6 @@ class _Constrained(object):
         g = np.empty((M, D))
         _lib.check(_lib.lib.ibo_cacq_grad_batch(*(lead + (_lib.dp(val), _lib.dp(g)))))
         return val, g
-
-    def values(self, X):
-        """the value at many points at once"""
-        return self._call(X, False)
-
-    def f(self, x):
-        return self._call(x, False)[0]
-
-    def negf(self, x):
-        return -self.f(x)
-
-    def gradient(self, X):
-        """(values, gradients (M, D)) at the points X, the conventions of negf (ibo_cacq_grad_batch)"""
-        return self._call(X, True)
-
-    def negf_grad(self, x):
-        """(negf(x), -grad f(x)): the objective and gradient scipy.optimize.minimize(jac=True) asks for"""
-        v, g = self.gradient(x)
-        return -v[0], -g[0]
 
 
 class ConstrainedEI(_Constrained):
@@ -245,23 +226,18 @@ def _maximize(model, constraints, bounds, acq, xi, maxiter, maxtime, maxsample, 
             int(maxiter), int(maxtime), int(maxsample), 1 if compat else 0, ctypes.byref(opt), _lib.dp(optx), ctypes.byref(ns)))))
         best, bestx = opt.value, optx
         if polish:
-            # _polish's rule on ibo_cacq_grad_batch: bounded L-BFGS-B from DIRECT's point on the objective DIRECT maximised,
-            # at most POLISH_MAXITER iterations, the end point re-evaluated and kept only when strictly better
-            from scipy.optimize import minimize
-            v, g = np.empty(1), np.empty((1, D))
+            v, g = np.empty(1), np.empty((1, D))           # the polish step on the objective DIRECT maximised
 
             def fg(x):
-                q = _lib.f64(np.clip(x, lb, ub).reshape(1, D))
+                q = _lib.f64(x.reshape(1, D))
                 _lib.check(_lib.lib.ibo_cacq_grad_batch(*(lead + (1, _lib.dp(q)) + tail + (_lib.dp(v), _lib.dp(g)))))
                 return -v[0], -g[0].copy()
 
-            res = minimize(fg, np.clip(optx, lb, ub), jac=True, method='L-BFGS-B', bounds=list(zip(lb, ub)),
-                           options=dict(maxiter=POLISH_MAXITER, ftol=1e-15, gtol=1e-12))
-            x = _lib.f64(np.clip(res.x, lb, ub))
-            val = np.empty(1)
-            _lib.check(_lib.lib.ibo_cacq_batch(*(lead + (1, _lib.dp(x)) + tail + (None, None, _lib.dp(val)))))
-            if val[0] > best:
-                best, bestx = float(val[0]), x
+            def value_at(x):
+                _lib.check(_lib.lib.ibo_cacq_batch(*(lead + (1, _lib.dp(x)) + tail + (None, None, _lib.dp(v)))))
+                return v[0]
+
+            best, bestx = _args._polish_step(fg, value_at, lb, ub, best, bestx)
     return best, bestx
 
 

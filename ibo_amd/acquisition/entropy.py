@@ -35,7 +35,7 @@ import numpy as np
 
 from .. import _lib
 from ..utils.latinhypercube import lhcSample
-from . import POLISH_MAXITER, _args
+from . import _args
 from .pathwise import MAXIMA_CANDIDATES, PosteriorPaths
 
 MAX_SAMPLES = 1024           # IBO_MES_MAX_SAMPLES
@@ -126,7 +126,7 @@ def maxValueSamples(GP, bounds=None, candidates=None, n=64, method='gumbel', see
     return _lib.f64(np.maximum(a - b * np.log(-np.log(u)), lo))
 
 
-class MaxValueEntropy(object):
+class MaxValueEntropy(_args._HostPointAcquisition):
     """MES(x) against the samples `ystar` of the maximum (1 .. 1024 finite numbers, any order); latent: the information in the latent
     function (the default) or in a noisy observation"""
 
@@ -148,25 +148,6 @@ class MaxValueEntropy(object):
         g = np.empty((M, D))
         _lib.check(_lib.lib.ibo_mes_grad_batch(*(lead + (_lib.dp(val), _lib.dp(g)))))
         return val, g
-
-    def values(self, X):
-        """the value at many points at once"""
-        return self._call(X, False)
-
-    def f(self, x):
-        return self._call(x, False)[0]
-
-    def negf(self, x):
-        return -self.f(x)
-
-    def gradient(self, X):
-        """(values, gradients (M, D)) at the points X (ibo_mes_grad_batch)"""
-        return self._call(X, True)
-
-    def negf_grad(self, x):
-        """(negf(x), -grad f(x)): the objective and gradient scipy.optimize.minimize(jac=True) asks for"""
-        v, g = self.gradient(x)
-        return -v[0], -g[0]
 
 
 def sweepMES(GP, candidates, ystar, exclude=None, radius=0, index_base=0, outputs=False, latent=True):
@@ -209,11 +190,4 @@ def maximizeMES(GP, bounds, ystar=None, n_samples=64, method='gumbel', seed=None
                                            ctypes.byref(opt), _lib.dp(optx), ctypes.byref(ns)))
     if not polish:
         return opt.value, optx
-    from scipy.optimize import minimize
-    res = minimize(lambda x: acq.negf_grad(np.clip(x, lb, ub)), np.clip(optx, lb, ub), jac=True, method='L-BFGS-B',
-                   bounds=list(zip(lb, ub)), options=dict(maxiter=POLISH_MAXITER, ftol=1e-15, gtol=1e-12))
-    x = _lib.f64(np.clip(res.x, lb, ub))
-    val = acq.f(x)
-    if val > opt.value:
-        return float(val), x
-    return opt.value, optx
+    return _args._polish_step(acq.negf_grad, acq.f, lb, ub, opt.value, optx)

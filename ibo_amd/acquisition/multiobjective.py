@@ -28,7 +28,7 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from . import POLISH_MAXITER, _args
+from . import _args
 from .constrained import _kstar_native
 
 MAX_FRONT = 1024             # IBO_EHVI_MAX_FRONT
@@ -130,7 +130,7 @@ def sweepEHVI(models, candidates, ref, front=None, native=True, exclude=None, ex
     return res
 
 
-class ExpectedHypervolumeImprovement(object):
+class ExpectedHypervolumeImprovement(_args._HostPointAcquisition):
     """the host-point class: Python-class semantics (NR erf, clamp [1e-7, 10], the kernels' own k* variance), like EI / PI and
     the constrained classes.  front=None: observedFront(models), taken once, here."""
 
@@ -152,25 +152,6 @@ class ExpectedHypervolumeImprovement(object):
         _lib.check(_lib.lib.ibo_ehvi_grad_batch(*(lead + (_lib.dp(val), _lib.dp(g)))))
         return val, g
 
-    def values(self, X):
-        """the value at many points at once"""
-        return self._call(X, False)
-
-    def f(self, x):
-        return self._call(x, False)[0]
-
-    def negf(self, x):
-        return -self.f(x)
-
-    def gradient(self, X):
-        """(values, gradients (M, D)) at the points X, the conventions of negf (ibo_ehvi_grad_batch)"""
-        return self._call(X, True)
-
-    def negf_grad(self, x):
-        """(negf(x), -grad f(x)): the objective and gradient scipy.optimize.minimize(jac=True) asks for"""
-        v, g = self.gradient(x)
-        return -v[0], -g[0]
-
 
 def maximizeEHVI(models, bounds, ref, front=None, maxiter=50, maxtime=30, maxsample=10000, polish=False, compat=True):
     """Maximise EHVI over the box `bounds` with DIRECT on the GPU objective (ibo_ehvi_direct_max; libego semantics as maximizeEI:
@@ -188,21 +169,16 @@ def maximizeEHVI(models, bounds, ref, front=None, maxiter=50, maxtime=30, maxsam
             int(maxiter), int(maxtime), int(maxsample), 1 if compat else 0, ctypes.byref(opt), _lib.dp(optx), ctypes.byref(ns)))))
         best, bestx = opt.value, optx
         if polish:
-            # _polish's rule on ibo_ehvi_grad_batch: bounded L-BFGS-B from DIRECT's point on the objective DIRECT maximised,
-            # at most POLISH_MAXITER iterations, the end point re-evaluated and kept only when strictly better
-            from scipy.optimize import minimize
-            v, g = np.empty(1), np.empty((1, D))
+            v, g = np.empty(1), np.empty((1, D))           # the polish step on the objective DIRECT maximised
 
             def fg(x):
-                q = _lib.f64(np.clip(x, lb, ub).reshape(1, D))
+                q = _lib.f64(x.reshape(1, D))
                 _lib.check(_lib.lib.ibo_ehvi_grad_batch(*(lead + (1, _lib.dp(q)) + tail + (_lib.dp(v), _lib.dp(g)))))
                 return -v[0], -g[0].copy()
 
-            res = minimize(fg, np.clip(optx, lb, ub), jac=True, method='L-BFGS-B', bounds=list(zip(lb, ub)),
-                           options=dict(maxiter=POLISH_MAXITER, ftol=1e-15, gtol=1e-12))
-            x = _lib.f64(np.clip(res.x, lb, ub))
-            val = np.empty(1)
-            _lib.check(_lib.lib.ibo_ehvi_batch(*(lead + (1, _lib.dp(x)) + tail + (_lib.dp(val),))))
-            if val[0] > best:
-                best, bestx = float(val[0]), x
+            def value_at(x):
+                _lib.check(_lib.lib.ibo_ehvi_batch(*(lead + (1, _lib.dp(x)) + tail + (_lib.dp(v),))))
+                return v[0]
+
+            best, bestx = _args._polish_step(fg, value_at, lb, ub, best, bestx)
     return best, bestx

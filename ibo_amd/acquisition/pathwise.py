@@ -177,15 +177,7 @@ class PosteriorPaths(object):
                                                  int(maxsample), 1 if compat else 0, ctypes.byref(opt), _lib.dp(optx), ctypes.byref(ns)))
         if not polish:
             return opt.value, optx
-        from scipy.optimize import minimize
-        from . import POLISH_MAXITER
-        res = minimize(lambda x: self.negf_grad(np.clip(x, lb, ub), path), np.clip(optx, lb, ub), jac=True, method='L-BFGS-B',
-                       bounds=list(zip(lb, ub)), options=dict(maxiter=POLISH_MAXITER, ftol=1e-15, gtol=1e-12))
-        x = _lib.f64(np.clip(res.x, lb, ub))
-        val = self.values(x)[int(path), 0]
-        if val > opt.value:
-            return float(val), x
-        return opt.value, optx
+        return _args._polish_step(lambda x: self.negf_grad(x, path), lambda x: self.values(x)[int(path), 0], lb, ub, opt.value, optx)
 
     def _ascend(self, X0, bounds):
         """Every path s ascended from its own start X0[s] inside the box, all S in lock-step: projected gradient steps with a

@@ -1,6 +1,6 @@
 // abi_cacq.hip -- the constrained acquisition behind the C ABI: A(x) prod_j Phi(z_j) over several handles -- ibo_cacq_sweep, ibo_cacq_batch,
-// ibo_cacq_grad_batch, ibo_cacq_direct_max (kernel: cacq.hip; the per-model work: run_sweep and eval_host_points).
-#include "abi_eval.h"
+// ibo_cacq_grad_batch, ibo_cacq_direct_max (kernel: cacq.hip; the sweep's chunks: abi_moments.h; the host batches' per-model work: eval_host_points).
+#include "abi_moments.h"
 #include "cacq.h"
 
 std::atomic<int> g_cacq_chunk{0};     // ibo_set_option("cacq_chunk", m): candidates per chunk of ibo_cacq_sweep (rounded up to 256); 0: by bytes
@@ -48,53 +48,31 @@ static int cacq_begin(const CacqCall &c, int64_t M, const void *points, bool any
     return IBO_OK;
 }
 
-// One plain sweep per model -- (mu, s2) into device scratch, no arg-max, no read-back -- one after the other (a handle may appear more
-// than once), then cacq_finish_kernel on the objective's stream.  Scratch: 16 (ncon + 1) bytes per candidate from the pool, at most
-// about 1 GiB (more candidates go in chunks), handed back before the call returns.
+// One plain sweep per model, one after the other (a handle may appear more than once; the pure probability of feasibility does not look at
+// the objective), then cacq_finish_kernel on the objective's stream.  Scratch: 16 (ncon + 1) bytes per candidate from the pool, at most
+// about 1 GiB (more candidates go in chunks), handed back before the call returns.  No launch is padded: see MomentsPipeline::padded.
 extern "C" int ibo_cacq_sweep(ibo_gp_t *obj, int ncon, ibo_gp_t *const *con, const double *thresh, const int *sense,
                               int64_t M, const double *cand_dev, int acq, double parm, int erf_mode, double clamp_lo, double ymax,
                               int n_excl, const double *excl_host, double excl_radius, int64_t index_base,
                               double *acq_dev, double *pof_dev, double *val_dev, double *best_val, int64_t *best_idx)
 {
     const CacqCall c = {obj, ncon, con, thresh, sense, acq, parm, erf_mode, clamp_lo, ymax};
-    CacqArgs a;
-    memset(&a, 0, sizeof(a));
-    IBO_TRY(cacq_begin(c, M, cand_dev, acq_dev || pof_dev || val_dev || best_val || best_idx, &a.spec));
-    ibo_gp *g = obj;
-    hipStream_t s = g->stream;
-    const int D = g->D;
-    a.D = D; a.index_base = index_base; a.excl_radius = excl_radius;
-    IBO_TRY(upload_exclusions(g, n_excl, excl_host, &a.n_excl, &a.excl));
-    int64_t mc = (((int64_t)1 << 30) / (16 * (ncon + 1))) / 256 * 256;        // candidates per chunk: a multiple of the combine's workgroup
-    if (g_cacq_chunk > 0) mc = ((int64_t)g_cacq_chunk + 255) / 256 * 256;
-    if (M <= mc) mc = M;
-    const int64_t nblk = (M + 255) / 256;
-    ScopedBuf<double> ms, pv;
-    ScopedBuf<int64_t> pi;
-    IBO_TRY(ms.ensure(2 * (size_t)(ncon + 1) * mc)); IBO_TRY(pv.ensure((size_t)nblk)); IBO_TRY(pi.ensure((size_t)nblk));
-    a.ms = ms.p; a.stride = mc;
-    for (int64_t c0 = 0; c0 < M; c0 += mc) {
-        const int64_t m = M - c0 < mc ? M - c0 : mc;
-        SweepRequest r;
-        r.M = m; r.cand_dev = cand_dev + c0 * D; r.acq = IBO_ACQ_NONE; r.erf_mode = erf_mode; r.clamp_lo = clamp_lo;
-        if (acq != IBO_ACQ_NONE) {                   // (the pure probability of feasibility does not look at the objective)
-            r.mu_dev = ms.p; r.s2_dev = ms.p + mc;
-            IBO_TRY(run_sweep(g, r));
-        }
-        for (int j = 0; j < ncon; j++) {
-            r.mu_dev = ms.p + 2 * (size_t)(1 + j) * mc; r.s2_dev = r.mu_dev + mc;
-            IBO_TRY(run_sweep(con[j], r));
-            if (con[j]->stream != s) HIP_TRY(hipStreamSynchronize(con[j]->stream));     // the combine runs on the objective's stream
-        }
-        a.M = m; a.first = c0; a.cand = r.cand_dev;
-        a.out_acq = acq_dev ? acq_dev + c0 : nullptr; a.out_pof = pof_dev ? pof_dev + c0 : nullptr; a.out_val = val_dev ? val_dev + c0 : nullptr;
-        a.part_val = pv.p + c0 / 256; a.part_idx = pi.p + c0 / 256;
+    CacqSpec spec;
+    IBO_TRY(cacq_begin(c, M, cand_dev, acq_dev || pof_dev || val_dev || best_val || best_idx, &spec));
+    MomentsPipeline p;
+    p.add(obj, true, true, clamp_lo, erf_mode, acq != IBO_ACQ_NONE);
+    for (int j = 0; j < ncon; j++) p.add(con[j], true, true, clamp_lo, erf_mode);
+    p.home = obj; p.padded = false; p.chunk_opt = g_cacq_chunk;
+    p.out[0] = acq_dev; p.out[1] = pof_dev; p.out[2] = val_dev;
+    p.finish = [&](const MomentChunk &k, hipStream_t s) -> int {
+        CacqArgs a;
+        memset(&a, 0, sizeof(a));
+        a.spec = spec; a.t = k.tail; a.ms = k.ms; a.stride = k.stride;
+        a.out_acq = k.at(p.out[0]); a.out_pof = k.at(p.out[1]); a.out_val = k.at(p.out[2]);
         KERNEL_TRY(launch_cacq_finish(a, s));
-        if (c0 + mc < M) HIP_TRY(hipStreamSynchronize(s));      // the next chunk's sweeps, on other streams, write the same scratch
-    }
-    if (best_val || best_idx) return argmax_readback(g, pv.p, pi.p, nblk, best_val, best_idx);
-    HIP_TRY(hipStreamSynchronize(s));
-    return IBO_OK;
+        return IBO_OK;
+    };
+    return p.sweep(M, cand_dev, M, n_excl, excl_host, excl_radius, index_base, best_val, best_idx);
 }
 
 // Host batches (and with them every DIRECT batch): the ncon + 1 eval_host_points calls one after the other -- the objective's acquisition

@@ -1,6 +1,6 @@
 // abi_ehvi.hip -- the two-objective expected hypervolume improvement behind the C ABI: ibo_ehvi_sweep, ibo_ehvi_batch, ibo_ehvi_grad_batch,
-// ibo_ehvi_direct_max (kernel: ehvi.hip; the per-model work: run_sweep; the front's canonical form: ehvi_front.h).
-#include "abi_eval.h"
+// ibo_ehvi_direct_max (kernel: ehvi.hip; the chunks and the per-model work: abi_moments.h; the front's canonical form: ehvi_front.h).
+#include "abi_moments.h"
 #include "ehvi.h"
 #include "ehvi_front.h"
 
@@ -51,72 +51,25 @@ static int ehvi_begin(ibo_gp_t *const *obj, int nfront, const double *front_host
     return IBO_OK;
 }
 
-// What a call may ask of the device pass beside the arg-max: the values, and the gradient's sums (six arrays M apart)
-struct EhviOut { double *val_dev = nullptr, *sums_dev = nullptr; double *best_val = nullptr; int64_t *best_idx = nullptr; };
+// What a call may ask of the device pass beside the arg-max (MomentsPipeline::out): the values, and the gradient's sums (six arrays M apart)
+enum { EHVI_OUT_VAL = 0, EHVI_OUT_SUMS };
 
-// The one route of every entry: per chunk the two plain sweeps -- (mu, s2) into pooled scratch, 32 bytes per candidate, no arg-max, no
-// read-back, one after the other (the same handle may be both) -- then ehvi_finish_kernel on the first model's stream.
-// cand_rows: the rows cand_dev has room for (>= M; rows from M on are the caller's padding, see class_padded).
-static int ehvi_device(const EhviCall &c, int64_t M, const double *cand_dev, int64_t cand_rows, int n_excl, const double *excl_host,
-                       double excl_radius, int64_t index_base, const EhviOut &o)
+// The one route of every entry: per chunk the two plain sweeps, 32 bytes of scratch per candidate (the same handle may be both), then
+// ehvi_finish_kernel on the first model's stream.
+static void ehvi_pipeline(const EhviCall &c, int64_t M, MomentsPipeline *p)
 {
-    ibo_gp *g = c.g1;
-    hipStream_t s = g->stream;
-    const int D = g->D;
-    EhviArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n = c.n; a.erf_mode = c.erf_mode; a.r1 = c.r1; a.r2 = c.r2;
-    a.D = D; a.index_base = index_base; a.excl_radius = excl_radius;
-    IBO_TRY(upload_exclusions(g, n_excl, excl_host, &a.n_excl, &a.excl));
-    int64_t mc = (((int64_t)1 << 30) / 32) / 256 * 256;        // candidates per chunk: a multiple of the combine's workgroup
-    if (g_ehvi_chunk > 0) mc = ((int64_t)g_ehvi_chunk + 255) / 256 * 256;
-    if (M <= mc) mc = M;
-    const int64_t nblk = (M + 255) / 256;
-    const int64_t stride = class_padded(mc, mc);               // (every launch of the call fits: a tail is padded to at most mc's own size class)
-    ScopedBuf<double> ms, pv, pad;
-    ScopedBuf<int64_t> pi;
-    IBO_TRY(ms.ensure(4 * (size_t)stride));
-    IBO_TRY(pv.ensure((size_t)nblk)); IBO_TRY(pi.ensure((size_t)nblk));
-    a.front = c.front_dev.p;
-    const bool timing = g_ehvi_timing != 0;
-    struct Events {                                             // (the diagnostic's: made and destroyed per call)
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } ev;
-    if (timing) { HIP_TRY(hipEventCreate(&ev.e0)); HIP_TRY(hipEventCreate(&ev.e1)); }
-    a.ms = ms.p; a.stride = stride; a.sums_stride = M;
-    for (int64_t c0 = 0; c0 < M; c0 += mc) {
-        const int64_t m = M - c0 < mc ? M - c0 : mc, mp = class_padded(m, mc);
-        SweepRequest r;
-        r.M = mp; r.cand_dev = cand_dev + c0 * D; r.acq = IBO_ACQ_NONE; r.erf_mode = c.erf_mode; r.clamp_lo = c.clamp_lo;
-        if (c0 + mp > cand_rows) {                              // a short launch of the caller's array: its candidates, then the padding
-            IBO_TRY(pad.ensure((size_t)mp * D));
-            HIP_TRY(hipMemcpyAsync(pad.p, r.cand_dev, sizeof(double) * (size_t)m * D, hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipMemsetAsync(pad.p + (size_t)m * D, 0, sizeof(double) * (size_t)(mp - m) * D, s));
-            HIP_TRY(hipStreamSynchronize(s));                   // (the second model's sweep reads them on its own stream)
-            r.cand_dev = pad.p;
-        }
-        r.mu_dev = ms.p; r.s2_dev = ms.p + stride;
-        IBO_TRY(run_sweep(c.g1, r));
-        r.mu_dev = ms.p + 2 * (size_t)stride; r.s2_dev = ms.p + 3 * (size_t)stride;
-        IBO_TRY(run_sweep(c.g2, r));
-        if (c.g2->stream != s) HIP_TRY(hipStreamSynchronize(c.g2->stream));     // the combine runs on the first model's stream
-        a.M = m; a.first = c0; a.cand = r.cand_dev;
-        a.out_val = o.val_dev ? o.val_dev + c0 : nullptr;
-        a.out_sums = o.sums_dev ? o.sums_dev + c0 : nullptr;
-        a.part_val = pv.p + c0 / 256; a.part_idx = pi.p + c0 / 256;
-        if (timing) HIP_TRY(hipEventRecord(ev.e0, s));
-        KERNEL_TRY(launch_ehvi_finish(a, o.sums_dev != nullptr, s));
-        if (timing) {
-            float ms1 = 0.f;
-            HIP_TRY(hipEventRecord(ev.e1, s)); HIP_TRY(hipEventSynchronize(ev.e1)); HIP_TRY(hipEventElapsedTime(&ms1, ev.e0, ev.e1));
-            t_ehvi_ms += ms1;
-        }
-        if (c0 + mc < M) HIP_TRY(hipStreamSynchronize(s));      // the next chunk's sweeps, on another stream, write the same scratch
-    }
-    if (o.best_val || o.best_idx) return argmax_readback(g, pv.p, pi.p, nblk, o.best_val, o.best_idx);
-    HIP_TRY(hipStreamSynchronize(s));
-    return IBO_OK;
+    p->add(c.g1, true, true, c.clamp_lo, c.erf_mode);
+    p->add(c.g2, true, true, c.clamp_lo, c.erf_mode);
+    p->home = c.g1; p->chunk_opt = g_ehvi_chunk; p->timing = g_ehvi_timing != 0; p->finish_ms = &t_ehvi_ms;
+    p->finish = [&c, p, M](const MomentChunk &k, hipStream_t s) -> int {
+        EhviArgs a;
+        memset(&a, 0, sizeof(a));
+        a.n = c.n; a.erf_mode = c.erf_mode; a.r1 = c.r1; a.r2 = c.r2; a.front = c.front_dev.p;
+        a.t = k.tail; a.ms = k.ms; a.stride = k.stride; a.sums_stride = M;
+        a.out_val = k.at(p->out[EHVI_OUT_VAL]); a.out_sums = k.at(p->out[EHVI_OUT_SUMS]);
+        KERNEL_TRY(launch_ehvi_finish(a, a.out_sums != nullptr, s));
+        return IBO_OK;
+    };
 }
 
 extern "C" int ibo_ehvi_sweep(ibo_gp_t *const *obj, int nfront, const double *front_host, const double *ref,
@@ -126,30 +79,21 @@ extern "C" int ibo_ehvi_sweep(ibo_gp_t *const *obj, int nfront, const double *fr
 {
     EhviCall c;
     IBO_TRY(ehvi_begin(obj, nfront, front_host, ref, M, cand_dev, erf_mode, clamp_lo, val_dev || best_val || best_idx, &c));
-    EhviOut o;
-    o.val_dev = val_dev; o.best_val = best_val; o.best_idx = best_idx;
-    return ehvi_device(c, M, cand_dev, M, n_excl, excl_host, excl_radius, index_base, o);
+    MomentsPipeline p;
+    ehvi_pipeline(c, M, &p);
+    p.out[EHVI_OUT_VAL] = val_dev;
+    return p.sweep(M, cand_dev, M, n_excl, excl_host, excl_radius, index_base, best_val, best_idx);
 }
 
-// Host points: uploaded, then the sweep's own two sweeps and kernel -- a strip scan on the host would cost about 40 us a point at 1024
-// strips, and the device's values are the sweep's bits.  val: M; sums (the gradient's): 6 M, see EhviArgs.
+// Host points through the sweep's own route -- a strip scan on the host would cost about 40 us a point at 1024 strips, and the device's
+// values are the sweep's bits.  val: M; sums (the gradient's): 6 M, see EhviArgs.
 static int ehvi_eval_host(const EhviCall &c, int64_t M, const double *Q_host, double *val, double *sums)
 {
-    const size_t m = (size_t)M;
-    hipStream_t s = c.g1->stream;
-    const size_t rows = (size_t)class_padded(M, M), D = (size_t)c.g1->D;      // (a short batch carries its padding: no copy on the device)
-    ScopedBuf<double> q, out;
-    IBO_TRY(q.ensure(rows * D)); IBO_TRY(out.ensure(m * (sums ? 7 : 1)));
-    HIP_TRY(hipMemcpyAsync(q.p, Q_host, sizeof(double) * m * D, hipMemcpyHostToDevice, s));
-    if (rows > m) HIP_TRY(hipMemsetAsync(q.p + m * D, 0, sizeof(double) * (rows - m) * D, s));
-    HIP_TRY(hipStreamSynchronize(s));                          // (the second model's sweep reads them on its own stream)
-    EhviOut o;
-    o.val_dev = out.p; o.sums_dev = sums ? out.p + m : nullptr;
-    IBO_TRY(ehvi_device(c, M, q.p, (int64_t)rows, 0, nullptr, 0.0, 0, o));
-    if (val) HIP_TRY(hipMemcpyAsync(val, out.p, sizeof(double) * m, hipMemcpyDeviceToHost, s));
-    if (sums) HIP_TRY(hipMemcpyAsync(sums, out.p + m, sizeof(double) * 6 * m, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return IBO_OK;
+    MomentsPipeline p;
+    ehvi_pipeline(c, M, &p);
+    double *const host[2] = {val, sums};
+    const size_t len[2] = {(size_t)M, 6 * (size_t)M};
+    return p.eval_host(M, Q_host, sums ? 2 : 1, host, len);
 }
 
 extern "C" int ibo_ehvi_batch(ibo_gp_t *const *obj, int nfront, const double *front_host, const double *ref,

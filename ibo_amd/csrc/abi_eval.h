@@ -1,5 +1,5 @@
-// abi_eval.h -- what the evaluation units (abi_sweep.hip, abi_batch.hip, abi_cacq.hip, abi_ehvi.hip, abi_mes.hip, abi_kg.hip, abi_paths.hip, abi_qei.hip, abi_gradobs.hip, abi_sparse.hip, abi_rows.hip) share beyond
-// abi_internal.h: the sweep request, the host batch, and the ONE copy of the arg-max read-back, the exclusion upload, the padding of a short sweep to its size class, the timed span, the V^T rows and the DIRECT driver.
+// abi_eval.h -- what the evaluation units (abi_sweep.hip, abi_batch.hip, abi_cacq.hip, abi_ehvi.hip, abi_mes.hip, abi_kg.hip, abi_paths.hip, abi_qei.hip, abi_gradobs.hip, abi_sparse.hip, abi_rows.hip, abi_moments.hip) share beyond
+// abi_internal.h: the sweep request, the host batch, and the ONE copy of the arg-max read-back, the exclusion upload, the padding of a short sweep to its size class, the timed span, the span clock, the V^T rows and the DIRECT driver.
 #pragma once
 #include "abi_internal.h"
 
@@ -46,6 +46,24 @@ static inline int64_t class_padded(int64_t m, int64_t mc)
     if (mc <= CLASS_PAD_LARGE_FROM) return m <= CLASS_PAD_SMALL_FROM ? CLASS_PAD_SMALL_TO : m;
     return m <= CLASS_PAD_LARGE_FROM ? CLASS_PAD_LARGE_FROM + 1 : m;
 }
+
+// The diagnostic's clock of an entry call whose unit has a timing option: two events around a span of one stream's work, the span's time
+// added to one of the unit's thread-local sums (stop waits for the span's end).  Made per call; everything is a no-op unless switched on.
+struct SpanClock {
+    bool on = false;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~SpanClock() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    int make(bool timing) { on = timing; if (on) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); } return IBO_OK; }
+    int start(hipStream_t s) { if (on) HIP_TRY(hipEventRecord(e0, s)); return IBO_OK; }
+    int stop(hipStream_t s, double *sum)
+    {
+        if (!on) return IBO_OK;
+        float ms = 0.f;
+        HIP_TRY(hipEventRecord(e1, s)); HIP_TRY(hipEventSynchronize(e1)); HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        *sum += ms;
+        return IBO_OK;
+    }
+};
 
 // ---- abi_batch.hip
 // host points in, host arrays out (any of mu / s2 / acq may be NULL): one sweep, or the pipelined chunks of a large batch

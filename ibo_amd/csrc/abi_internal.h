@@ -14,8 +14,10 @@
 //   abi_qei.hip     the Monte-Carlo parallel expected improvement (ibo_qei_*)
 //   abi_gradobs.hip the GP observed with gradients (ibo_ggp_*): its own handle around a P-row frame, the row pipeline with its own K*
 //   abi_sparse.hip  the sparse GP on inducing points (ibo_sgp_*): its own handle around two m-row frames and the kept Gram matrix
-//   abi_rows.hip    the row pipeline of the three above: chunk, scratch, stage clock, host batch, device sweep (abi_rows.h)
-//                   (these eleven are the evaluation units: what they share among themselves is in abi_eval.h)
+//   abi_rows.hip    the row pipeline of abi_kg, abi_qei and abi_gradobs: chunk, scratch, stage clock, host batch, device sweep (abi_rows.h)
+//   abi_moments.hip the moments pipeline of abi_cacq, abi_ehvi, abi_mes and abi_sparse: the plain sweeps of a chunk into scratch, the
+//                   stream rule, the padded tail, host batch, device sweep (abi_moments.h)
+//                   (these twelve are the evaluation units: what they share among themselves is in abi_eval.h)
 //   abi_nlml.hip    marginal-likelihood grid and gradient, ibo_trim
 //   abi_legacy.hip  libego's symbols (acqmaxGP, direct, logCDFs) and ibo_direct_host
 // There is no CPU fallback anywhere behind this header: without a gfx950 device every compute entry point returns IBO_ERR_NO_DEVICE.

@@ -1,4 +1,4 @@
-// abi_rows.h -- the row pipeline of the acquisitions built on kg.hip's row kernel (abi_kg.hip, abi_qei.hip): a chunk of candidates goes
+// abi_rows.h -- the row pipeline of the acquisitions built on kg.hip's row kernel (abi_kg.hip, abi_qei.hip, abi_gradobs.hip): a chunk of candidates goes
 // through K*, V^T = K* W^T and the row kernel, then the unit's own tail (its cross launch and its last kernel).  The ONE copy of the chunk,
 // the chunk length, the scratch, the stage clock, the host batch and the device sweep -- abi_rows.hip.
 #pragma once

@@ -9,14 +9,14 @@
 // are not kept.
 //   chunk of data     upload (pinned staging) -> U sweep (s2_U, unclipped) -> sgp_scaled_kuf_kernel -> sgp_gram_kernel, on the A frame's stream
 //   refactor          K~uu (the U frame's R) + G -> sgp_assemble_kernel -> fit_factor on the A frame
-//   chunk of points   U sweep, A sweep into pool scratch -> sgp_finish_kernel; launch_argmax_final for the winner
+//   chunk of points   U sweep, A sweep into pool scratch -> sgp_finish_kernel; launch_argmax_final for the winner (abi_moments.h)
 // Host batches and DIRECT are uploaded and take the route of the sweep: the same bits within a size class of the plain sweep (class_padded).
 // ibo_sgp_nlml_grad (at the end; kernels: sparse_grad.hip) is stateless: ibo_sgp_fit on a private per-device handle, then
 //   the inverses      A^-1 = W_A^T W_A, K~uu^-1 = W_u^T W_u (launch_wtw)
 //   chunk of data     upload -> U sweep, A sweep (q, mu, a) -> sgp_grad_obs_kernel -> sgp_grad_gen_kernel -> sgp_grad_contract_kernel
 //                     -> sgp_grad_reduce_kernel; not for dtc: H += (K E) K^T (sgp_abt_kernel)
 //   after the chunks  S from A^-1, K~uu^-1, alpha and K~uu^-1 H K~uu^-1, then the contraction kernel again with Z as the observations
-#include "abi_eval.h"
+#include "abi_moments.h"
 #include "abi_factor.h"
 #include "sparse.h"
 #include "sparse_grad.h"
@@ -42,24 +42,6 @@ struct ibo_sgp {
 
 namespace {
 
-// the diagnostic's events: made per call, a stage at a time (the stage's stream is waited for)
-struct SgpClock {
-    bool on = false;
-    double *dst = t_sgp_ms;                  // (the gradient's stages: t_sgp_grad_ms)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~SgpClock() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    int make() { on = g_sgp_timing != 0; if (on) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); } return IBO_OK; }
-    int start(hipStream_t s) { if (on) HIP_TRY(hipEventRecord(e0, s)); return IBO_OK; }
-    int stop(hipStream_t s, int stage)
-    {
-        if (!on) return IBO_OK;
-        float ms = 0.f;
-        HIP_TRY(hipEventRecord(e1, s)); HIP_TRY(hipEventSynchronize(e1)); HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        dst[stage] += ms;
-        return IBO_OK;
-    }
-};
-
 int sgp_pinned(ibo_sgp *h, size_t need)
 {
     if (need <= h->pin_cap) return IBO_OK;
@@ -77,29 +59,20 @@ bool all_finite(const double *p, size_t n)
     return true;
 }
 
-// observations / candidates per chunk: a multiple of 256 unless the whole call is one chunk
-int64_t sgp_chunking(int64_t n, int64_t by_bytes)
-{
-    int64_t nc = by_bytes / 256 * 256;
-    if (nc < 256) nc = 256;
-    if (g_sgp_chunk > 0) nc = ((int64_t)g_sgp_chunk + 255) / 256 * 256;
-    return n <= nc ? n : nc;
-}
-
 // n observations into G+, ll, tt, N and the largest target; chunks in ascending order on the A frame's stream
 int sgp_accumulate(ibo_sgp *h, int64_t n, const double *X, const double *Y, double *lambda_host)
 {
     ibo_gp *gu = h->gu, *ga = h->ga;
     hipStream_t su = gu->stream, sa = ga->stream;
     const int D = h->D, m = h->m, mp = h->mp;
-    const int64_t nc = sgp_chunking(n, ((int64_t)256 << 20) / (8 * (int64_t)(mp + 64)));
+    const int64_t nc = moments_chunk_length(n, 8 * (int64_t)(mp + 64), g_sgp_chunk, (int64_t)256 << 20);
     const int64_t rows = class_padded(nc, nc), ldmax = (nc + 31) / 32 * 32, nblkmax = (nc + 255) / 256;
     ScopedBuf<double> xc, yc, s2, Ft, lam, part;
     IBO_TRY(xc.ensure((size_t)rows * D)); IBO_TRY(yc.ensure((size_t)nc)); IBO_TRY(s2.ensure((size_t)rows));
     IBO_TRY(Ft.ensure((size_t)(mp + 64) * ldmax)); IBO_TRY(lam.ensure((size_t)nc)); IBO_TRY(part.ensure(2 * (size_t)nblkmax));
     IBO_TRY(sgp_pinned(h, (size_t)rows * D + 2 * (size_t)nc + 2 * (size_t)nblkmax));
-    SgpClock clock;
-    IBO_TRY(clock.make());
+    SpanClock clock;
+    IBO_TRY(clock.make(g_sgp_timing != 0));
     for (int64_t c0 = 0; c0 < n; c0 += nc) {
         const int64_t k = n - c0 < nc ? n - c0 : nc, kp = class_padded(k, nc), nblk = (k + 255) / 256;
         double *px = h->pin, *py = px + (size_t)rows * D, *pl = py + nc, *pp = pl + nc;
@@ -116,7 +89,7 @@ int sgp_accumulate(ibo_sgp *h, int64_t n, const double *X, const double *Y, doub
         r.M = kp; r.cand_dev = xc.p; r.acq = IBO_ACQ_NONE; r.clamp_lo = -1.0; r.s2_dev = s2.p;
         IBO_TRY(clock.start(su));
         IBO_TRY(run_sweep(gu, r));
-        IBO_TRY(clock.stop(su, SGP_ST_Q));
+        IBO_TRY(clock.stop(su, &t_sgp_ms[SGP_ST_Q]));
         HIP_TRY(hipStreamSynchronize(su));                       // the generation runs on the A frame's stream
         SgpKufArgs a;
         memset(&a, 0, sizeof(a));
@@ -125,10 +98,10 @@ int sgp_accumulate(ibo_sgp *h, int64_t n, const double *X, const double *Y, doub
         a.Ft = Ft.p; a.lam = lam.p; a.part = part.p;
         IBO_TRY(clock.start(sa));
         KERNEL_TRY(launch_sgp_scaled_kuf(a, sa));
-        IBO_TRY(clock.stop(sa, SGP_ST_GEN));
+        IBO_TRY(clock.stop(sa, &t_sgp_ms[SGP_ST_GEN]));
         IBO_TRY(clock.start(sa));
         KERNEL_TRY(launch_sgp_gram(Ft.p, a.ld, mp, h->Gp.p, sa));
-        IBO_TRY(clock.stop(sa, SGP_ST_GRAM));
+        IBO_TRY(clock.stop(sa, &t_sgp_ms[SGP_ST_GRAM]));
         HIP_TRY(hipMemcpyAsync(pp, part.p, sizeof(double) * 2 * (size_t)nblk, hipMemcpyDeviceToHost, sa));
         if (lambda_host) HIP_TRY(hipMemcpyAsync(pl, lam.p, sizeof(double) * (size_t)k, hipMemcpyDeviceToHost, sa));
         HIP_TRY(hipStreamSynchronize(sa));                       // the staging and the scratch are the next chunk's
@@ -156,21 +129,21 @@ int sgp_refactor(ibo_sgp *h, int *info)
     ibo_gp *gu = h->gu, *ga = h->ga;
     hipStream_t sa = ga->stream;
     const int m = h->m, mp = h->mp;
-    SgpClock clock;
-    IBO_TRY(clock.make());
+    SpanClock clock;
+    IBO_TRY(clock.make(g_sgp_timing != 0));
     IBO_TRY(ensure_R(gu));
     HIP_TRY(hipStreamSynchronize(gu->stream));
     IBO_TRY(ga->A.ensure((size_t)m * m));
     IBO_TRY(clock.start(sa));
     KERNEL_TRY(launch_sgp_assemble(gu->R.p, gu->Npad, h->Gp.p, mp + 64, m, mp, ga->Npad, ga->A.p, ga->Y.p, sa));
-    IBO_TRY(clock.stop(sa, SGP_ST_ASSEMBLE));
+    IBO_TRY(clock.stop(sa, &t_sgp_ms[SGP_ST_ASSEMBLE]));
     ga->maxY = h->maxY;
     ga->st_gen = 0;
     IBO_TRY(clock.start(sa));
     const int rc = fit_factor(ga, h->kp, m, 0.0, true, info);        // synchronises
     if (rc == IBO_ERR_NOT_PD) return fail(IBO_ERR_NOT_PD, "A = K~uu + G is not positive definite (pivot %d)", info ? *info : -1);
     IBO_TRY(rc);
-    IBO_TRY(clock.stop(sa, SGP_ST_FACTOR));
+    IBO_TRY(clock.stop(sa, &t_sgp_ms[SGP_ST_FACTOR]));
     // |W_A b|^2 from launch_alpha's first product (fit_end left W_A b at the head of the frame's scratch)
     std::vector<double> wb((size_t)m);
     HIP_TRY(hipMemcpy(wb.data(), ga->tmp.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost));
@@ -193,79 +166,36 @@ int sgp_check(ibo_sgp *h, bool ptrs_ok, int64_t M, int acq, int erf_mode, bool n
 }
 
 struct SgpCall { int acq, erf_mode; double parm, clamp_lo, ymax; };
-struct SgpOut { double *mu = nullptr, *s2 = nullptr, *acq = nullptr; double *best_val = nullptr; int64_t *best_idx = nullptr; };
+enum { SGP_OUT_MU = 0, SGP_OUT_S2, SGP_OUT_ACQ };           // MomentsPipeline::out
 
-// The one route of every evaluating entry.  cand_rows: the rows cand_dev has room for (>= M; rows from M on are the caller's padding).
-int sgp_device(ibo_sgp *h, const SgpCall &c, int64_t M, const double *cand_dev, int64_t cand_rows, int n_excl, const double *excl_host,
-               double excl_radius, int64_t index_base, const SgpOut &o)
+// The one route of every evaluating entry: per chunk s2_U from the U frame, (mu, s2_A) from the A frame -- nothing is clipped before the
+// composition -- then sgp_finish_kernel on the A frame's stream.
+void sgp_pipeline(ibo_sgp *h, const SgpCall &c, MomentsPipeline *p)
 {
-    ibo_gp *gu = h->gu, *ga = h->ga;
-    hipStream_t su = gu->stream, sa = ga->stream;
-    const int D = h->D;
-    SgpFinishArgs a;
-    memset(&a, 0, sizeof(a));
-    a.D = D; a.noise = h->noise; a.jitter = h->jitter; a.clamp_lo = c.clamp_lo; a.ymax = c.ymax == c.ymax ? c.ymax : h->maxY; a.parm = c.parm;
-    a.acq = c.acq; a.erf_mode = c.erf_mode; a.index_base = index_base; a.excl_radius = excl_radius;
-    IBO_TRY(upload_exclusions(ga, n_excl, excl_host, &a.n_excl, &a.excl));
-    const int64_t mc = sgp_chunking(M, ((int64_t)1 << 30) / 24);
-    const int64_t stride = class_padded(mc, mc), nblk = (M + 255) / 256;
-    ScopedBuf<double> ms, pv, pad;
-    ScopedBuf<int64_t> pi;
-    IBO_TRY(ms.ensure(3 * (size_t)stride)); IBO_TRY(pv.ensure((size_t)nblk)); IBO_TRY(pi.ensure((size_t)nblk));
-    SgpClock clock;
-    IBO_TRY(clock.make());
-    a.s2u = ms.p; a.mua = ms.p + stride; a.s2a = ms.p + 2 * stride;
-    for (int64_t c0 = 0; c0 < M; c0 += mc) {
-        const int64_t k = M - c0 < mc ? M - c0 : mc, kp = class_padded(k, mc);
-        const double *rows = cand_dev + c0 * D;
-        if (c0 + kp > cand_rows) {                               // a padded copy where the padded launch does not fit into the caller's rows
-            IBO_TRY(pad.ensure((size_t)kp * D));
-            HIP_TRY(hipMemcpyAsync(pad.p, rows, sizeof(double) * (size_t)k * D, hipMemcpyDeviceToDevice, sa));
-            HIP_TRY(hipMemsetAsync(pad.p + (size_t)k * D, 0, sizeof(double) * (size_t)(kp - k) * D, sa));
-            HIP_TRY(hipStreamSynchronize(sa));                   // (the U frame reads it on its own stream)
-            rows = pad.p;
-        }
-        SweepRequest r;
-        r.M = kp; r.cand_dev = rows; r.acq = IBO_ACQ_NONE; r.clamp_lo = -1.0;     // nothing is clipped before the composition
-        r.s2_dev = ms.p;
-        IBO_TRY(clock.start(su));
-        IBO_TRY(run_sweep(gu, r));
-        HIP_TRY(hipStreamSynchronize(su));                       // the finish runs on the A frame's stream
-        r.mu_dev = ms.p + stride; r.s2_dev = ms.p + 2 * stride;
-        IBO_TRY(run_sweep(ga, r));
-        if (clock.on) { HIP_TRY(hipStreamSynchronize(sa)); IBO_TRY(clock.stop(su, SGP_ST_SWEEPS)); }
-        a.M = k; a.first = c0; a.cand = rows;
-        a.out_mu = o.mu ? o.mu + c0 : nullptr; a.out_s2 = o.s2 ? o.s2 + c0 : nullptr; a.out_acq = o.acq ? o.acq + c0 : nullptr;
-        a.part_val = pv.p + c0 / 256; a.part_idx = pi.p + c0 / 256;
-        IBO_TRY(clock.start(sa));
-        KERNEL_TRY(launch_sgp_finish(a, sa));
-        IBO_TRY(clock.stop(sa, SGP_ST_FINISH));
-        if (c0 + mc < M) HIP_TRY(hipStreamSynchronize(sa));      // the next chunk's U sweep, on the other stream, writes the same scratch
-    }
-    if (o.best_val || o.best_idx) return argmax_readback(ga, pv.p, pi.p, nblk, o.best_val, o.best_idx);
-    HIP_TRY(hipStreamSynchronize(sa));
-    return IBO_OK;
+    p->add(h->gu, false, true, -1.0, IBO_ERF_LIBM);
+    p->add(h->ga, true, true, -1.0, IBO_ERF_LIBM);
+    p->home = h->ga; p->chunk_opt = g_sgp_chunk; p->timing = g_sgp_timing != 0;
+    p->sweeps_ms = &t_sgp_ms[SGP_ST_SWEEPS]; p->finish_ms = &t_sgp_ms[SGP_ST_FINISH];
+    p->finish = [h, &c, p](const MomentChunk &k, hipStream_t s) -> int {
+        SgpFinishArgs a;
+        memset(&a, 0, sizeof(a));
+        a.noise = h->noise; a.jitter = h->jitter; a.clamp_lo = c.clamp_lo; a.ymax = c.ymax == c.ymax ? c.ymax : h->maxY; a.parm = c.parm;
+        a.acq = c.acq; a.erf_mode = c.erf_mode;
+        a.t = k.tail; a.s2u = k.ms; a.mua = k.ms + k.stride; a.s2a = k.ms + 2 * k.stride;
+        a.out_mu = k.at(p->out[SGP_OUT_MU]); a.out_s2 = k.at(p->out[SGP_OUT_S2]); a.out_acq = k.at(p->out[SGP_OUT_ACQ]);
+        KERNEL_TRY(launch_sgp_finish(a, s));
+        return IBO_OK;
+    };
 }
 
-// Host points: uploaded, then the sweep's own route -- the device's values are the sweep's bits.
+// Host points through the sweep's own route -- the device's values are the sweep's bits.
 int sgp_eval_host(ibo_sgp *h, const SgpCall &c, int64_t M, const double *Q_host, double *mu, double *s2, double *acq)
 {
-    const size_t m = (size_t)M, D = (size_t)h->D;
-    hipStream_t s = h->ga->stream;
-    const size_t rows = (size_t)class_padded(M, sgp_chunking(M, ((int64_t)1 << 30) / 24));     // (a short batch carries its padding)
-    ScopedBuf<double> q, out;
-    IBO_TRY(q.ensure(rows * D)); IBO_TRY(out.ensure(3 * m));
-    HIP_TRY(hipMemcpyAsync(q.p, Q_host, sizeof(double) * m * D, hipMemcpyHostToDevice, s));
-    if (rows > m) HIP_TRY(hipMemsetAsync(q.p + m * D, 0, sizeof(double) * (rows - m) * D, s));
-    HIP_TRY(hipStreamSynchronize(s));                            // (Q_host is the caller's pageable memory; the U frame reads q on its own stream)
-    SgpOut o;
-    o.mu = mu ? out.p : nullptr; o.s2 = s2 ? out.p + m : nullptr; o.acq = acq ? out.p + 2 * m : nullptr;
-    IBO_TRY(sgp_device(h, c, M, q.p, (int64_t)rows, 0, nullptr, 0.0, 0, o));
-    if (mu) HIP_TRY(hipMemcpyAsync(mu, out.p, sizeof(double) * m, hipMemcpyDeviceToHost, s));
-    if (s2) HIP_TRY(hipMemcpyAsync(s2, out.p + m, sizeof(double) * m, hipMemcpyDeviceToHost, s));
-    if (acq) HIP_TRY(hipMemcpyAsync(acq, out.p + 2 * m, sizeof(double) * m, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return IBO_OK;
+    MomentsPipeline p;
+    sgp_pipeline(h, c, &p);
+    double *const host[3] = {mu, s2, acq};
+    const size_t len[3] = {(size_t)M, (size_t)M, (size_t)M};
+    return p.eval_host(M, Q_host, 3, host, len);
 }
 
 }  // namespace
@@ -369,9 +299,10 @@ extern "C" int ibo_sgp_acq_sweep(ibo_sgp_t *h, int64_t M, const double *cand_dev
     IBO_TRY(sgp_check(h, cand_dev != nullptr, M, acq, erf_mode, true));
     if (!mu_dev && !s2_dev && !acq_dev && !best_val && !best_idx) return fail(IBO_ERR_ARG, "every output is NULL");
     const SgpCall c = {acq, erf_mode, parm, clamp_lo, ymax};
-    SgpOut o;
-    o.mu = mu_dev; o.s2 = s2_dev; o.acq = acq_dev; o.best_val = best_val; o.best_idx = best_idx;
-    return sgp_device(h, c, M, cand_dev, M, n_excl, excl_host, excl_radius, index_base, o);
+    MomentsPipeline p;
+    sgp_pipeline(h, c, &p);
+    p.out[SGP_OUT_MU] = mu_dev; p.out[SGP_OUT_S2] = s2_dev; p.out[SGP_OUT_ACQ] = acq_dev;
+    return p.sweep(M, cand_dev, M, n_excl, excl_host, excl_radius, index_base, best_val, best_idx);
 }
 
 extern "C" int ibo_sgp_direct_max(ibo_sgp_t *h, int D, const double *lb, const double *ub, int acq, double parm, int erf_mode,
@@ -475,9 +406,8 @@ int sgp_grad_pass(ibo_sgp *h, int kind, int64_t N, const double *X, const double
     if (gu->Npad != ldi || ldi < mp) return fail(IBO_ERR_STATE, "the two frames are padded to %d and %d rows for mp=%d", gu->Npad, ldi, mp);
     const bool two = kind != SGP_GRAD_DTC;                      // a DTC objective has e = 0: no K~uu^-1 half, no signed Gram matrix
     const int ldb = (two ? 2 : 1) * mp;
-    SgpClock clock;
-    clock.dst = t_sgp_grad_ms;
-    IBO_TRY(clock.make());
+    SpanClock clock;
+    IBO_TRY(clock.make(g_sgp_timing != 0));
     // the inverses: A^-1 = W_A^T W_A, K~uu^-1 = W_u^T W_u (ibo_nlml_grad's product)
     const size_t nn = (size_t)ldi * ldi;
     ScopedBuf<double> Ainv, Uinv, wt;
@@ -486,9 +416,9 @@ int sgp_grad_pass(ibo_sgp *h, int kind, int64_t N, const double *X, const double
     IBO_TRY(clock.start(sa));
     KERNEL_TRY(launch_wtw(ga->W.p, wt.p, Ainv.p, ldi, sa));
     KERNEL_TRY(launch_wtw(gu->W.p, wt.p, Uinv.p, ldi, sa));
-    IBO_TRY(clock.stop(sa, SGP_GR_INVERSES));
+    IBO_TRY(clock.stop(sa, &t_sgp_grad_ms[SGP_GR_INVERSES]));
     // the chunks: the fit's chunking, so that the U sweep gives the fit's q_i bit for bit
-    const int64_t nc = sgp_chunking(N, ((int64_t)256 << 20) / (8 * (int64_t)(mp + 64)));
+    const int64_t nc = moments_chunk_length(N, 8 * (int64_t)(mp + 64), g_sgp_chunk, (int64_t)256 << 20);
     const int64_t rows = class_padded(nc, nc), ldmax = (nc + 63) / 64 * 64, nblkmax = (ldmax + 255) / 256;
     const int rb = mp / 64;
     // a workgroup per 64 inducing rows and strip of tiles: about 1024 workgroups, the strips as even as the tiles allow
@@ -535,7 +465,7 @@ int sgp_grad_pass(ibo_sgp *h, int kind, int64_t N, const double *X, const double
         HIP_TRY(hipStreamSynchronize(su));
         r.mu_dev = ms.p + rows; r.s2_dev = ms.p + 2 * rows;
         IBO_TRY(run_sweep(ga, r));
-        if (clock.on) { HIP_TRY(hipStreamSynchronize(sa)); IBO_TRY(clock.stop(su, SGP_GR_SWEEPS)); }
+        if (clock.on) { HIP_TRY(hipStreamSynchronize(sa)); IBO_TRY(clock.stop(su, &t_sgp_grad_ms[SGP_GR_SWEEPS])); }
         SgpGradObsArgs o;
         memset(&o, 0, sizeof(o));
         o.n = (int)k; o.ld = ld; o.kind = kind; o.noise = h->noise; o.jitter = h->jitter; o.s2u = ms.p; o.mua = ms.p + rows; o.s2a = ms.p + 2 * rows;
@@ -547,21 +477,21 @@ int sgp_grad_pass(ibo_sgp *h, int kind, int64_t N, const double *X, const double
         IBO_TRY(clock.start(sa));
         KERNEL_TRY(launch_sgp_grad_obs(o, sa));
         KERNEL_TRY(launch_sgp_grad_gen(ge, sa));
-        IBO_TRY(clock.stop(sa, SGP_GR_GEN));
+        IBO_TRY(clock.stop(sa, &t_sgp_grad_ms[SGP_GR_GEN]));
         g.X = xc.p; g.ldx = D; g.n = (int)k; g.ntiles = ld / 64;
         g.nstrips = strips_for(g.ntiles, &g.tiles_per_strip);
         if (g.nstrips > nsmax) return fail(IBO_ERR_STATE, "%d strips, room for %d", g.nstrips, nsmax);
         IBO_TRY(zero_partials(g.nstrips));
         IBO_TRY(clock.start(sa));
         KERNEL_TRY(launch_sgp_grad_contract(g, 0, sa));
-        IBO_TRY(clock.stop(sa, SGP_GR_CONTRACT));
+        IBO_TRY(clock.stop(sa, &t_sgp_grad_ms[SGP_GR_CONTRACT]));
         IBO_TRY(clock.start(sa));
         KERNEL_TRY(launch_sgp_grad_reduce(partZ, partL, partS, g.nstrips, m, mp, D, totd.p, totd.p + tn, totd.p + 2 * tn, sa));
-        IBO_TRY(clock.stop(sa, SGP_GR_REDUCE));
+        IBO_TRY(clock.stop(sa, &t_sgp_grad_ms[SGP_GR_REDUCE]));
         if (two) {                                               // H += (K E) K^T, the lower tiles, continued in ascending observation order
             IBO_TRY(clock.start(sa));
             KERNEL_TRY(launch_sgp_abt(ge.KEt, ld, ge.Kt, ld, H.p, mp, mp, ld, 1, 1, sa));
-            IBO_TRY(clock.stop(sa, SGP_GR_GRAM));
+            IBO_TRY(clock.stop(sa, &t_sgp_grad_ms[SGP_GR_GRAM]));
         }
         HIP_TRY(hipMemcpyAsync(pp, pc.p, sizeof(double) * (size_t)nblk, hipMemcpyDeviceToHost, sa));
         HIP_TRY(hipStreamSynchronize(sa));
@@ -586,7 +516,7 @@ int sgp_grad_pass(ibo_sgp *h, int kind, int64_t N, const double *X, const double
     KERNEL_TRY(launch_sgp_grad_contract(g, 1, sa));
     double *t1 = totd.p + 2 * tn + 1;
     KERNEL_TRY(launch_sgp_grad_reduce(partZ, partL, partS, g.nstrips, m, mp, D, t1, t1 + tn, t1 + 2 * tn, sa));
-    IBO_TRY(clock.stop(sa, SGP_GR_UU));
+    IBO_TRY(clock.stop(sa, &t_sgp_grad_ms[SGP_GR_UU]));
     std::vector<double> host(2 * (2 * tn + 1));
     HIP_TRY(hipMemcpyAsync(host.data(), totd.p, sizeof(double) * host.size(), hipMemcpyDeviceToHost, sa));
     HIP_TRY(hipStreamSynchronize(sa));
@@ -613,12 +543,11 @@ extern "C" int ibo_sgp_nlml_grad(int device, int ktype, int D, const double *hyp
     std::lock_guard<std::mutex> lk(g_dev_mu[device & 15]);      // (the private handle is per device)
     ibo_sgp *&h = g_sgp_grad_handle[device & 15];
     if (!h) IBO_TRY(ibo_sgp_create(device, &h));
-    SgpClock clock;
-    clock.dst = t_sgp_grad_ms;
-    IBO_TRY(clock.make());
+    SpanClock clock;
+    IBO_TRY(clock.make(g_sgp_timing != 0));
     IBO_TRY(clock.start(h->ga->stream));
     IBO_TRY(ibo_sgp_fit(h, ktype, D, hyper, nhyper, sf2, noise, jitter, kind == IBO_SGP_VFE ? IBO_SGP_DTC : kind, m, Z, N, X, Y, nullptr, info));
-    IBO_TRY(clock.stop(h->ga->stream, SGP_GR_FIT));
+    IBO_TRY(clock.stop(h->ga->stream, &t_sgp_grad_ms[SGP_GR_FIT]));
     double v = 0.0;
     IBO_TRY(ibo_sgp_nlml(h, kind == IBO_SGP_VFE ? IBO_SGP_NLML_VFE : IBO_SGP_NLML_MODEL, &v));
     const bool want_hyper = ngrad > 0 && grad_hyper;

@@ -7,15 +7,10 @@
 // constraint model in order (the objective's pair is not read when spec.acq == 3).
 struct CacqArgs {
     CacqSpec spec;
-    int64_t M;                           // candidates of this chunk (<= stride)
-    int64_t first;                       // the chunk's first candidate in the call's array (a multiple of 256)
     int64_t stride;
     const double *ms;
-    const double *cand; int D;           // the chunk's candidates, M x D
-    int n_excl; const double *excl; double excl_radius;     // n_excl x D (device)
-    int64_t index_base;
+    FinishTail t;                        // the chunk (t.M <= stride), the exclusion balls, the partials
     double *out_acq, *out_pof, *out_val; // the chunk's part of the optional outputs
-    double *part_val; int64_t *part_idx; // the chunk's partials: one per 256 candidates
 };
 int launch_cacq_finish(const CacqArgs &a, hipStream_t s);
 

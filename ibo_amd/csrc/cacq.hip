@@ -11,34 +11,24 @@
 __global__ __launch_bounds__(256) void cacq_finish_kernel(CacqArgs a)
 {
     const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = li < a.M;
-    const int64_t gi = valid ? li : a.M - 1;
+    const bool valid = li < a.t.M;
+    const int64_t gi = valid ? li : a.t.M - 1;
     double A, P;
     double val = cacq_value_dev(a.spec, [&](int k, double *mu, double *s2) {
         *mu = a.ms[(size_t)(2 * k) * a.stride + gi];
         *s2 = a.ms[(size_t)(2 * k + 1) * a.stride + gi];
     }, &A, &P);
-    const double *xp = a.cand + gi * a.D;
-    bool excl = false;
-    for (int e = 0; e < a.n_excl; e++) {             // (finish_candidate's rule, coordinates read from the candidate array)
-        double d2 = 0.0;
-        for (int j = 0; j < a.D; j++) { double t = xp[j] - a.excl[(size_t)e * a.D + j]; d2 += t * t; }
-        if (!(sqrt(d2) > a.excl_radius)) excl = true;
-    }
-    if (valid) {
+    finish_tail<true>(a.t, li, val, [&] {
         if (a.out_acq) a.out_acq[li] = A;
         if (a.out_pof) a.out_pof[li] = P;
         if (a.out_val) a.out_val[li] = val;
-    }
-    int64_t idx = a.index_base + a.first + li;
-    if (!valid || excl || !(val == val)) { val = -INFINITY; idx = INT64_MAX; }
-    block256_argmax(val, idx, a.part_val, a.part_idx);
+    });
 }
 
 int launch_cacq_finish(const CacqArgs &a, hipStream_t s)
 {
-    if (a.M < 1 || a.M > a.stride || (a.first & 255)) return (int)hipErrorInvalidValue;
-    const int64_t nblk = (a.M + 255) / 256;
+    if (!finish_tail_ok(a.t) || a.t.M > a.stride) return (int)hipErrorInvalidValue;
+    const int64_t nblk = (a.t.M + 255) / 256;
     hipLaunchKernelGGL(cacq_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, s, a);
     return (int)hipGetLastError();
 }

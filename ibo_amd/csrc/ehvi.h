@@ -11,16 +11,11 @@ struct EhviArgs {
     int erf_mode;
     double r1, r2;                       // the reference point: a_0 = r1, b_{n+1} = r2
     const double *front;                 // device, n interleaved (a_i, b_i), a ascending, b descending
-    int64_t M;                           // candidates of this chunk (<= stride)
-    int64_t first;                       // the chunk's first candidate in the call's array (a multiple of 256)
-    int64_t stride;                      // (>= M: a short launch is padded for the sweeps, see abi_ehvi.hip)
+    int64_t stride;                      // (>= t.M: a short launch is padded for the sweeps, see abi_eval.h: class_padded)
     const double *ms;
-    const double *cand; int D;           // the chunk's candidates, M x D
-    int n_excl; const double *excl; double excl_radius;     // n_excl x D (device)
-    int64_t index_base;
+    FinishTail t;                        // the chunk, the exclusion balls, the partials
     double *out_val;                     // the chunk's part of the optional output
     double *out_sums; int64_t sums_stride;      // the gradient's variant: the chunk's part of six arrays `sums_stride` apart -- G_mu1, G_sigma1, G_mu2, G_sigma2, sigma_1, sigma_2
-    double *part_val; int64_t *part_idx; // the chunk's partials: one per 256 candidates
 };
 // sums: the variant that also stores out_sums (the same value, bit for bit)
 int launch_ehvi_finish(const EhviArgs &a, bool sums, hipStream_t s);

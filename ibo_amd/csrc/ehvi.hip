@@ -33,8 +33,8 @@ __global__ __launch_bounds__(256) void ehvi_finish_kernel(EhviArgs a)
     for (int k = threadIdx.x; k < 2 * a.n; k += 256) fr[k] = a.front[k];
     __syncthreads();
     const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = li < a.M;
-    const int64_t gi = valid ? li : a.M - 1;
+    const bool valid = li < a.t.M;
+    const int64_t gi = valid ? li : a.t.M - 1;
     const double mu1 = a.ms[gi], sg1 = sqrt(a.ms[(size_t)a.stride + gi]);
     const double mu2 = a.ms[2 * (size_t)a.stride + gi], sg2 = sqrt(a.ms[3 * (size_t)a.stride + gi]);
     double c0, p0, c1, p1, c2, p2;
@@ -59,31 +59,21 @@ __global__ __launch_bounds__(256) void ehvi_finish_kernel(EhviArgs a)
         }
         prev = next;
     }
-    const double *xp = a.cand + gi * a.D;
-    bool excl = false;
-    for (int e = 0; e < a.n_excl; e++) {             // (finish_candidate's rule, coordinates read from the candidate array)
-        double d2 = 0.0;
-        for (int j = 0; j < a.D; j++) { double t = xp[j] - a.excl[(size_t)e * a.D + j]; d2 += t * t; }
-        if (!(sqrt(d2) > a.excl_radius)) excl = true;
-    }
-    if (valid) {
+    finish_tail<false>(a.t, li, val, [&] {
         if (a.out_val) a.out_val[li] = val;
         if (SUMS) {
             const size_t st = (size_t)a.sums_stride;
             a.out_sums[li] = gm1; a.out_sums[st + li] = gs1; a.out_sums[2 * st + li] = gm2; a.out_sums[3 * st + li] = gs2;
             a.out_sums[4 * st + li] = sg1; a.out_sums[5 * st + li] = sg2;
         }
-    }
-    int64_t idx = a.index_base + a.first + li;
-    if (!valid || excl || !(val == val)) { val = -INFINITY; idx = INT64_MAX; }
-    block256_argmax(val, idx, a.part_val, a.part_idx);
+    });
 }
 
 int launch_ehvi_finish(const EhviArgs &a, bool sums, hipStream_t s)
 {
-    if (a.M < 1 || a.M > a.stride || (a.first & 255) || a.n < 0 || a.n > IBO_EHVI_MAX_PAIRS || (a.n > 0 && !a.front) || (a.erf_mode != 0 && a.erf_mode != 1) || (sums && (!a.out_sums || a.sums_stride < a.M)))
+    if (!finish_tail_ok(a.t) || a.t.M > a.stride || a.n < 0 || a.n > IBO_EHVI_MAX_PAIRS || (a.n > 0 && !a.front) || (a.erf_mode != 0 && a.erf_mode != 1) || (sums && (!a.out_sums || a.sums_stride < a.t.M)))
         return (int)hipErrorInvalidValue;
-    const int64_t nblk = (a.M + 255) / 256;
+    const int64_t nblk = (a.t.M + 255) / 256;
     void (*k)(EhviArgs) = sums ? (a.erf_mode ? ehvi_finish_kernel<true, 1> : ehvi_finish_kernel<true, 0>)
                                : (a.erf_mode ? ehvi_finish_kernel<false, 1> : ehvi_finish_kernel<false, 0>);
     hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(256), 0, s, a);

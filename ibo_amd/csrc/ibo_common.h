@@ -387,6 +387,46 @@ __device__ __forceinline__ void block256_argmax(double val, int64_t idx, double 
     }
 }
 
+// What the finish kernels of the moments pipeline (abi_moments.h: cacq.hip, ehvi.hip, mes.hip, sparse.hip) are told alike about one chunk
+// of candidates; the pipeline fills it, the unit's own arguments stand beside it.  (The fields, and the struct's place after `ms` in the
+// units' arguments, keep the order the kernel arguments have always had: ehvi.hip's libm-erf instances sit at the scalar register limit, and
+// another order of the scalar loads costs them a dozen more spills.)
+struct FinishTail {
+    int64_t M;                           // candidates of this chunk
+    int64_t first;                       // the chunk's first candidate in the call's array (a multiple of 256)
+    const double *cand; int D;           // the chunk's candidates, M x D
+    int n_excl; const double *excl; double excl_radius;     // n_excl x D (device)
+    int64_t index_base;
+    double *part_val; int64_t *part_idx; // the chunk's partials: one per 256 candidates
+};
+// the half of a finish launch's argument check that does not depend on the kernel
+static inline bool finish_tail_ok(const FinishTail &t)
+{
+    return t.M >= 1 && !(t.first & 255) && t.cand && t.part_val && t.part_idx && (t.n_excl <= 0 || t.excl);
+}
+// ... and how such a kernel ends, with candidate li's value in hand: the exclusion balls (finish_candidate's rule, coordinates read from
+// the candidate array), store() -- the kernel's own per-candidate outputs, for a lane in range; after the balls, whose centres stay scalar
+// loads that way -- then a lane that is out of range, excluded or NaN never wins, the index in the call's numbering, block256_argmax.
+// FMA: whether the squared distance is summed with fused multiply-adds -- written out, because the kernels differ and a ball's edge must
+// not move with the compiler's mood: ehvi.hip and mes.hip are compiled with contraction off, cacq.hip and sparse.hip with it on.
+template <bool FMA, typename Store>
+__device__ __forceinline__ void finish_tail(const FinishTail &t, int64_t li, double val, Store store)
+{
+#pragma clang fp contract(off)
+    const bool valid = li < t.M;
+    const double *xp = t.cand + (valid ? li : t.M - 1) * t.D;
+    bool excl = false;
+    for (int e = 0; e < t.n_excl; e++) {
+        double d2 = 0.0;
+        for (int j = 0; j < t.D; j++) { double d = xp[j] - t.excl[(size_t)e * t.D + j]; d2 = FMA ? fma(d, d, d2) : d2 + d * d; }
+        if (!(sqrt(d2) > t.excl_radius)) excl = true;
+    }
+    if (valid) store();
+    int64_t idx = t.index_base + t.first + li;
+    if (!valid || excl || !(val == val)) { val = -INFINITY; idx = INT64_MAX; }
+    block256_argmax(val, idx, t.part_val, t.part_idx);
+}
+
 int launch_sweep_mfma(const SweepArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 int launch_sweep_gemv(const SweepArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 // large batches, dot form: 32-candidate tiles, 1024-row panels, exponent GEMM on the MFMA unit (sweep2.hip)

@@ -12,16 +12,11 @@ struct MesArgs {
     int K;                               // samples of the maximum (1 .. IBO_MES_MAX_K)
     const double *ystar;                 // device, K doubles, ascending
     double s2_offset, clamp_lo;          // v = max(s2 - s2_offset, clamp_lo), sigma = sqrt(v)
-    int64_t M;                           // candidates of this chunk (<= stride)
-    int64_t first;                       // the chunk's first candidate in the call's array (a multiple of 256)
-    int64_t stride;                      // (>= M: a short launch is padded for the sweep, see abi_eval.h: class_padded)
+    int64_t stride;                      // (>= t.M: a short launch is padded for the sweep, see abi_eval.h: class_padded)
     const double *ms;
-    const double *cand; int D;           // the chunk's candidates, M x D
-    int n_excl; const double *excl; double excl_radius;     // n_excl x D (device)
-    int64_t index_base;
+    FinishTail t;                        // the chunk, the exclusion balls, the partials
     double *out_val;                     // the chunk's part of the optional output
     double *out_sums; int64_t sums_stride;      // the gradient's variant: the chunk's part of four arrays `sums_stride` apart -- G_mu, G_sigma, sigma, and 1 where v follows s2 (0 where its floor is active)
-    double *part_val; int64_t *part_idx; // the chunk's partials: one per 256 candidates
 };
 // sums: the variant that also stores out_sums (the same value, bit for bit)
 int launch_mes_finish(const MesArgs &a, bool sums, hipStream_t s);

@@ -39,8 +39,8 @@ __global__ __launch_bounds__(256) void mes_finish_kernel(MesArgs a)
     for (int k = threadIdx.x; k < a.K; k += 256) ys[k] = a.ystar[k];
     __syncthreads();
     const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = li < a.M;
-    const int64_t gi = valid ? li : a.M - 1;
+    const bool valid = li < a.t.M;
+    const int64_t gi = valid ? li : a.t.M - 1;
     const double mu = a.ms[gi];
     double v = a.ms[(size_t)a.stride + gi] - a.s2_offset;
     const bool floored = v < a.clamp_lo;                             // (a NaN is not: it goes through)
@@ -59,32 +59,21 @@ __global__ __launch_bounds__(256) void mes_finish_kernel(MesArgs a)
         }
     }
     double val = sum / (double)a.K;
-    const double *xp = a.cand + gi * a.D;
-    bool excl = false;
-    for (int e = 0; e < a.n_excl; e++) {             // (finish_candidate's rule, coordinates read from the candidate array)
-        double d2 = 0.0;
-        for (int j = 0; j < a.D; j++) { double t = xp[j] - a.excl[(size_t)e * a.D + j]; d2 += t * t; }
-        if (!(sqrt(d2) > a.excl_radius)) excl = true;
-    }
-    if (valid) {
+    finish_tail<false>(a.t, li, val, [&] {
         if (a.out_val) a.out_val[li] = val;
         if (SUMS) {
             const size_t st = (size_t)a.sums_stride;
             a.out_sums[li] = -(sd / (double)a.K) / sigma; a.out_sums[st + li] = -(sdg / (double)a.K) / sigma;
             a.out_sums[2 * st + li] = sigma; a.out_sums[3 * st + li] = floored ? 0.0 : 1.0;
         }
-    }
-    int64_t idx = a.index_base + a.first + li;
-    if (!valid || excl || !(val == val)) { val = -INFINITY; idx = INT64_MAX; }
-    block256_argmax(val, idx, a.part_val, a.part_idx);
+    });
 }
 
 int launch_mes_finish(const MesArgs &a, bool sums, hipStream_t s)
 {
-    if (a.M < 1 || a.M > a.stride || (a.first & 255) || a.K < 1 || a.K > IBO_MES_MAX_K || !a.ystar || !a.ms || !a.cand || !a.part_val || !a.part_idx
-        || (a.n_excl > 0 && !a.excl) || (sums && (!a.out_sums || a.sums_stride < a.M)))
+    if (!finish_tail_ok(a.t) || a.t.M > a.stride || a.K < 1 || a.K > IBO_MES_MAX_K || !a.ystar || !a.ms || (sums && (!a.out_sums || a.sums_stride < a.t.M)))
         return (int)hipErrorInvalidValue;
-    const int64_t nblk = (a.M + 255) / 256;
+    const int64_t nblk = (a.t.M + 255) / 256;
     hipLaunchKernelGGL(sums ? mes_finish_kernel<true> : mes_finish_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, s, a);
     return (int)hipGetLastError();
 }

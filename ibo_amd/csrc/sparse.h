@@ -39,15 +39,10 @@ int launch_sgp_assemble(const double *Kuu, int ldk, const double *G, int ldg, in
 // One chunk of candidates from the two frames' plain sweeps: s2 = noise + (s2u - jitter) + (1 - s2a), clipped to [clamp_lo, 10];
 // mu = mua; then the acquisition, the exclusion balls and one (max, lowest index) partial per 256 candidates.
 struct SgpFinishArgs {
-    int64_t M;                           // candidates of this chunk
-    int64_t first;                       // the chunk's first candidate in the call's array (a multiple of 256)
+    FinishTail t;                        // the chunk, the exclusion balls, the partials
     const double *s2u, *mua, *s2a;
-    const double *cand; int D;           // the chunk's candidates, M x D
     double noise, jitter, clamp_lo, ymax, parm;
     int acq, erf_mode;
-    int n_excl; const double *excl; double excl_radius;
-    int64_t index_base;
     double *out_mu, *out_s2, *out_acq;   // the chunk's part of the optional outputs
-    double *part_val; int64_t *part_idx;
 };
 int launch_sgp_finish(const SgpFinishArgs &a, hipStream_t s);

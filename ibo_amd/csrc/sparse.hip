@@ -149,8 +149,8 @@ int launch_sgp_assemble(const double *Kuu, int ldk, const double *G, int ldg, in
 __global__ __launch_bounds__(256) void sgp_finish_kernel(SgpFinishArgs a)
 {
     const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = li < a.M;
-    const int64_t gi = valid ? li : a.M - 1;
+    const bool valid = li < a.t.M;
+    const int64_t gi = valid ? li : a.t.M - 1;
     const double mu = a.mua[gi];
     // sigma^2 + (1 - q_U) + q_A in exactly this order; additions only, so there is nothing to contract
     const double du = a.s2u[gi] - a.jitter, da = 1.0 - a.s2a[gi];
@@ -158,27 +158,17 @@ __global__ __launch_bounds__(256) void sgp_finish_kernel(SgpFinishArgs a)
     if (s2 < a.clamp_lo) s2 = a.clamp_lo;                     // (a NaN passes both clamps)
     else if (s2 > 10.0) s2 = 10.0;
     double val = (a.acq == 3) ? mu : acq_value_dev(a.acq, a.erf_mode, mu, sqrt(s2), a.ymax, a.parm);
-    const double *xp = a.cand + gi * a.D;
-    bool excl = false;
-    for (int e = 0; e < a.n_excl; e++) {                      // (finish_candidate's rule, coordinates read from the candidate array)
-        double d2 = 0.0;
-        for (int j = 0; j < a.D; j++) { double t = xp[j] - a.excl[(size_t)e * a.D + j]; d2 += t * t; }
-        if (!(sqrt(d2) > a.excl_radius)) excl = true;
-    }
-    if (valid) {
+    finish_tail<true>(a.t, li, val, [&] {
         if (a.out_mu) a.out_mu[li] = mu;
         if (a.out_s2) a.out_s2[li] = s2;
         if (a.out_acq) a.out_acq[li] = val;
-    }
-    int64_t idx = a.index_base + a.first + li;
-    if (!valid || excl || !(val == val)) { val = -INFINITY; idx = INT64_MAX; }
-    block256_argmax(val, idx, a.part_val, a.part_idx);
+    });
 }
 
 int launch_sgp_finish(const SgpFinishArgs &a, hipStream_t s)
 {
-    if (a.M < 1 || (a.first & 255)) return (int)hipErrorInvalidValue;
-    const int64_t nblk = (a.M + 255) / 256;
+    if (!finish_tail_ok(a.t)) return (int)hipErrorInvalidValue;
+    const int64_t nblk = (a.t.M + 255) / 256;
     hipLaunchKernelGGL(sgp_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, s, a);
     return (int)hipGetLastError();
 }
