@@ -5,10 +5,11 @@ The library is the product's ONLY compute path: if it is missing this module
 raises at import, and every compute call raises IBOError(IBO_ERR_NO_DEVICE)
 when no MI355X is visible.  Nothing here falls back to NumPy.
 
-Every symbol of the header is bound below and listed in EXPORTED (116 of them: tests/test_cpu_host.py holds the two lists to
+Every symbol of the header is bound below and listed in EXPORTED (118 of them: tests/test_cpu_host.py holds the two lists to
 the header and to the library), the ibo_qei_* entries of the parallel expected improvement and the ibo_ehvi_* entries of the
 two-objective hypervolume improvement, the ibo_ggp_* entries of a GP observed with gradients, the ibo_mes_* entries of
-max-value entropy search and the ibo_sgp_* entries of the sparse GP with its likelihood gradient among them.
+max-value entropy search, the ibo_sgp_* entries of the sparse GP with its likelihood gradient and ibo_ggp_nlml_grad, the
+gradient-observation model's likelihood with its gradient, among them.
 """
 import ctypes
 import os
@@ -162,6 +163,9 @@ _sig("ibo_ggp_acq_sweep", c_int, _GGP, c_int64, c_void_p, c_int, c_double, c_int
 _sig("ibo_ggp_direct_max", c_int, _GGP, c_int, _DP, _DP, c_int, c_double, c_int, c_double, c_int, c_int, c_int, c_int,
      _DP, _DP, POINTER(c_int64))
 _sig("ibo_ggp_stage_ms", c_int, _DP, c_int)
+_sig("ibo_ggp_nlml_grad", c_int, c_int, c_int, c_int, c_int, _DP, _DP, _DP, _DP, c_int, c_double, c_double, _DP, c_int,
+     POINTER(c_int), POINTER(c_int), _DP, _DP, _DP)
+_sig("ibo_ggp_grad_stage_ms", c_int, _DP, c_int)
 _SGP = c_void_p                                                            # ibo_sgp_t *
 _sig("ibo_sgp_create", c_int, c_int, POINTER(_SGP))
 _sig("ibo_sgp_destroy", c_int, _SGP)
@@ -207,7 +211,7 @@ EXPORTED = ["ibo_abi_version", "ibo_last_error", "ibo_device_count", "ibo_device
             "ibo_gp_get_W", "ibo_gp_info", "ibo_gp_last_fit_ms", "ibo_cov_matrix", "ibo_spd_solve", "ibo_spd_inverse", "ibo_posterior_batch",
             "ibo_acq_sweep", "ibo_acq_batch", "ibo_acq_grad_batch", "ibo_posterior_cov", "ibo_posterior_sample", "ibo_acq_sweep_incremental", "ibo_sweep_state_info", "ibo_sweep_state_levels", "ibo_last_sweep_kernel_ms", "ibo_direct_max", "ibo_cacq_sweep", "ibo_cacq_batch", "ibo_cacq_grad_batch", "ibo_cacq_direct_max", "ibo_ehvi_sweep", "ibo_ehvi_batch", "ibo_ehvi_grad_batch", "ibo_ehvi_direct_max", "ibo_ehvi_scan_ms", "ibo_mes_sweep", "ibo_mes_batch", "ibo_mes_grad_batch", "ibo_mes_direct_max", "ibo_mes_maxcdf", "ibo_mes_scan_ms", "ibo_kg_sweep", "ibo_kg_batch", "ibo_kg_direct_max", "ibo_kg_stage_ms", "ibo_qei_sweep", "ibo_qei_batch", "ibo_qei_direct_max", "ibo_qei_stage_ms", "ibo_paths_create", "ibo_paths_destroy", "ibo_paths_info", "ibo_paths_coef", "ibo_paths_sweep", "ibo_paths_batch", "ibo_paths_grad_batch", "ibo_paths_direct_max",
             "ibo_ggp_create", "ibo_ggp_destroy", "ibo_ggp_info", "ibo_ggp_fit", "ibo_ggp_get_R", "ibo_ggp_get_L", "ibo_ggp_acq_batch", "ibo_ggp_acq_sweep",
-            "ibo_ggp_direct_max", "ibo_ggp_stage_ms",
+            "ibo_ggp_direct_max", "ibo_ggp_stage_ms", "ibo_ggp_nlml_grad", "ibo_ggp_grad_stage_ms",
             "ibo_sgp_create", "ibo_sgp_destroy", "ibo_sgp_fit", "ibo_sgp_add", "ibo_sgp_acq_batch", "ibo_sgp_acq_sweep", "ibo_sgp_direct_max",
             "ibo_sgp_nlml", "ibo_sgp_get", "ibo_sgp_stage_ms", "ibo_sgp_nlml_grad", "ibo_sgp_grad_stage_ms", "ibo_direct_host", "ibo_nlml_grid", "ibo_nlml_grad", "ibo_gp_loo", "ibo_loo_grad",
             "ibo_comm_get_unique_id", "ibo_comm_init", "ibo_comm_destroy", "ibo_comm_count", "ibo_comm_argmax", "ibo_comm_allreduce_sum", "ibo_acq_sweep_exchange", "ibo_comm_barrier",

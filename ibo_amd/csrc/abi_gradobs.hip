@@ -169,7 +169,7 @@ extern "C" int ibo_ggp_fit(ibo_ggp_t *h, int ktype, int N, int D, const double *
     HIP_TRY(hipMemsetAsync(g->info.p, 0, sizeof(int), s));
     HIP_TRY(hipEventRecord(g->fit0, s));
     IBO_TRY(clock.mark(0));
-    KERNEL_TRY(launch_gradobs_assemble(kp, h->X.p, N, noise, h->gnoise.p, b.A, Np, s));
+    KERNEL_TRY(launch_gradobs_assemble(kp, h->X.p, N, 1.0 + noise, h->gnoise.p, b.A, Np, s));
     IBO_TRY(clock.mark(1));
     IBO_TRY(factor_invert(route, P, Np, b, s));
     std::swap(g->T, g->Wp);
@@ -197,7 +197,7 @@ extern "C" int ibo_ggp_get_R(ibo_ggp_t *h, double *R_host)
     hipStream_t s = h->g->stream;
     ScopedBuf<double> A;
     IBO_TRY(A.ensure((size_t)Np * Np));
-    KERNEL_TRY(launch_gradobs_assemble(h->kp, h->X.p, h->N, h->noise, h->gnoise.p, A.p, Np, s));
+    KERNEL_TRY(launch_gradobs_assemble(h->kp, h->X.p, h->N, 1.0 + h->noise, h->gnoise.p, A.p, Np, s));
     HIP_TRY(hipMemcpy2DAsync(R_host, sizeof(double) * h->P, A.p, sizeof(double) * Np, sizeof(double) * h->P, (size_t)h->P, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return IBO_OK;

@@ -1,7 +1,8 @@
-// abi_nlml.hip -- the marginal-likelihood side of the C ABI: the batched theta-grid, one value + gradient, and ibo_trim (which owns
-// their per-device workspaces).
+// abi_nlml.hip -- the marginal-likelihood side of the C ABI: the batched theta-grid, one value + gradient (of the plain model, of leave-one-out
+// and of the gradient-observation model) and ibo_trim (which owns their per-device workspaces).
 #include "abi_factor.h"
 #include "loo.h"
+#include "gradobs.h"
 
 // ------------------------------------------------------------------------ marginal-likelihood grid
 struct NlmlWorkspace {
@@ -24,8 +25,12 @@ struct GradWorkspace {
     // a learning loop calls with the same data and another theta dozens of times: what is on the device is kept (compared by content) and
     // the results come back through one pinned block behind one synchronisation
     std::vector<double> hostX, hostY;
-    double *pin = nullptr;                          // IBO_GRAD_MAX + 4 doubles: gradient, two scalars, the info word
+    double *pin = nullptr;                          // kGradPin doubles: the results, the info word at kGradPinInfo
+    // ibo_ggp_nlml_grad's data, in buffers of their own: the plain entries' resident X and Y are never touched
+    DevBuf<double> gX, gT, gN, gpart, gout;         // X, the interleaved targets (padded), gnoise, the contraction's partial sums, the results
+    std::vector<double> hostGX, hostGT, hostGN;
 };
+static const int kGradPin = 2 * IBO_GRAD_MAX + 8, kGradPinInfo = 2 * IBO_GRAD_MAX + 6;     // (ibo_ggp_nlml_grad: ngrad + 1 + D + 2 results)
 static GradWorkspace g_grad_ws[16];
 
 extern "C" int ibo_trim(int device)
@@ -44,7 +49,8 @@ extern "C" int ibo_trim(int device)
     gw.dal.release(); gw.da1.release(); gw.tmp.release(); gw.dpart.release(); gw.dout.release(); gw.dinfo.release();
     gw.dpiece.release(); gw.dtasks.release(); gw.dsums.release(); gw.plan_Np = 0; gw.tall.release(); gw.Pk2.release();
     gw.lpart.release(); gw.lout.release(); gw.lmu.release();
-    gw.hostX.clear(); gw.hostY.clear();              // (dX / dY went back to the pool: nothing of this data is on the device any more)
+    gw.gX.release(); gw.gT.release(); gw.gN.release(); gw.gpart.release(); gw.gout.release();
+    gw.hostX.clear(); gw.hostY.clear(); gw.hostGX.clear(); gw.hostGT.clear(); gw.hostGN.clear();      // (dX / dY went back to the pool: nothing of this data is on the device any more)
     if (gw.pin) { (void)hipHostFree(gw.pin); gw.pin = nullptr; }
     sgp_grad_trim(device);                           // (ibo_sgp_nlml_grad's private handle)
     pool_trim(device);
@@ -197,59 +203,48 @@ extern "C" int ibo_nlml_grid(int device, int ktype, int N, int D, const double *
     return IBO_OK;
 }
 
-// What ibo_nlml_grad and ibo_loo_grad share, on the device's one GradWorkspace (the caller holds its mutex): X and Y resident (compared by
-// content), the covariance matrix, the factorisation with W riding along, alpha, K^-1 = W^T W on the route the size selects -- queued on the
-// null stream behind ws.t0, nothing waited for.  scalars (optional, device): (y . alpha, sum log L_ii).  Kinv: where K^-1's lower 64 x 64 blocks are.
-static int grad_prepare(GradWorkspace &ws, const KParams &kp, int N, int D, const double *X, const double *Y, double noise, double *scalars,
-                        const double **Kinv_out)
+// The frame of one evaluation on the device's GradWorkspace (the caller holds its mutex): the buffers of an Np-row factorisation, the pinned
+// result block, the fit's route for Np rows and the operands factor_invert takes on it -- the matrix in dT (in super-panels: in the tall
+// buffer, with the ride-along's identity), the factor into dL, (L^-1)^T (or the doubling's scratch) in dKi, W into dW -- no packed copy:
+// nothing sweeps here; the two-level order is lent no packed-update store.  The caller sets b->eye_ready.
+static int grad_frame(GradWorkspace &ws, int Np, FactorRoute *route, FactorBufs *b)
 {
-    const int Np = round_up(N, 64);
     const size_t nn = (size_t)Np * Np;
     // workspace kept between calls (BFGS calls this dozens of times; five N^2 buffers allocated and freed per
     // call cost as much as the arithmetic); ibo_trim() releases it
-    DevBuf<double> &dX = ws.dX, &dY = ws.dY, &dL = ws.dL, &dW = ws.dW, &dT = ws.dT, &dKi = ws.dKi, &d64 = ws.d64,
-                   &dal = ws.dal, &da1 = ws.da1, &tmp = ws.tmp;
-    DevBuf<int> &dinfo = ws.dinfo;
-    IBO_TRY(dX.ensure((size_t)N * D)); IBO_TRY(dY.ensure(Np)); IBO_TRY(dL.ensure(nn)); IBO_TRY(dW.ensure(nn));
-    IBO_TRY(dT.ensure(nn)); IBO_TRY(dKi.ensure(nn)); IBO_TRY(d64.ensure(diag64_size(Np)));
-    IBO_TRY(dal.ensure(Np)); IBO_TRY(da1.ensure(Np)); IBO_TRY(tmp.ensure(alpha_scratch(Np)));
-    IBO_TRY(dinfo.ensure(1));
-    hipStream_t s = nullptr;
-    if (ws.hostX.size() != (size_t)N * D || memcmp(ws.hostX.data(), X, sizeof(double) * N * D) != 0) {
-        ws.hostX.clear();                            // (not valid while the copy is in flight or if it fails)
-        HIP_TRY(hipMemcpy(dX.p, X, sizeof(double) * N * D, hipMemcpyHostToDevice));
-        ws.hostX.assign(X, X + (size_t)N * D);
-    }
-    if (ws.hostY.size() != (size_t)Np || memcmp(ws.hostY.data(), Y, sizeof(double) * N) != 0) {
-        std::vector<double> yp(Np, 0.0);
-        for (int i = 0; i < N; i++) yp[i] = Y[i];
-        ws.hostY.clear();
-        HIP_TRY(hipMemcpy(dY.p, yp.data(), sizeof(double) * Np, hipMemcpyHostToDevice));
-        ws.hostY.swap(yp);
-    }
-    if (!ws.pin) HIP_TRY(hipHostMalloc((void **)&ws.pin, sizeof(double) * (IBO_GRAD_MAX + 4), hipHostMallocDefault));
-    // the fit's routes: the matrix in dT (in super-panels: in the tall buffer, with the ride-along's identity), the factor into dL, (L^-1)^T
-    // (or the doubling's scratch) in dKi, W into dW -- no packed copy: nothing sweeps here; the two-level order is lent no packed-update store
-    FactorRoute route;
-    IBO_TRY(factor_route(Np, FACTOR_FIT, &route));
-    const bool fused = route != ROUTE_TWO_LEVEL;
-    FactorBufs b = {};
-    b.A = dT.p; b.eye = dW.p;
-    if (route == ROUTE_RIDE_SUPER) {
+    IBO_TRY(ws.dL.ensure(nn)); IBO_TRY(ws.dW.ensure(nn)); IBO_TRY(ws.dT.ensure(nn)); IBO_TRY(ws.dKi.ensure(nn)); IBO_TRY(ws.d64.ensure(diag64_size(Np)));
+    IBO_TRY(ws.dal.ensure(Np)); IBO_TRY(ws.da1.ensure(Np)); IBO_TRY(ws.tmp.ensure(alpha_scratch(Np)));
+    IBO_TRY(ws.dinfo.ensure(1));
+    if (!ws.pin) HIP_TRY(hipHostMalloc((void **)&ws.pin, sizeof(double) * kGradPin, hipHostMallocDefault));
+    IBO_TRY(factor_route(Np, FACTOR_FIT, route));
+    *b = FactorBufs{};
+    b->A = ws.dT.p; b->eye = ws.dW.p;
+    if (*route == ROUTE_RIDE_SUPER) {
         IBO_TRY(ws.tall.ensure(2 * nn)); IBO_TRY(ws.Pk2.ensure(2 * nn));
-        b.A = ws.tall.p; b.eye = ws.tall.p + nn; b.Pk = ws.Pk2.p;
+        b->A = ws.tall.p; b->eye = ws.tall.p + nn; b->Pk = ws.Pk2.p;
     }
-    b.L = dL.p; b.Et = dKi.p; b.W = dW.p; b.d64 = d64.p; b.info = dinfo.p;
-    b.info_zero = true; b.eye_ready = fused;             // (launch_cov_fit's one pass)
+    b->L = ws.dL.p; b->Et = ws.dKi.p; b->W = ws.dW.p; b->d64 = ws.d64.p; b->info = ws.dinfo.p;
+    b->info_zero = true;
     if (!ws.t0) { HIP_TRY(hipEventCreate(&ws.t0)); HIP_TRY(hipEventCreate(&ws.t1)); }
-    HIP_TRY(hipEventRecord(ws.t0, s));
-    KERNEL_TRY(launch_cov_fit(kp, N, dX.p, D, IBO_DIAG_KERNEL_PLUS_NOISE, noise, b.A, Np, fused ? b.eye : nullptr, dinfo.p, s));
+    return IBO_OK;
+}
+
+// Behind the matrix in b.A (its info word cleared): the factorisation with W riding along, alpha = A^-1 y, the two scalars (optional, device:
+// (y . alpha, sum log L_ii)) and, if Kinv_out is given, K^-1 = W^T W on the route the size selects; *Kinv_out: where its lower 64 x 64 blocks
+// are.  Queued on the null stream, nothing waited for.  mid (optional): recorded between alpha / the scalars and the product.
+static int grad_factor(GradWorkspace &ws, FactorRoute route, const FactorBufs &b, int N, int Np, const double *y, double *scalars,
+                       const double **Kinv_out, hipEvent_t mid = nullptr)
+{
+    hipStream_t s = nullptr;
+    const bool fused = route != ROUTE_TWO_LEVEL;
+    DevBuf<double> &dL = ws.dL, &dW = ws.dW, &dT = ws.dT, &dKi = ws.dKi;
     // no look at the info word until everything is queued: a failed factorisation only turns the rest into NaNs
     IBO_TRY(factor_invert(route, N, Np, b, s));
-    KERNEL_TRY(launch_alpha(dW.p, N, Np, dY.p, tmp.p, dal.p, da1.p, s));
+    KERNEL_TRY(launch_alpha(dW.p, N, Np, y, ws.tmp.p, ws.dal.p, ws.da1.p, s));
+    if (scalars) KERNEL_TRY(launch_nlml_scalars(dL.p, Np, N, y, ws.dal.p, scalars, s));        // (y . alpha, sum log L_ii): L has been read for the last time
+    if (mid) HIP_TRY(hipEventRecord(mid, s));
+    if (!Kinv_out) return IBO_OK;
     // K^-1 = W^T W: with the ride-along, W^T is what the factorisation left in dKi -- no transpose; the result goes to dT, free by now
-    const double *Kinv = fused ? dT.p : dKi.p;
-    if (scalars) KERNEL_TRY(launch_nlml_scalars(dL.p, Np, N, dY.p, dal.p, scalars, s));        // (y . alpha, sum log L_ii): L has been read for the last time
     if (fused && Np >= kSyrk3From) {
         // from 1792 rows the product runs on the packed-operand kernel (128 x 128 tiles, A fragments straight from L2), its long K ranges in pieces
         // of 256 columns below 2560 rows, 512 below 4096, 1024 from there (measured: 0.692 -> 0.668 ms per evaluation at N = 1792, 0.809 -> 0.766 at
@@ -267,8 +262,39 @@ static int grad_prepare(GradWorkspace &ws, const KParams &kp, int N, int D, cons
         KERNEL_TRY(launch_syrk3(dKi.p, dL.p, dT.p, Np, ws.dtasks.p, ws.ntasks, ws.dsums.p, ws.nsums, ws.dpiece.p, s));
     } else if (fused) KERNEL_TRY(launch_wtw(dW.p, dKi.p, dT.p, Np, s, 1, 1));
     else KERNEL_TRY(launch_wtw(dW.p, dT.p, dKi.p, Np, s, 1));                      // (dT: scratch for W^T)
-    *Kinv_out = Kinv;
+    *Kinv_out = fused ? dT.p : dKi.p;
     return IBO_OK;
+}
+
+// What ibo_nlml_grad and ibo_loo_grad share, on the device's one GradWorkspace (the caller holds its mutex): X and Y resident (compared by
+// content), the covariance matrix, then grad_factor -- queued on the null stream behind ws.t0, nothing waited for.
+static int grad_prepare(GradWorkspace &ws, const KParams &kp, int N, int D, const double *X, const double *Y, double noise, double *scalars,
+                        const double **Kinv_out)
+{
+    const int Np = round_up(N, 64);
+    DevBuf<double> &dX = ws.dX, &dY = ws.dY;
+    IBO_TRY(dX.ensure((size_t)N * D)); IBO_TRY(dY.ensure(Np));
+    FactorRoute route;
+    FactorBufs b;
+    IBO_TRY(grad_frame(ws, Np, &route, &b));
+    hipStream_t s = nullptr;
+    if (ws.hostX.size() != (size_t)N * D || memcmp(ws.hostX.data(), X, sizeof(double) * N * D) != 0) {
+        ws.hostX.clear();                            // (not valid while the copy is in flight or if it fails)
+        HIP_TRY(hipMemcpy(dX.p, X, sizeof(double) * N * D, hipMemcpyHostToDevice));
+        ws.hostX.assign(X, X + (size_t)N * D);
+    }
+    if (ws.hostY.size() != (size_t)Np || memcmp(ws.hostY.data(), Y, sizeof(double) * N) != 0) {
+        std::vector<double> yp(Np, 0.0);
+        for (int i = 0; i < N; i++) yp[i] = Y[i];
+        ws.hostY.clear();
+        HIP_TRY(hipMemcpy(dY.p, yp.data(), sizeof(double) * Np, hipMemcpyHostToDevice));
+        ws.hostY.swap(yp);
+    }
+    const bool fused = route != ROUTE_TWO_LEVEL;
+    b.eye_ready = fused;                                 // (launch_cov_fit's one pass)
+    HIP_TRY(hipEventRecord(ws.t0, s));
+    KERNEL_TRY(launch_cov_fit(kp, N, dX.p, D, IBO_DIAG_KERNEL_PLUS_NOISE, noise, b.A, Np, fused ? b.eye : nullptr, ws.dinfo.p, s));
+    return grad_factor(ws, route, b, N, Np, dY.p, scalars, Kinv_out);
 }
 
 // modes / dims -> the derivative spec the contraction kernels take (ngrad = 0: none)
@@ -289,10 +315,10 @@ static int grad_finish(GradWorkspace &ws, int device, const double *res_dev, int
     hipStream_t s = nullptr;
     HIP_TRY(hipEventRecord(ws.t1, s));
     HIP_TRY(hipMemcpyAsync(ws.pin, res_dev, sizeof(double) * nres, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ws.pin + IBO_GRAD_MAX + 2, ws.dinfo.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ws.pin + kGradPinInfo, ws.dinfo.p, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     int h = 0;
-    memcpy(&h, ws.pin + IBO_GRAD_MAX + 2, sizeof(int));
+    memcpy(&h, ws.pin + kGradPinInfo, sizeof(int));
     { float ms = 0.f; if (hipEventElapsedTime(&ms, ws.t0, ws.t1) == hipSuccess) gpu_time_add(device, ms); }
     return factor_info_word(h, "covariance matrix", nullptr);
 }
@@ -358,5 +384,94 @@ extern "C" int ibo_loo_grad(int device, int ktype, int N, int D, const double *X
     if (s2_host) HIP_TRY(hipMemcpy(s2_host, ds2, sizeof(double) * N, hipMemcpyDeviceToHost));
     for (int i = 0; i < gs.nh; i++) grad_host[i] = ws.pin[i];
     *nloo_host = ws.pin[IBO_GRAD_MAX] + 0.5 * N * log(2.0 * M_PI);
+    return IBO_OK;
+}
+
+// ------------------------------------------------------------------------ the gradient-observation model's marginal likelihood
+static thread_local double t_ggp_grad_ms[IBO_GGP_GRAD_STAGES];
+
+// NL = t^T A_nl^-1 t / 2 + sum log L_ii + (P / 2) log 2 pi of the N (D + 1)-row model of values and slopes, and its exact gradient (ibo_abi.h):
+// the fit's assembly kernel with sf2 + noise on the value rows, grad_factor on the frame of P rows, then gradobs.hip's contraction.
+extern "C" int ibo_ggp_nlml_grad(int device, int ktype, int N, int D, const double *X, const double *Y, const double *G,
+                                 const double *hyper, int nhyper, double sf2, double noise, const double *gnoise,
+                                 int ngrad, const int *modes, const int *dims, double *nlml_host, double *grad_host, double *grad_noise_host)
+{
+    IBO_TRY(use_device(device));
+    if (!X || !Y || !G || !hyper || !gnoise || !nlml_host) return fail(IBO_ERR_ARG, "NULL argument");
+    if (N < 1) return fail(IBO_ERR_ARG, "N=%d", N);
+    if (grad_host && (!modes || !dims)) return fail(IBO_ERR_ARG, "modes / dims is NULL");
+    if (grad_host && (ngrad < 1 || ngrad > IBO_GRAD_MAX)) return fail(IBO_ERR_ARG, "ngrad=%d unsupported (1..%d)", ngrad, IBO_GRAD_MAX);
+    KParams kp;
+    IBO_TRY(make_kparams(ktype, D, hyper, nhyper, sf2, &kp));
+    if ((int64_t)N * (D + 1) > IBO_GGP_MAX_ROWS)
+        return fail(IBO_ERR_ARG, "N (D + 1) = %lld rows, at most %d", (long long)N * (D + 1), IBO_GGP_MAX_ROWS);
+    GradSpec gs;
+    IBO_TRY(grad_spec(grad_host ? ngrad : 0, modes, dims, D, &gs));
+    std::lock_guard<std::mutex> lk(g_dev_mu[device & 15]);      // (ibo_nlml_grad's workspace)
+    const int B = D + 1, P = N * B, Np = round_up(P, 64);
+    const bool want_grad = gs.nh > 0 || grad_noise_host;
+    const int nres = gs.nh + B + 2;                              // the derivatives, the 1 + D noise terms, (t . alpha, sum log L_ii)
+    GradWorkspace &ws = g_grad_ws[device & 15];
+    IBO_TRY(ws.gX.ensure((size_t)N * D)); IBO_TRY(ws.gT.ensure(Np)); IBO_TRY(ws.gN.ensure(D)); IBO_TRY(ws.gout.ensure(kGradPin));
+    if (want_grad) IBO_TRY(ws.gpart.ensure(gradobs_contract_scratch(N, D)));
+    FactorRoute route;
+    FactorBufs b;
+    IBO_TRY(grad_frame(ws, Np, &route, &b));
+    hipStream_t s = nullptr;
+    if (ws.hostGX.size() != (size_t)N * D || memcmp(ws.hostGX.data(), X, sizeof(double) * N * D) != 0) {
+        ws.hostGX.clear();                           // (not valid while the copy is in flight or if it fails)
+        HIP_TRY(hipMemcpy(ws.gX.p, X, sizeof(double) * N * D, hipMemcpyHostToDevice));
+        ws.hostGX.assign(X, X + (size_t)N * D);
+    }
+    {
+        std::vector<double> tp(Np, 0.0);             // [Y; G] interleaved point by point, zero in the pad
+        for (int i = 0; i < N; i++) {
+            tp[(size_t)i * B] = Y[i];
+            for (int d = 0; d < D; d++) tp[(size_t)i * B + 1 + d] = G[(size_t)i * D + d];
+        }
+        if (ws.hostGT.size() != tp.size() || memcmp(ws.hostGT.data(), tp.data(), sizeof(double) * Np) != 0) {
+            ws.hostGT.clear();
+            HIP_TRY(hipMemcpy(ws.gT.p, tp.data(), sizeof(double) * Np, hipMemcpyHostToDevice));
+            ws.hostGT.swap(tp);
+        }
+    }
+    if (ws.hostGN.size() != (size_t)D || memcmp(ws.hostGN.data(), gnoise, sizeof(double) * D) != 0) {
+        ws.hostGN.clear();
+        HIP_TRY(hipMemcpy(ws.gN.p, gnoise, sizeof(double) * D, hipMemcpyHostToDevice));
+        ws.hostGN.assign(gnoise, gnoise + D);
+    }
+    const bool timing = g_ggp_timing != 0;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    struct EvDrop { hipEvent_t *e; ~EvDrop() { for (int k = 0; k < 5; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } drop{ev};
+    if (timing)
+        for (int k = 0; k < 5; k++) HIP_TRY(hipEventCreate(&ev[k]));
+    b.eye_ready = false;
+    HIP_TRY(hipMemsetAsync(ws.dinfo.p, 0, sizeof(int), s));
+    HIP_TRY(hipEventRecord(ws.t0, s));
+    if (timing) HIP_TRY(hipEventRecord(ev[0], s));
+    KERNEL_TRY(launch_gradobs_assemble(kp, ws.gX.p, N, sf2 + noise, ws.gN.p, b.A, Np, s));
+    if (timing) HIP_TRY(hipEventRecord(ev[1], s));
+    const double *Kinv = nullptr;
+    double *res = ws.gout.p;
+    IBO_TRY(grad_factor(ws, route, b, P, Np, ws.gT.p, res + gs.nh + B, want_grad ? &Kinv : nullptr, ev[2]));
+    if (timing) HIP_TRY(hipEventRecord(ev[3], s));
+    if (want_grad) KERNEL_TRY(launch_gradobs_contract(kp, gs, ws.gX.p, N, Kinv, Np, ws.dal.p, noise, ws.gN.p, ws.gpart.p, res, s));
+    if (timing) HIP_TRY(hipEventRecord(ev[4], s));
+    const int rc = grad_finish(ws, device, res, nres);
+    if (timing)
+        for (int k = 0; k < 4; k++) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) t_ggp_grad_ms[k] += ms; }
+    IBO_TRY(rc);
+    const double *r = ws.pin;
+    for (int i = 0; i < gs.nh; i++) grad_host[i] = r[i];
+    if (grad_noise_host)
+        for (int e = 0; e < B; e++) grad_noise_host[e] = r[gs.nh + e];
+    *nlml_host = 0.5 * r[gs.nh + B] + r[gs.nh + B + 1] + 0.5 * P * log(2.0 * M_PI);
+    return IBO_OK;
+}
+
+extern "C" int ibo_ggp_grad_stage_ms(double *ms, int reset)
+{
+    if (ms) memcpy(ms, t_ggp_grad_ms, sizeof(t_ggp_grad_ms));
+    if (reset) memset(t_ggp_grad_ms, 0, sizeof(t_ggp_grad_ms));
     return IBO_OK;
 }

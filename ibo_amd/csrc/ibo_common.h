@@ -152,6 +152,18 @@ __device__ __forceinline__ d4_t mfma_f64(double a, double b, d4_t c)
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
 
+// the wave's 64 values summed in a fixed order without a trip through the LDS crossbar: four DPP steps inside the rows of 16 lanes (xor 1, xor 2,
+// half-row mirror, row mirror), then the four row sums, first to last (assemble.hip: nlml_grad_fast_kernel; gradobs.hip: gradobs_contract_kernel)
+__device__ __forceinline__ double wave_sum_rows(double v)
+{
+#define WS_STEP(ctrl) { const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, 0xf, 0xf, true), \
+                                  hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, 0xf, 0xf, true); v += __hiloint2double(hi, lo); }
+    WS_STEP(0xB1) WS_STEP(0x4E) WS_STEP(0x141) WS_STEP(0x140)
+#undef WS_STEP
+    auto row = [&](int l) { return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l)); };
+    return ((row(0) + row(16)) + row(32)) + row(48);
+}
+
 // RBF-network mean prior parameters (device pointers)
 struct PriorDev {
     int nb;

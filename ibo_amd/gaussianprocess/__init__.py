@@ -5,6 +5,7 @@ on the MI355X backend.
     GaussianProcess(kernel, X=None, Y=None, prior=None, noise=.1, gnoise=1e-4, G=None)
         .addData(X, Y, G=None)  .removeData(indices)  .posterior(x, getvar=True)  .posteriors(X)  .mu(x)  .negmu(x)
         .getYfromX(qx)  .done(x)   attributes X, Y, R, L, noise, kernel, prior, ...
+        with G=: .nlml()  .learn(nhyper=None, noise=False, gnoise=False, maxiter=30, bounds=None)   (the likelihood of values and slopes)
     PrefGaussianProcess(kernel, prefs=None, **kw)
         .addPreferences(prefs)  .addObservationPoint(x)   attributes preferences, C
 
@@ -91,7 +92,7 @@ class _DeviceGGP(object):
 
 
 _GRADIENT_WHY = ("the model is observed with gradients (G=): it has N (D + 1) rows of values and derivatives, and only posterior, "
-                 "posteriors, mu, negmu, R, L, EI / PI / UCB, acquisition.sweep and maximizeEI / PI / UCB are built for it")
+                 "posteriors, mu, negmu, R, L, nlml, learn, EI / PI / UCB, acquisition.sweep and maximizeEI / PI / UCB are built for it")
 
 
 class GaussianProcess(object):
@@ -179,6 +180,79 @@ class GaussianProcess(object):
         ptr = lambda k: _lib.dp(res[k]) if k in res else None
         _lib.check(_lib.lib.ibo_ggp_acq_batch(self._gdev.h, M, _lib.dp(Q), acq, float(parm), erf_mode, clamp_lo,
                                               float('nan') if ymax is None else float(ymax), ptr("mu"), ptr("s2"), ptr("acq")))
+        return res
+
+    def nlml(self):
+        """the negative log marginal likelihood of a model observed with gradients at its own kernel, noise and gnoise
+        (trainhyper.gradientLikelihood: the kernel's own signal variance on the value rows' diagonal).  A model of values alone has none of
+        its own: NotImplementedError naming trainhyper.marginalLikelihood."""
+        if self.G is None:
+            raise NotImplementedError("GaussianProcess.nlml is the likelihood of a model observed with gradients (G=); for values alone "
+                                      "call trainhyper.marginalLikelihood(kernel, X, Y, nhyper, noise=...)")
+        from . import trainhyper
+        return trainhyper.gradientLikelihood(self.kernel, self.X, self.Y, self.G, 0, noise=self.noise, gnoise=self.gnoise,
+                                             computeGradient=False)
+
+    def learn(self, nhyper=None, noise=False, gnoise=False, maxiter=30, bounds=None):
+        """minimise the marginal likelihood of a model observed with gradients over [log theta (the kernel's first nhyper
+        hyper-parameters; None: all), log noise (noise=True), log gnoise_1 .. log gnoise_D (gnoise=True)] by L-BFGS-B on
+        ibo_ggp_nlml_grad: every evaluation is one device call, a point where the matrix does not factor counts as +inf for the line
+        search.  bounds: L-BFGS-B's, one (lo, hi) per variable in that order, or None.  When the search ends at a finite value below the
+        one it started from -- also when it stopped for lack of iterations -- the kernel is rebuilt as kernel.__class__(exp(log theta)),
+        noise and gnoise are set and a NEW handle is fitted and swapped in; a failing fit leaves the model as it was.  Otherwise the
+        model is not touched.  Returns the scipy result with .start_value, .end_value and .applied.  A model of values alone:
+        NotImplementedError naming trainhyper.nlml."""
+        if self.G is None:
+            raise NotImplementedError("GaussianProcess.learn is built for a model observed with gradients (G=); for values alone minimise "
+                                      "trainhyper.nlml / dnlml (scipy.optimize.fmin_bfgs, as the reference does)")
+        from scipy.optimize import minimize
+        from . import trainhyper
+        cls = self.kernel.__class__
+        th0 = np.asarray(self.kernel.hyperparams, dtype=float)
+        nh = len(th0) if nhyper is None else int(nhyper)
+        if not 0 <= nh <= len(th0):
+            raise ValueError("kernel has %d hyperparameters, %d asked for" % (len(th0), nh))
+        D = self.X.shape[1]
+        gn0 = np.asarray(self.gnoise, dtype=float).reshape(-1)
+        gn0 = np.tile(gn0, D) if len(gn0) == 1 else gn0
+        x0 = np.r_[np.log(th0[:nh]), [np.log(float(self.noise))] if noise else [], np.log(gn0) if gnoise else []]
+        if len(x0) == 0:
+            raise ValueError("nothing to learn")
+
+        def unpack(x):
+            kern = cls(np.r_[np.exp(x[:nh]), th0[nh:]]) if nh else self.kernel
+            o = nh
+            nz = float(self.noise)
+            if noise:
+                nz = float(np.exp(x[o])); o += 1
+            return kern, nz, (np.exp(x[o:o + D]) if gnoise else gn0)
+
+        values = []
+
+        def fg(x):
+            kern, nz, gn = unpack(x)
+            try:
+                v, g, g_nz, g_gn = trainhyper.gradientLikelihood(kern, self.X, self.Y, self.G, nh, noise=nz, gnoise=gn, gradNoise=True)
+            except np.linalg.LinAlgError:
+                return np.inf, np.zeros(len(x))
+            values.append(v)
+            return v, np.r_[g, [g_nz] if noise else [], g_gn if gnoise else []]
+
+        res = minimize(fg, x0, jac=True, method='L-BFGS-B', bounds=bounds, options=dict(maxiter=int(maxiter)))
+        res.start_value = values[0] if values else float('nan')
+        res.end_value = float(res.fun)
+        res.evaluations = len(values)
+        res.applied = bool(values) and np.isfinite(res.end_value) and res.end_value < res.start_value
+        if not res.applied:
+            return res
+        kern, nz, gn = unpack(np.asarray(res.x, dtype=float))
+        keep = self.kernel, self.noise, self.gnoise
+        self.kernel, self.noise, self.gnoise = kern, nz, np.array(gn, dtype=float)
+        try:
+            self._fit_gradient(self.X, self.Y, self.G)      # (a new handle, swapped in only when the fit succeeded)
+        except Exception:
+            self.kernel, self.noise, self.gnoise = keep
+            raise
         return res
 
     # ------------------------------------------------------------------ device plumbing

@@ -8,13 +8,17 @@ Marginal likelihood of the GP hyper-parameters (ego/gaussianprocess/trainhyper.p
     nloo(loghyper, Kernel, X, Y, noise=1e-3)     dnloo(loghyper, Kernel, X, Y, noise=1e-3)
     sparseLikelihood(kernel, X, Y, Z, nhyper, noise, jitter=1e-6, kind='vfe', computeGradient=True, gradZ=True)      <- new: the sparse
         model's objective (FITC, DTC or Titsias' bound) with its gradient w.r.t. log theta, log noise and the inducing points
+    gradientLikelihood(kernel, X, Y, G, nhyper, noise=1e-3, gnoise=1e-4, computeGradient=True, gradNoise=False)      <- new: the likelihood
+        of a model observed with gradients (GaussianProcess(G=)), with its gradient w.r.t. log theta, log noise and log gnoise
+    ngnlml(loghyper, Kernel, X, Y, G, noise=1e-3, gnoise=1e-4)     dgnlml(loghyper, Kernel, X, Y, G, noise=1e-3, gnoise=1e-4)
 
 The value (K assembly, Cholesky, L^-1 Y, log det) is computed on the GPU by
 ibo_nlml_grid; value + gradient for one theta by ibo_nlml_grad (K^-1 = W^T W from the device
 factorisation, then one fused kernel contracts K^-1 - alpha alpha^T with every dK/dtheta_i,
 recomputed from X on the fly).  The leave-one-out objective (Rasmussen & Williams 5.4.2), its gradient and the leave-one-out
 predictions come from ibo_loo_grad: the same sequence up to K^-1, then T = K^-1 dK/dtheta_i on the MFMA unit.
-These three factor N x N; the sparse model's likelihood on m inducing points, O(N m^2), comes from ibo_sgp_nlml_grad.
+These three factor N x N; the sparse model's likelihood on m inducing points, O(N m^2), comes from ibo_sgp_nlml_grad, and the
+N (D + 1)-row likelihood of values and slopes from ibo_ggp_nlml_grad.
 """
 import numpy as np
 from numpy.linalg import LinAlgError
@@ -25,8 +29,8 @@ from .. import _lib
 def _no_gradient_data(G, what):
     """hyper-parameter learning is built for value observations: the likelihoods of an N (D + 1)-row gradient model are not"""
     if G is not None:
-        raise NotImplementedError("%s with gradient observations (G=): hyper-parameter learning on gradient data is not available -- "
-                                  "the likelihood kernels factor K(X, X) of the values alone" % what)
+        raise NotImplementedError("%s with gradient observations (G=): this likelihood factors K(X, X) of the values alone -- the "
+                                  "N (D + 1)-row model's own is trainhyper.gradientLikelihood (GaussianProcess.nlml / .learn)" % what)
 
 
 def _spec_rows(kernels):
@@ -221,3 +225,85 @@ def sparseLikelihood(kernel, X, Y, Z, nhyper, noise, jitter=1e-6, kind='vfe', co
     if not computeGradient:
         return v
     return v, g['hyper'], g['noise'], g.get('Z')
+
+
+# ---------------------------------------------------------------------------------------- the model observed with gradients
+def _gnoise_row(gnoise, D):
+    gn = np.asarray(gnoise, dtype=float).reshape(-1)
+    gn = _lib.f64(np.tile(gn, D) if len(gn) == 1 else gn)
+    if len(gn) != D:
+        raise ValueError("gnoise has %d entries, the data %d dimensions" % (len(gn), D))
+    return gn
+
+
+def gradientLikelihood(kernel, X, Y, G, nhyper, noise=1e-3, gnoise=1e-4, computeGradient=True, gradNoise=False):
+    """the negative log marginal likelihood of the N (D + 1)-row model of values Y and slopes G (GaussianProcess(kernel, X, Y, G=G)) with
+    A = C + diag(noise, gnoise_1 .. gnoise_D) per point, C the derivative covariance with the kernel's own diagonal (marginalLikelihood's
+    convention, covMatrix + noise I: for a signal variance other than 1 the fitted model's value rows hold 1 + noise instead), and with
+    computeGradient its exact partial derivatives: `value`, `(value, grad_loghyper)` or, with gradNoise, `(value, grad_loghyper,
+    grad_lognoise, grad_loggnoise)` -- w.r.t. the log of the kernel's first nhyper hyper-parameters, the log noise and the log of each
+    of the D gradient noises.  gnoise: one number or one per dimension.  One device call (ibo_ggp_nlml_grad).  LinAlgError when A is
+    not positive definite, ValueError for G.shape != X.shape."""
+    import ctypes
+    Xa = _lib.rows(X); Ya = _lib.f64(Y).reshape(-1)
+    Ga = _lib.f64(np.array(G, dtype=float, ndmin=2))
+    if Ga.shape != Xa.shape:
+        raise ValueError("G has shape %s, X has %s: one partial derivative per coordinate of every point" % (Ga.shape, Xa.shape))
+    assert len(Xa) == len(Ya)
+    N, D = Xa.shape
+    gn = _gnoise_row(gnoise, D)
+    ktype, hyper, sf2, _ = kernel._ibo_spec()
+    modes = dims = None
+    g = None
+    if computeGradient:
+        spec = kernel._ibo_grad_spec(D)[:nhyper]
+        if len(spec) < nhyper:
+            raise ValueError("kernel has %d hyperparameters, %d gradients requested" % (len(spec), nhyper))
+        modes = (ctypes.c_int * nhyper)(*[m for m, _ in spec])
+        dims = (ctypes.c_int * nhyper)(*[d for _, d in spec])
+        g = np.empty(nhyper)
+    gnz = np.empty(D + 1) if computeGradient and gradNoise else None
+    v = ctypes.c_double()
+    try:
+        _lib.check(_lib.lib.ibo_ggp_nlml_grad(_lib.default_device(), ktype, N, D, _lib.dp(Xa), _lib.dp(Ya), _lib.dp(Ga), _lib.dp(hyper),
+                                              len(hyper), sf2, float(noise), _lib.dp(gn), nhyper if computeGradient else 0, modes, dims,
+                                              ctypes.byref(v), None if g is None or nhyper == 0 else _lib.dp(g),      # (nhyper = 0: the noise terms alone)
+                                              None if gnz is None else _lib.dp(gnz)))
+    except _lib.NotPositiveDefinite:
+        raise LinAlgError("the gradient-observation matrix is not positive definite for hyperparameters %s" % (kernel.hyperparams,))
+    if not computeGradient:
+        return v.value
+    return (v.value, g, gnz[0], gnz[1:].copy()) if gradNoise else (v.value, g)
+
+
+_last_g = {"key": None, "value": None, "grad": None}      # (as _last: f(x) and f'(x) at one x cost one device call)
+
+
+def _g_value_and_grad(loghyper, kernel, X, Y, G, noise=1e-3, gnoise=1e-4):
+    loghyper = np.asarray(loghyper, dtype=float)
+    import hashlib
+    dig = hashlib.blake2b(_lib.rows(X).tobytes(), digest_size=16)
+    dig.update(_lib.f64(Y).tobytes())
+    dig.update(_lib.f64(G).tobytes())
+    key = (loghyper.tobytes(), kernel, dig.digest(), float(noise), _lib.f64(np.asarray(gnoise, dtype=float).reshape(-1)).tobytes())
+    if _last_g["key"] != key:
+        k = kernel(np.exp(loghyper))
+        _last_g["key"] = None
+        _last_g["value"], _last_g["grad"] = gradientLikelihood(k, X, Y, G, len(loghyper), noise=noise, gnoise=gnoise)
+        _last_g["key"] = key
+    return _last_g["value"], _last_g["grad"]
+
+
+def ngnlml(loghyper, kernel, X, Y, G, noise=1e-3, gnoise=1e-4):
+    """gradientLikelihood as a function of LOG hyper-parameters, for fmin_bfgs; 100 when not PD (as nlml)"""
+    try:
+        v = _g_value_and_grad(loghyper, kernel, X, Y, G, noise, gnoise)[0]
+    except LinAlgError as e:
+        print(e)
+        v = 100
+        print('returning ngnlml = 100')
+    return v
+
+
+def dgnlml(loghyper, kernel, X, Y, G, noise=1e-3, gnoise=1e-4):
+    return _g_value_and_grad(loghyper, kernel, X, Y, G, noise, gnoise)[1]

@@ -67,7 +67,9 @@ extern "C" {
                              * ibo_sgp_nlml, ibo_sgp_get, ibo_sgp_stage_ms (a sparse GP on inducing points, DTC / FITC, on a handle type of its own) and the
                              * options "sgp_chunk", "sgp_timing": added within 8, nothing else changed;
                              * + ibo_sgp_nlml_grad, ibo_sgp_grad_stage_ms (the sparse marginal likelihood's gradient with respect to the log
-                             * hyper-parameters, the log noise and the inducing points, for fitc / dtc / vfe): added within 8, nothing else changed */
+                             * hyper-parameters, the log noise and the inducing points, for fitc / dtc / vfe): added within 8, nothing else changed;
+                             * + ibo_ggp_nlml_grad, ibo_ggp_grad_stage_ms (the marginal likelihood of a GP observed with gradients and its gradient with
+                             * respect to the log hyper-parameters, the log noise and the log gradient noises): added within 8, nothing else changed */
 
 /* status codes */
 #define IBO_OK              0
@@ -966,6 +968,42 @@ int ibo_ggp_direct_max(ibo_ggp_t *h, int D, const double *lb, const double *ub, 
  * [3] the row kernel, [4] unused (0), [5] the acquisition, [6] factor-and-invert, [7] the alpha vectors. */
 #define IBO_GGP_STAGES 8
 int ibo_ggp_stage_ms(double *ms, int reset);
+/*
+ * The negative log marginal likelihood of the gradient-observation model and its gradient for ONE theta, stateless like ibo_nlml_grad (and on
+ * the same per-device workspace, under the same mutex; X and the interleaved targets stay resident while their content is unchanged, in
+ * buffers of their own: ibo_nlml_grad / ibo_loo_grad called before and after return the same bits).
+ *   t = [Y; G] interleaved point-major, P = N (D + 1);  A_nl = C + diag(noise, gnoise_1 .. gnoise_D) per point, C the derivative covariance
+ *   of the blocks above with ITS OWN diagonal: sf2 on a value row (ibo_nlml_grad's convention, covMatrix + noise I -- ibo_ggp_fit puts
+ *   1 + noise there whatever sf2 is; for sf2 = 1 A_nl is ibo_ggp_fit's matrix bit for bit), g1(0) w_d on derivative row d.
+ *   NL = t^T A^-1 t / 2 + sum_i log L_ii + (P / 2) log 2 pi;   dNL/dlog theta_h = sum_ab (A^-1 - alpha alpha^T)_ab (dA/dlog theta_h)_ab / 2,
+ *   the exact derivative of NL.
+ * modes / dims are numbered as ibo_nlml_grad's -- 0: the SE-ARD length scale of dimension dims[h]; 1, 3, 4: the one length scale of an
+ * SE-iso, Matern-3/2, Matern-5/2 kernel; 2: the signal magnitude (dA = 2 C, diagonal included) -- but every mode here is the derivative of A
+ * itself.  Modes 3 and 4 are NOT the reference's Kernel.derivative matrices that ibo_nlml_grad reproduces (quirks of value-only kernels,
+ * an unscaled r in mode 3): with z = sum_d w_d u_d^2, t_d = w_d u_d, d = d/dlog theta,
+ *   mode 0     dz = -2 w_h u_h^2, dt_d = -2 t_d [d = h], dw_d = -2 w_d [d = h], dk = -(g1/2) dz, dg1 = -(g2/2) dz, dg2 = -(k/2) dz
+ *   1, 3, 4    dz = -2 z, dt_d = -2 t_d, dw_d = -2 w_d, dk = g1 z, dg1 = g2 z, dg2 (always times t_d t_e, 0 at r = 0) = k z (SE),
+ *              9 sf2 e^-r (1 + r) / r (Matern-3/2), 25/3 sf2 e^-r r (Matern-5/2)
+ *   d(value, d/dx'_e) = dg1 t_e + g1 dt_e, its mirror image the negative; d(d, e) = (dg1 w_d + g1 dw_d) [d = e] - dg2 t_d t_e - g2 (dt_d t_e + t_d dt_e)
+ * grad_noise_host (1 + D, optional): dNL/dlog noise = noise sum_{value rows} d / 2 and dNL/dlog gnoise_e = gnoise_e sum_{rows of d/dx_e} d / 2,
+ * d = diag(A^-1) - alpha o alpha.  grad_host (ngrad) may be NULL: value only, when grad_noise_host is NULL too nothing but the factorisation runs
+ * and *nlml_host has the same bits.
+ * Launches: the assembly of A_nl into the frame of the fit's route for P rows, factor-and-invert, alpha, the two scalars, K^-1 = W^T W as
+ * ibo_nlml_grad forms it (64 x 64 tiles below 1792 rows, the packed-operand product from there), one contraction kernel -- a workgroup per
+ * tile of 16 x 16 point pairs, O(D^2) per pair once and O(1) per derivative -- and a fixed-order sum of the per-tile partial sums; one pinned
+ * read-back behind one synchronisation.  No atomics: two calls give the same bits, and a component has the same bits alone, in a full list
+ * and in a permuted one.
+ * Limits: N (D + 1) <= IBO_GGP_MAX_ROWS, D in 1 .. 64, 1 <= ngrad <= 65 when grad_host is given.
+ * Errors: IBO_ERR_NO_DEVICE first; IBO_ERR_ARG for NULLs, sizes and a bad derivative spec; IBO_ERR_NOT_PD leaves the outputs untouched.
+ */
+int ibo_ggp_nlml_grad(int device, int ktype, int N, int D, const double *X_host, const double *Y_host, const double *G_host,
+                      const double *hyper_host, int nhyper, double sf2, double noise, const double *gnoise_host /* D */,
+                      int ngrad, const int *modes, const int *dims,
+                      double *nlml_host, double *grad_host /* ngrad, or NULL: value only */, double *grad_noise_host /* 1 + D, or NULL */);
+/* under ibo_set_option("ggp_timing", 1), accumulated per thread: [0] the assembly of A_nl, [1] factor-and-invert with alpha and the two
+ * scalars, [2] K^-1 = W^T W, [3] the contraction and its sum. */
+#define IBO_GGP_GRAD_STAGES 4
+int ibo_ggp_grad_stage_ms(double *ms, int reset);
 
 /* ---------------------------------------------------------------- sparse (inducing-point) GP */
 /*
