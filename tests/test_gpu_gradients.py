@@ -4,7 +4,8 @@ maximizeEI / PI / UCB(polish=True).
 
 The yardstick is tests/grad_reference.py, the formulas restated in NumPy/SciPy float64 (R with the diagonal 1 + noise,
 cho_solve for the alphas and u = R^-1 k*) and pinned to the oracle by tests/test_grad_reference.py.  Tolerance: |err_d| <=
-1e-9 sum_i |dk*_i c_i| + 1e-13 per entry, on models with cond(R) far below 1e8 (noise 0.1).  Central differences of
+1e-9 sum_i |dk*_i c_i| + 1e-13 per entry, on models with cond(R) far below 1e8 (noise 0.1; tests/test_gpu_conditioning.py
+holds the same gradients to long-double truth at cond(R) 1e6 .. 1e8).  Central differences of
 ibo_acq_batch catch what a restatement sharing a mistake would miss (sign, scale, the k* variance).
 """
 import ctypes
