@@ -26,6 +26,15 @@ preference GP (entropy.py): MaxValueEntropy, maxValueSamples, sweepMES, maximize
 The default maximize* path is the reference's cdirectGP -> acqmaxGP -> DIRECT
 (ego/acquisition/__init__.py:307-447, cpp/optimizeGP.cpp:262-349) with the tree
 on the host and every batch of sample points evaluated by the HIP sweep kernel.
+
+Every kind of model -- plain, observed with gradients (G=), sparse -- goes through the same sweep, cdirectGP and _maximize: the model's
+handle owner (model._owner(), gaussianprocess._Device) knows its kind and names the entry,
+
+    kind 'gp'   ibo_acq_batch       ibo_acq_sweep (_incremental, _exchange)   ibo_direct_max       + ibo_gp_set_kstar_sf2, ibo_last_sweep_kernel_ms
+    kind 'ggp'  ibo_ggp_acq_batch   ibo_ggp_acq_sweep                         ibo_ggp_direct_max
+    kind 'sgp'  ibo_sgp_acq_batch   ibo_sgp_acq_sweep                         ibo_sgp_direct_max
+
+and what a kind refuses of sweep() is the table _SWEEP_REFUSES.
 """
 import ctypes
 
@@ -36,6 +45,8 @@ from ..gaussianprocess import GaussianProcess, PrefGaussianProcess, CDF, PDF    
 from ..gaussianprocess.sparse import SparseGaussianProcess
 from ..utils.optimize import direct, cdirect
 from ..utils.latinhypercube import lhcSample                                        # noqa: F401
+from . import _args
+from ._args import POLISH_MAXITER                                                 # noqa: F401  (the polish step itself: _args._polish_step)
 
 _ACQ = {'ei': _lib.ACQ_EI, 'pi': _lib.ACQ_PI, 'ucb': _lib.ACQ_UCB}
 
@@ -65,7 +76,18 @@ def _acq_gradient(GP, X, acq, parm, ymax):
     return val, grad
 
 
-class UCB(object):
+class _ModelAcquisition(_args._HostPointAcquisition):
+    """what EI, PI and UCB share (f, negf, values, gradient, negf_grad) over the subclass's _spec(grad) -> (acq code, parm, ymax):
+    Python-class semantics, NR erf and the clamp [1e-7, 10]"""
+
+    def _call(self, X, grad):
+        code, parm, ymax = self._spec(grad)
+        if grad:
+            return _acq_gradient(self.GP, X, code, parm, ymax)
+        return self.GP._eval(X, code, parm, _lib.ERF_NR, _lib.CLAMP_PY, ("acq",), ymax=ymax)["acq"]
+
+
+class UCB(_ModelAcquisition):
     """upper confidence bound; note sqrt(scale * sBeta) with sBeta already a square
     root -- the class and the native path disagree in the reference and both are
     kept (ego/acquisition/__init__.py:60-71 vs :319)"""
@@ -77,24 +99,11 @@ class UCB(object):
         t = len(self.GP.Y) + 1
         self.sBeta = np.sqrt(2.0 * np.log(t ** (NA // 2 + 2) * np.pi ** 2 / (3.0 * delta)))
 
-    def negf(self, x):
-        r = self.GP._eval(x, _lib.ACQ_UCB, np.sqrt(self.scale * self.sBeta), _lib.ERF_NR, _lib.CLAMP_PY, ("acq",))
-        return -r["acq"][0]
-
-    def f(self, x):
-        return -self.negf(x)
-
-    def gradient(self, X):
-        """(values, gradients (M, D)) at the points X, the conventions of negf"""
-        return _acq_gradient(self.GP, X, _lib.ACQ_UCB, np.sqrt(self.scale * self.sBeta), np.max(self.GP.Y))
-
-    def negf_grad(self, x):
-        """(negf(x), -grad f(x)): the objective and gradient scipy.optimize.minimize(jac=True) asks for"""
-        v, g = self.gradient(x)
-        return -v[0], -g[0]
+    def _spec(self, grad):                           # (the value takes no incumbent; the gradient entry is handed one all the same)
+        return _lib.ACQ_UCB, np.sqrt(self.scale * self.sBeta), np.max(self.GP.Y) if grad else None
 
 
-class PI(object):
+class PI(_ModelAcquisition):
     """probability of improvement (:100-114); NR-erf CDF as the Python reference"""
 
     def __init__(self, GP, xi=.01, **kwargs):
@@ -103,25 +112,12 @@ class PI(object):
         self.xi = xi
         self.Z = np.max(self.GP.Y) + xi
 
-    def negf(self, x):
-        r = self.GP._eval(x, _lib.ACQ_PI, self.xi, _lib.ERF_NR, _lib.CLAMP_PY, ("acq",), ymax=self.Z - self.xi)
-        return -r["acq"][0]
-
-    def f(self, x):
-        return -self.negf(x)
-
-    def gradient(self, X):
-        """(values, gradients (M, D)) at the points X, the conventions of negf"""
-        return _acq_gradient(self.GP, X, _lib.ACQ_PI, self.xi, self.Z - self.xi)
-
-    def negf_grad(self, x):
-        """(negf(x), -grad f(x)): the objective and gradient scipy.optimize.minimize(jac=True) asks for"""
-        v, g = self.gradient(x)
-        return -v[0], -g[0]
+    def _spec(self, grad):
+        return _lib.ACQ_PI, self.xi, self.Z - self.xi
 
 
-class EI(object):
-    """expected improvement (:138-169); NR-erf CDF/PDF as the Python reference"""
+class EI(_ModelAcquisition):
+    """expected improvement (:138-169); NR-erf CDF/PDF as the Python reference.  .values(X): EI at many points at once (one GPU launch)"""
 
     def __init__(self, GP, xi=.01, **kwargs):
         super(EI, self).__init__()
@@ -131,25 +127,8 @@ class EI(object):
         assert np.isscalar(self.ymax)
         assert np.isscalar(self.xi)
 
-    def negf(self, x):
-        r = self.GP._eval(x, _lib.ACQ_EI, self.xi, _lib.ERF_NR, _lib.CLAMP_PY, ("acq",), ymax=self.ymax)
-        return -r["acq"][0]
-
-    def f(self, x):
-        return -self.negf(x)
-
-    def gradient(self, X):
-        """(values, gradients (M, D)) at the points X, the conventions of negf"""
-        return _acq_gradient(self.GP, X, _lib.ACQ_EI, self.xi, self.ymax)
-
-    def negf_grad(self, x):
-        """(negf(x), -grad f(x)): the objective and gradient scipy.optimize.minimize(jac=True) asks for"""
-        v, g = self.gradient(x)
-        return -v[0], -g[0]
-
-    def values(self, X):
-        """EI at many points at once (one GPU launch)"""
-        return self.GP._eval(X, _lib.ACQ_EI, self.xi, _lib.ERF_NR, _lib.CLAMP_PY, ("acq",), ymax=self.ymax)["acq"]
+    def _spec(self, grad):
+        return _lib.ACQ_EI, self.xi, self.ymax
 
 
 def _ucb_parm(model, bounds, delta, scale):
@@ -160,67 +139,56 @@ def _ucb_parm(model, bounds, delta, scale):
     return float(np.sqrt(scale * 2.0 * np.log(t ** (NA // 2 + 2) * np.pi ** 2 / (3.0 * delta))))
 
 
+def _default_parm(model, acq, nd, native, xi, delta, scale):
+    """the parameter an acquisition takes where the caller names none: xi for EI and PI; for UCB in nd dimensions the sigma multiplier of
+    the native path (_ucb_parm) or, native=False, the UCB class's"""
+    if acq != 'ucb':
+        return xi
+    if native:
+        return _ucb_parm(model, [None] * nd, delta, scale)
+    return float(np.sqrt(scale * UCB(model, nd, delta, scale).sBeta))
+
+
 def cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc=None, xi=-1, beta=-1, scale=-1, delta=-1, compat=True,
               return_samples=False, **kwargs):
     """cdirectGP (ego/acquisition/__init__.py:307-468), same name, positional order and defaults (`beta` is accepted and
     unused, as in the reference): same enum mapping and `parm`, then DIRECT on the GPU objective.  The model is already
     factored on the device, so the per-call linalg.inv(R) of the reference disappears.  `compat` / `return_samples` are
-    additions (the dimension-0 stall switch, the sample count)."""
-    if acqfunc == 'ei' or acqfunc == 'pi':
-        parm = xi
-    elif acqfunc == 'ucb':
-        parm = _ucb_parm(model, bounds, delta, scale)
-    else:
+    additions (the dimension-0 stall switch, the sample count).
+    Every kind of model takes the direct_max entry of its handle with libm erf and the native clamp; the plain kind runs it under
+    libego's k* signal variance, a model observed with gradients and a sparse one under their own throughout (libego has neither to be
+    compatible with)."""
+    if acqfunc not in _ACQ:
         raise NotImplementedError('unknown acquisition function %s' % acqfunc)
+    parm = _default_parm(model, acqfunc, len(bounds), True, xi, delta, scale)
     if len(model.X) == 0:
         raise ValueError("model has no data")
-    _, _, sf2_py, sf2_native = model.kernel._ibo_spec()
     lb = _lib.f64([b[0] for b in bounds]); ub = _lib.f64([b[1] for b in bounds])
     D = len(lb)
-    if isinstance(model, SparseGaussianProcess):
-        # a sparse model: the same DIRECT on ibo_sgp_direct_max, the model's own signal variance throughout
-        res = model._direct(lb, ub, _ACQ[acqfunc], parm, maxiter, maxtime, maxsample, compat)
-        return res if return_samples else res[:2]
+    plain = model._kind == 'gp'
+    if plain:
+        model._handle()
+        model._push_prior()
+    dev = model._owner()
     opt = ctypes.c_double(); optx = np.empty(D); ns = ctypes.c_int64()
-    if model.G is not None:
-        # a model observed with gradients: the same DIRECT on ibo_ggp_direct_max, libm erf and the native clamp as here, but the
-        # model's own signal variance throughout (libego has no gradient models to be compatible with)
-        _lib.check(_lib.lib.ibo_ggp_direct_max(model._gdev.h, D, _lib.dp(lb), _lib.dp(ub), _ACQ[acqfunc], float(parm), _lib.ERF_LIBM,
-                                               _lib.CLAMP_NATIVE, int(maxiter), int(maxtime), int(maxsample), 1 if compat else 0,
-                                               ctypes.byref(opt), _lib.dp(optx), ctypes.byref(ns)))
-        return (opt.value, optx, ns.value) if return_samples else (opt.value, optx)
-    h = model._handle()
-    model._push_prior()
-    _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(h, sf2_native))
-    try:
-        _lib.check(_lib.lib.ibo_direct_max(h, D, _lib.dp(lb), _lib.dp(ub), _ACQ[acqfunc], float(parm),
-                                           _lib.ERF_LIBM, _lib.CLAMP_NATIVE, int(maxiter), int(maxtime),
-                                           int(maxsample), 1 if compat else 0, ctypes.byref(opt), _lib.dp(optx),
-                                           ctypes.byref(ns)))
-    finally:
-        _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(h, sf2_py))
-    if return_samples:
-        return opt.value, optx, ns.value
-    return opt.value, optx
+    with _args._kstar_native([model], plain):
+        _lib.check(dev.entry("direct_max")(dev.h, D, _lib.dp(lb), _lib.dp(ub), _ACQ[acqfunc], float(parm), _lib.ERF_LIBM,
+                                           _lib.CLAMP_NATIVE, int(maxiter), int(maxtime), int(maxsample), 1 if compat else 0,
+                                           ctypes.byref(opt), _lib.dp(optx), ctypes.byref(ns)))
+    return (opt.value, optx, ns.value) if return_samples else (opt.value, optx)
 
 
 gpuDirectGP = cdirectGP          # the name earlier rounds of this package used
-
-
-from ._args import POLISH_MAXITER                                                 # noqa: E402,F401  (the polish step itself: _args._polish_step)
 
 
 def _polish(model, bounds, acqfunc, parm, opt, optx):
     """finish DIRECT's point with L-BFGS-B on the objective DIRECT maximised (libego's k* variance, libm erf, clamp
     [1e-8, 10], the same parm; one ibo_acq_grad_batch call per evaluation), bounded to the box and at most POLISH_MAXITER
     iterations.  The end point is re-evaluated with ibo_acq_batch and returned only if it is strictly better than DIRECT's."""
-    from . import _args
-    model._no_gradient("polish=True")
     lb = _lib.f64([b[0] for b in bounds]); ub = _lib.f64([b[1] for b in bounds])
     D = len(lb)
     code = _ACQ[acqfunc]
-    _, _, sf2_py, sf2_native = model.kernel._ibo_spec()
-    h = model._handle()
+    h = model._handle()                              # (refuses the kinds without a gradient entry, as _maximize did before DIRECT ran)
     model._push_prior()
     v, g = np.empty(1), np.empty((1, D))
 
@@ -235,65 +203,47 @@ def _polish(model, bounds, acqfunc, parm, opt, optx):
                                           float('nan'), None, None, _lib.dp(v)))
         return v[0]
 
-    _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(h, sf2_native))
-    try:
+    with _args._kstar_native([model]):
         return _args._polish_step(fg, value_at, lb, ub, opt, optx)
-    finally:
-        _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(h, sf2_py))
+
+
+def _maximize(acqfunc, model, bounds, useCDIRECT, maxiter, maxtime, maxsample, polish, kwargs, **parms):
+    """maximizeEI / PI / UCB; parms: the acquisition's own (xi=, or delta= and scale=)"""
+    kwargs = dict(parms, **kwargs)
+    if not useCDIRECT:
+        print('using DIRECT')
+        # (the reference forgets to forward the budgets in maximizeUCB (:86) and raises; they are forwarded)
+        a = UCB(model, len(bounds), **kwargs) if acqfunc == 'ucb' else {'ei': EI, 'pi': PI}[acqfunc](model, **kwargs)
+        opt, optx = direct(a.negf, bounds, maxiter=maxiter, maxtime=maxtime, maxsample=maxsample)
+        return -opt, optx
+    if isinstance(model, (GaussianProcess, SparseGaussianProcess)):
+        if polish:
+            model._no_gradient("maximize%s(polish=True)" % acqfunc.upper())
+        opt, optx = cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc=acqfunc, **kwargs)
+        if polish:
+            return _polish(model, bounds, acqfunc, _ucb_parm(model, bounds, **parms) if acqfunc == 'ucb' else parms['xi'], opt, optx)
+        return opt, optx
+    raise ValueError
 
 
 def maximizeUCB(model, bounds, delta=0.1, scale=0.2, useCDIRECT=True, maxiter=50, maxtime=30, maxsample=10000,
                 polish=False, **kwargs):
     """maximise the GP-UCB of [Srinivas 2009] (:78-96); polish=True: see _polish"""
-    if not useCDIRECT:
-        print('using DIRECT')
-        ucb = UCB(model, len(bounds), delta=delta, scale=scale, **kwargs)
-        # the reference forgets to forward the budgets here (:86) and raises; they are forwarded
-        opt, optx = direct(ucb.negf, bounds, maxiter=maxiter, maxtime=maxtime, maxsample=maxsample)
-        return -opt, optx
-    if isinstance(model, (GaussianProcess, SparseGaussianProcess)):
-        if polish:
-            model._no_gradient("maximizeUCB(polish=True)")
-        opt, optx = cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='ucb', delta=delta, scale=scale,
-                              **kwargs)
-        if polish:
-            return _polish(model, bounds, 'ucb', _ucb_parm(model, bounds, delta, scale), opt, optx)
-        return opt, optx
-    raise ValueError
+    return _maximize('ucb', model, bounds, useCDIRECT, maxiter, maxtime, maxsample, polish, kwargs, delta=delta, scale=scale)
 
 
 def maximizePI(model, bounds, xi=0.01, maxiter=50, maxtime=30, maxsample=10000, useCDIRECT=True, polish=False, **kwargs):
     """maximise the probability of improvement [Lizotte 2008] (:117-134); polish=True: see _polish"""
-    if not useCDIRECT:
-        print('using DIRECT')
-        pi = PI(model, xi, **kwargs)
-        opt, optx = direct(pi.negf, bounds, maxiter=maxiter, maxtime=maxtime, maxsample=maxsample)
-        return -opt, optx
-    if isinstance(model, (GaussianProcess, SparseGaussianProcess)):
-        if polish:
-            model._no_gradient("maximizePI(polish=True)")
-        opt, optx = cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='pi', xi=xi, **kwargs)
-        if polish:
-            return _polish(model, bounds, 'pi', xi, opt, optx)
-        return opt, optx
-    raise ValueError
+    return _maximize('pi', model, bounds, useCDIRECT, maxiter, maxtime, maxsample, polish, kwargs, xi=xi)
 
 
 def maximizeEI(model, bounds, useCDIRECT=True, xi=0.01, maxiter=50, maxtime=30, maxsample=10000, polish=False, **kwargs):
     """maximise expected improvement (:174-197); polish=True: see _polish"""
-    if not useCDIRECT:
-        print('using DIRECT')
-        ei = EI(model, xi, **kwargs)
-        opt, optx = direct(ei.negf, bounds, maxiter=maxiter, maxtime=maxtime, maxsample=maxsample)
-        return -opt, optx
-    if isinstance(model, (GaussianProcess, SparseGaussianProcess)):
-        if polish:
-            model._no_gradient("maximizeEI(polish=True)")
-        opt, optx = cdirectGP(model, bounds, maxiter, maxtime, maxsample, acqfunc='ei', xi=xi, **kwargs)
-        if polish:
-            return _polish(model, bounds, 'ei', xi, opt, optx)
-        return opt, optx
-    raise ValueError
+    return _maximize('ei', model, bounds, useCDIRECT, maxiter, maxtime, maxsample, polish, kwargs, xi=xi)
+
+
+_SWEEP_REFUSES = {'gp': (), 'ggp': ('exclude', 'incremental', 'exchange'), 'sgp': ('incremental', 'exchange')}
+_SWEEP_KERNEL = {'ggp': "gradobs row pipeline", 'sgp': "sparse two-frame sweep"}      # (the plain kind's handle names its own)
 
 
 def sweep(model, candidates, acq='ei', xi=0.01, delta=0.1, scale=0.2, parm=None, native=True, ymax=None,
@@ -319,111 +269,55 @@ def sweep(model, candidates, acq='ei', xi=0.01, delta=0.1, scale=0.2, parm=None,
     A sparse model (SparseGaussianProcess) takes ibo_sgp_acq_sweep: the same, exclude= included; NotImplementedError for incremental= and
     exchange=.
     """
-    if isinstance(model, SparseGaussianProcess):
-        return _sweep_sparse(model, candidates, acq, xi, delta, scale, parm, native, ymax, exclude, exclude_radius, index_base, outputs, NA,
-                             incremental, exchange)
-    if model.G is not None:
-        return _sweep_gradient(model, candidates, acq, xi, delta, scale, parm, native, ymax, exclude, index_base, outputs, NA,
-                               incremental, exchange)
+    kind = model._kind
+    given = dict(exclude=exclude is not None and len(exclude) > 0, incremental=incremental, exchange=exchange is not None)
+    for name in _SWEEP_REFUSES[kind]:
+        if given[name]:
+            model._no_gradient("sweep(%s=)" % name)
+    plain = kind == 'gp'
+    dev = model._owner()
     if isinstance(candidates, _lib.DeviceArray):
         cand = candidates
     else:
-        cand = _lib.DeviceArray.from_host(np.atleast_2d(candidates), model._dev.device)
+        cand = _lib.DeviceArray.from_host(np.atleast_2d(candidates), dev.device)
         incremental = False
     M = cand.shape[0]
-    code = _ACQ[acq]
     if parm is None:
-        if acq == 'ucb':
-            nd = NA if NA is not None else cand.shape[1]
-            parm = _ucb_parm(model, [None] * nd, delta, scale) if native else \
-                float(np.sqrt(scale * UCB(model, nd, delta, scale).sBeta))
-        else:
-            parm = xi
-    _, _, sf2_py, sf2_native = model.kernel._ibo_spec()
-    h = model._handle()
-    model._push_prior()
-    outs = {k: _lib.DeviceArray((M,), model._dev.device) for k in outputs}
+        parm = _default_parm(model, acq, NA if NA is not None else cand.shape[1], native, xi, delta, scale)
+    if plain:                                        # its handle (made now when there is none yet) and its mean prior
+        model._handle()
+        model._push_prior()
+        dev = model._dev
+    outs = {k: _lib.DeviceArray((M,), dev.device) for k in outputs}
     ex = None if exclude is None or len(exclude) == 0 else _lib.f64(np.atleast_2d(exclude))
     bv = ctypes.c_double(); bi = ctypes.c_int64()
-    if native:
-        _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(h, sf2_native))
+    lead = (M, cand.ptr, _ACQ[acq], float(parm), _lib.ERF_LIBM if native else _lib.ERF_NR, _lib.CLAMP_NATIVE if native else _lib.CLAMP_PY,
+            float('nan') if ymax is None else float(ymax))
+    if kind != 'ggp':                                # (ibo_ggp_acq_sweep has no exclusion arguments)
+        lead += (0 if ex is None else len(ex), None if ex is None else _lib.dp(ex), float(exclude_radius))
+    lead += (int(index_base),)
+    best = (ctypes.byref(bv), ctypes.byref(bi))
     glob = None
-    try:
+    t0 = None if plain else _lib.gpu_time_ms(dev.device)
+    with _args._kstar_native([model], plain and native):
         if exchange is not None:
             if outputs:
                 raise ValueError("per-candidate outputs are not available together with exchange=")
             gv = ctypes.c_double(); gi = ctypes.c_int64(); gr = ctypes.c_int(); gx = np.zeros(cand.shape[1])
-            _lib.check(_lib.lib.ibo_acq_sweep_exchange(
-                h, exchange.h, 1 if incremental else 0, M, cand.ptr, code, float(parm), _lib.ERF_LIBM if native else _lib.ERF_NR,
-                _lib.CLAMP_NATIVE if native else _lib.CLAMP_PY, float('nan') if ymax is None else float(ymax),
-                0 if ex is None else len(ex), None if ex is None else _lib.dp(ex), float(exclude_radius), int(index_base),
-                ctypes.byref(bv), ctypes.byref(bi), ctypes.byref(gv), ctypes.byref(gi), _lib.dp(gx), ctypes.byref(gr)))
+            _lib.check(_lib.lib.ibo_acq_sweep_exchange(*((dev.h, exchange.h, 1 if incremental else 0) + lead + best + (
+                ctypes.byref(gv), ctypes.byref(gi), _lib.dp(gx), ctypes.byref(gr)))))
             glob = dict(global_val=gv.value, global_idx=gi.value, global_x=gx, global_rank=gr.value)
-        entry = _lib.lib.ibo_acq_sweep_incremental if incremental else _lib.lib.ibo_acq_sweep
-        if exchange is None:
-            _lib.check(entry(
-                h, M, cand.ptr, code, float(parm), _lib.ERF_LIBM if native else _lib.ERF_NR,
-                _lib.CLAMP_NATIVE if native else _lib.CLAMP_PY, float('nan') if ymax is None else float(ymax),
-                0 if ex is None else len(ex), None if ex is None else _lib.dp(ex), float(exclude_radius),
-                int(index_base), outs["mu"].ptr if "mu" in outs else None, outs["s2"].ptr if "s2" in outs else None,
-                outs["acq"].ptr if "acq" in outs else None, ctypes.byref(bv), ctypes.byref(bi)))
-    finally:
-        if native:
-            _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(h, sf2_py))
-    ms = ctypes.c_float(); name = ctypes.c_char_p()
-    _lib.check(_lib.lib.ibo_last_sweep_kernel_ms(h, ctypes.byref(ms), ctypes.byref(name)))
-    res = dict(best_val=bv.value, best_idx=bi.value, kernel_ms=ms.value, kernel=name.value.decode())
+        else:
+            entry = _lib.lib.ibo_acq_sweep_incremental if incremental else dev.entry("acq_sweep")
+            _lib.check(entry(*((dev.h,) + lead + tuple(outs[k].ptr if k in outs else None for k in ("mu", "s2", "acq")) + best)))
+    if plain:
+        ms = ctypes.c_float(); name = ctypes.c_char_p()
+        _lib.check(_lib.lib.ibo_last_sweep_kernel_ms(dev.h, ctypes.byref(ms), ctypes.byref(name)))
+        res = dict(best_val=bv.value, best_idx=bi.value, kernel_ms=ms.value, kernel=name.value.decode())
+    else:
+        res = dict(best_val=bv.value, best_idx=bi.value, kernel_ms=_lib.gpu_time_ms(dev.device) - t0, kernel=_SWEEP_KERNEL[kind])
     if glob is not None:
         res.update(glob)
-    for k, v in outs.items():
-        res[k] = v.to_host()
-    return res
-
-
-def _sweep_sparse(model, candidates, acq, xi, delta, scale, parm, native, ymax, exclude, exclude_radius, index_base, outputs, NA, incremental,
-                  exchange):
-    """sweep() on a sparse model (ibo_sgp_acq_sweep): the same arguments and result, exclusion balls included; kernel_ms is the whole
-    call's device time"""
-    if incremental:
-        model._no_gradient("sweep(incremental=)")
-    if exchange is not None:
-        model._no_gradient("sweep(exchange=)")
-    if parm is None:
-        if acq == 'ucb':
-            nd = NA if NA is not None else (candidates.shape[1] if hasattr(candidates, "shape") else np.atleast_2d(candidates).shape[1])
-            parm = _ucb_parm(model, [None] * nd, delta, scale) if native else float(np.sqrt(scale * UCB(model, nd, delta, scale).sBeta))
-        else:
-            parm = xi
-    return model._sweep(candidates, _ACQ[acq], parm, native, ymax, exclude, exclude_radius, index_base, outputs)
-
-
-def _sweep_gradient(model, candidates, acq, xi, delta, scale, parm, native, ymax, exclude, index_base, outputs, NA, incremental,
-                    exchange):
-    """sweep() on a model observed with gradients (ibo_ggp_acq_sweep)"""
-    if exclude is not None and len(exclude) > 0:
-        model._no_gradient("sweep(exclude=)")
-    if incremental:
-        model._no_gradient("sweep(incremental=)")
-    if exchange is not None:
-        model._no_gradient("sweep(exchange=)")
-    dev = model._gdev.device
-    cand = candidates if isinstance(candidates, _lib.DeviceArray) else _lib.DeviceArray.from_host(np.atleast_2d(candidates), dev)
-    M = cand.shape[0]
-    if parm is None:
-        if acq == 'ucb':
-            nd = NA if NA is not None else cand.shape[1]
-            parm = _ucb_parm(model, [None] * nd, delta, scale) if native else float(np.sqrt(scale * UCB(model, nd, delta, scale).sBeta))
-        else:
-            parm = xi
-    outs = {k: _lib.DeviceArray((M,), dev) for k in outputs}
-    bv = ctypes.c_double(); bi = ctypes.c_int64()
-    t0 = _lib.gpu_time_ms(dev)
-    _lib.check(_lib.lib.ibo_ggp_acq_sweep(
-        model._gdev.h, M, cand.ptr, _ACQ[acq], float(parm), _lib.ERF_LIBM if native else _lib.ERF_NR,
-        _lib.CLAMP_NATIVE if native else _lib.CLAMP_PY, float('nan') if ymax is None else float(ymax), int(index_base),
-        outs["mu"].ptr if "mu" in outs else None, outs["s2"].ptr if "s2" in outs else None,
-        outs["acq"].ptr if "acq" in outs else None, ctypes.byref(bv), ctypes.byref(bi)))
-    res = dict(best_val=bv.value, best_idx=bi.value, kernel_ms=_lib.gpu_time_ms(dev) - t0, kernel="gradobs row pipeline")
     for k, v in outs.items():
         res[k] = v.to_host()
     return res

@@ -1,5 +1,5 @@
-"""What the acquisition modules share: the checks of their arguments (points, candidate arrays, bounds), the methods of a host-point
-acquisition class, and the polish step of the maximisers."""
+"""What the acquisition modules share: the checks of their arguments (points, candidate arrays, bounds), the switch to libego's k* signal
+variance, the methods of a host-point acquisition class, and the polish step of the maximisers."""
 import numpy as np
 
 from .. import _lib
@@ -8,7 +8,7 @@ from .. import _lib
 def _no_gradient(GP, what):
     """refuse `what` on a model observed with gradients (GaussianProcess(G=)) and on a sparse model (SparseGaussianProcess); anything
     without a G attribute passes"""
-    if getattr(GP, "G", None) is not None or getattr(GP, "_sparse", False):
+    if getattr(GP, "G", None) is not None or getattr(GP, "_kind", "gp") != "gp":
         GP._no_gradient(what)
 
 
@@ -44,6 +44,30 @@ def _bounds(bounds, D_model):
     if len(lb) != D_model:
         raise ValueError("bounds have %d dimensions, the model has %d" % (len(lb), D_model))
     return lb, ub, len(lb)
+
+
+class _kstar_native(object):
+    """libego's k* signal variance on every (plain) model involved, the Python one restored on exit; on=False: nothing"""
+
+    def __init__(self, models, on=True):
+        self.models = list(models) if on else []
+
+    def __enter__(self):
+        self.done = []
+        try:
+            for m in self.models:
+                _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(m._handle(), m.kernel._ibo_spec()[3]))
+                self.done.append(m)
+        except Exception:
+            self.__exit__(None, None, None)
+            raise
+        return self
+
+    def __exit__(self, *exc):
+        for m in self.done:
+            _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(m._handle(), m.kernel._ibo_spec()[2]))
+        self.done = []
+        return False
 
 
 POLISH_MAXITER = 30

@@ -30,6 +30,7 @@ import numpy as np
 
 from .. import _lib
 from . import _args
+from ._args import _kstar_native
 
 _CACQ = {'ei': _lib.ACQ_EI, 'pi': _lib.ACQ_PI, 'pof': _lib.ACQ_NONE}
 MAX_CONSTRAINTS = 8          # IBO_CACQ_MAX_CON
@@ -64,30 +65,6 @@ def _pack(constraints):
     thresh = _lib.f64([c.thresh for c in constraints] or [0.0])
     sense = (ctypes.c_int * max(n, 1))(*[c.sense for c in constraints])
     return n, con, thresh, sense
-
-
-class _kstar_native(object):
-    """libego's k* signal variance on every model involved, the Python one restored on exit"""
-
-    def __init__(self, models, on=True):
-        self.models = list(models) if on else []
-
-    def __enter__(self):
-        self.done = []
-        try:
-            for m in self.models:
-                _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(m._handle(), m.kernel._ibo_spec()[3]))
-                self.done.append(m)
-        except Exception:
-            self.__exit__(None, None, None)
-            raise
-        return self
-
-    def __exit__(self, *exc):
-        for m in self.done:
-            _lib.check(_lib.lib.ibo_gp_set_kstar_sf2(m._handle(), m.kernel._ibo_spec()[2]))
-        self.done = []
-        return False
 
 
 def feasibleIncumbent(model, constraints):

@@ -29,7 +29,7 @@ import numpy as np
 
 from .. import _lib
 from . import _args
-from .constrained import _kstar_native
+from ._args import _kstar_native
 
 MAX_FRONT = 1024             # IBO_EHVI_MAX_FRONT
 

@@ -13,6 +13,10 @@ Everything numerical -- K(X,X), Cholesky, L^-1, posterior mean/variance -- runs
 in libibo_hip on the GPU; this file holds the bookkeeping the reference keeps
 in Python (data accumulation, preference indexing, the MAP optimiser's control
 flow).  There is no NumPy fallback: without the library or a GPU, fitting raises.
+
+A model's device handle is a _Device of one of three kinds -- 'gp' (ibo_gp_t), 'ggp' (ibo_ggp_t, once the model holds gradient
+observations), 'sgp' (ibo_sgp_t, sparse.py) -- kept in _dev, _gdev, _sdev; model._owner() is the one in force and model._kind its kind.
+_acq_batch is the host batch of all three (ibo_acq_batch / ibo_ggp_acq_batch / ibo_sgp_acq_batch).
 """
 import ctypes
 from time import time
@@ -21,6 +25,7 @@ import numpy as np
 
 from .. import _lib
 from .._lib import NotPositiveDefinite
+from . import trainhyper
 from .kernel import GaussianKernel_ard, GaussianKernel_iso, MaternKernel3, MaternKernel5  # noqa: F401
 
 LinAlgError = np.linalg.LinAlgError
@@ -49,19 +54,28 @@ def PDF(x):
     return np.exp(-(x ** 2 / 2)) * 0.398942
 
 
-class _DeviceGP(object):
-    """owner of one ibo_gp_t handle"""
+class _Device(object):
+    """owner of one device handle.  Its kind names the model and, through it, the entries that take the handle -- ibo_<kind>_create and
+    _destroy, and the evaluating ones (entry):
+        'gp'   ibo_gp_t   the plain model                    ibo_acq_batch      ibo_acq_sweep      ibo_direct_max
+        'ggp'  ibo_ggp_t  a model observed with gradients    ibo_ggp_acq_batch  ibo_ggp_acq_sweep  ibo_ggp_direct_max
+        'sgp'  ibo_sgp_t  a sparse model                     ibo_sgp_acq_batch  ibo_sgp_acq_sweep  ibo_sgp_direct_max"""
+    kind = 'gp'
 
     def __init__(self, device=None):
         self.device = _lib.default_device() if device is None else device
         h = ctypes.c_void_p()
-        _lib.check(_lib.lib.ibo_gp_create(self.device, ctypes.byref(h)))
+        _lib.check(getattr(_lib.lib, "ibo_%s_create" % self.kind)(self.device, ctypes.byref(h)))
         self.h = h
+
+    def entry(self, name):
+        """the evaluating entry `name` ('acq_batch', 'acq_sweep', 'direct_max') of this kind"""
+        return getattr(_lib.lib, "ibo_" + ("" if self.kind == 'gp' else self.kind + "_") + name)
 
     def close(self):
         if getattr(self, "h", None):
             try:
-                _lib.lib.ibo_gp_destroy(self.h)
+                getattr(_lib.lib, "ibo_%s_destroy" % self.kind)(self.h)
             except Exception:
                 pass
             self.h = None
@@ -70,25 +84,27 @@ class _DeviceGP(object):
         self.close()
 
 
-class _DeviceGGP(object):
-    """owner of one ibo_ggp_t handle: a model observed with gradients"""
+class _DeviceGP(_Device):
+    kind = 'gp'
 
-    def __init__(self, device=None):
-        self.device = _lib.default_device() if device is None else device
-        h = ctypes.c_void_p()
-        _lib.check(_lib.lib.ibo_ggp_create(self.device, ctypes.byref(h)))
-        self.h = h
 
-    def close(self):
-        if getattr(self, "h", None):
-            try:
-                _lib.lib.ibo_ggp_destroy(self.h)
-            except Exception:
-                pass
-            self.h = None
+class _DeviceGGP(_Device):
+    kind = 'ggp'
 
-    def __del__(self):
-        self.close()
+
+def _acq_batch(dev, Q, acq, parm, erf_mode, clamp_lo, want, ymax):
+    """host points Q (M, D) in, host arrays out, through the acq_batch entry of the handle's kind (PCIe-inclusive); with 'acq' among
+    `want` also its first maximiser"""
+    M = len(Q)
+    res = {k: np.empty(M) for k in want}
+    ptr = lambda k: _lib.dp(res[k]) if k in res else None
+    _lib.check(dev.entry("acq_batch")(dev.h, M, _lib.dp(Q), acq, float(parm), erf_mode, clamp_lo,
+                                      float('nan') if ymax is None else float(ymax), ptr("mu"), ptr("s2"), ptr("acq")))
+    if "acq" in res:                             # first maximiser, NaNs never win: what the device arg-max does
+        score = np.where(np.isnan(res["acq"]), -np.inf, res["acq"])
+        k = int(np.argmax(score))
+        res["best_val"], res["best_idx"] = float(score[k]), k
+    return res
 
 
 _GRADIENT_WHY = ("the model is observed with gradients (G=): it has N (D + 1) rows of values and derivatives, and only posterior, "
@@ -144,10 +160,7 @@ class GaussianProcess(object):
                                       "prior's gradient, which the device does not subtract")
         ktype, hyper, sf2, _ = self.kernel._ibo_spec()
         N, D = X.shape
-        gn = np.asarray(self.gnoise, dtype=float).reshape(-1)
-        gn = _lib.f64(np.tile(gn, D) if len(gn) == 1 else gn)
-        if len(gn) != D:
-            raise ValueError("gnoise has %d entries, the data %d dimensions" % (len(gn), D))
+        gn = trainhyper._gnoise_row(self.gnoise, D)
         dev = _DeviceGGP(self._device)
         Xc, Yc, Gc = _lib.f64(X), _lib.f64(Y), _lib.f64(G)
         info = ctypes.c_int(0)
@@ -174,14 +187,6 @@ class GaussianProcess(object):
         self._fit_gradient(allX, allY, allG)         # (raises before anything of the model changes)
         self.X, self.Y, self.G = allX, allY, allG
 
-    def _ggp_eval(self, Q, acq, parm, erf_mode, clamp_lo, want, ymax):
-        M = len(Q)
-        res = {k: np.empty(M) for k in want}
-        ptr = lambda k: _lib.dp(res[k]) if k in res else None
-        _lib.check(_lib.lib.ibo_ggp_acq_batch(self._gdev.h, M, _lib.dp(Q), acq, float(parm), erf_mode, clamp_lo,
-                                              float('nan') if ymax is None else float(ymax), ptr("mu"), ptr("s2"), ptr("acq")))
-        return res
-
     def nlml(self):
         """the negative log marginal likelihood of a model observed with gradients at its own kernel, noise and gnoise
         (trainhyper.gradientLikelihood: the kernel's own signal variance on the value rows' diagonal).  A model of values alone has none of
@@ -189,7 +194,6 @@ class GaussianProcess(object):
         if self.G is None:
             raise NotImplementedError("GaussianProcess.nlml is the likelihood of a model observed with gradients (G=); for values alone "
                                       "call trainhyper.marginalLikelihood(kernel, X, Y, nhyper, noise=...)")
-        from . import trainhyper
         return trainhyper.gradientLikelihood(self.kernel, self.X, self.Y, self.G, 0, noise=self.noise, gnoise=self.gnoise,
                                              computeGradient=False)
 
@@ -200,24 +204,19 @@ class GaussianProcess(object):
         search.  bounds: L-BFGS-B's, one (lo, hi) per variable in that order, or None.  When the search ends at a finite value below the
         one it started from -- also when it stopped for lack of iterations -- the kernel is rebuilt as kernel.__class__(exp(log theta)),
         noise and gnoise are set and a NEW handle is fitted and swapped in; a failing fit leaves the model as it was.  Otherwise the
-        model is not touched.  Returns the scipy result with .start_value, .end_value and .applied.  A model of values alone:
-        NotImplementedError naming trainhyper.nlml."""
+        model is not touched.  Returns the scipy result with .start_value, .end_value, .evaluations and .applied (trainhyper._learn).
+        A model of values alone: NotImplementedError naming trainhyper.nlml."""
         if self.G is None:
             raise NotImplementedError("GaussianProcess.learn is built for a model observed with gradients (G=); for values alone minimise "
                                       "trainhyper.nlml / dnlml (scipy.optimize.fmin_bfgs, as the reference does)")
-        from scipy.optimize import minimize
-        from . import trainhyper
         cls = self.kernel.__class__
         th0 = np.asarray(self.kernel.hyperparams, dtype=float)
         nh = len(th0) if nhyper is None else int(nhyper)
         if not 0 <= nh <= len(th0):
             raise ValueError("kernel has %d hyperparameters, %d asked for" % (len(th0), nh))
         D = self.X.shape[1]
-        gn0 = np.asarray(self.gnoise, dtype=float).reshape(-1)
-        gn0 = np.tile(gn0, D) if len(gn0) == 1 else gn0
+        gn0 = trainhyper._gnoise_row(self.gnoise, D)
         x0 = np.r_[np.log(th0[:nh]), [np.log(float(self.noise))] if noise else [], np.log(gn0) if gnoise else []]
-        if len(x0) == 0:
-            raise ValueError("nothing to learn")
 
         def unpack(x):
             kern = cls(np.r_[np.exp(x[:nh]), th0[nh:]]) if nh else self.kernel
@@ -225,37 +224,27 @@ class GaussianProcess(object):
             nz = float(self.noise)
             if noise:
                 nz = float(np.exp(x[o])); o += 1
-            return kern, nz, (np.exp(x[o:o + D]) if gnoise else gn0)
-
-        values = []
+            return dict(kernel=kern, noise=nz, gnoise=np.array(np.exp(x[o:o + D]) if gnoise else gn0, dtype=float))
 
         def fg(x):
-            kern, nz, gn = unpack(x)
-            try:
-                v, g, g_nz, g_gn = trainhyper.gradientLikelihood(kern, self.X, self.Y, self.G, nh, noise=nz, gnoise=gn, gradNoise=True)
-            except np.linalg.LinAlgError:
-                return np.inf, np.zeros(len(x))
-            values.append(v)
+            p = unpack(x)
+            v, g, g_nz, g_gn = trainhyper.gradientLikelihood(p["kernel"], self.X, self.Y, self.G, nh, noise=p["noise"], gnoise=p["gnoise"],
+                                                             gradNoise=True)
             return v, np.r_[g, [g_nz] if noise else [], g_gn if gnoise else []]
 
-        res = minimize(fg, x0, jac=True, method='L-BFGS-B', bounds=bounds, options=dict(maxiter=int(maxiter)))
-        res.start_value = values[0] if values else float('nan')
-        res.end_value = float(res.fun)
-        res.evaluations = len(values)
-        res.applied = bool(values) and np.isfinite(res.end_value) and res.end_value < res.start_value
-        if not res.applied:
-            return res
-        kern, nz, gn = unpack(np.asarray(res.x, dtype=float))
-        keep = self.kernel, self.noise, self.gnoise
-        self.kernel, self.noise, self.gnoise = kern, nz, np.array(gn, dtype=float)
-        try:
-            self._fit_gradient(self.X, self.Y, self.G)      # (a new handle, swapped in only when the fit succeeded)
-        except Exception:
-            self.kernel, self.noise, self.gnoise = keep
-            raise
-        return res
+        # (the refit is a new handle, swapped in only when the fit succeeded)
+        return trainhyper._learn(self, x0, fg, unpack, lambda: self._fit_gradient(self.X, self.Y, self.G), maxiter, bounds)
 
     # ------------------------------------------------------------------ device plumbing
+    @property
+    def _kind(self):
+        """the kind of the model's handle (_Device): 'ggp' once it holds gradient observations, else 'gp'"""
+        return 'gp' if self.G is None else 'ggp'
+
+    def _owner(self):
+        """the handle owner (_Device) that _eval, sweep and cdirectGP run on; None before the first fit"""
+        return self._dev if self.G is None else self._gdev
+
     def _handle(self):
         self._no_gradient("this call (it takes the model's ibo_gp_t handle)")
         if self._dev is None:
@@ -367,13 +356,8 @@ class GaussianProcess(object):
               want=("mu", "s2"), ymax=None):
         """host points in, host arrays out, through the device sweep (PCIe-inclusive)"""
         Q = _lib.f64(np.atleast_2d(Q))
-        M, D = Q.shape
-        if self.G is not None:
-            res = self._ggp_eval(Q, acq, parm, erf_mode, clamp_lo, want, ymax)
-        else:
-            res = None
-        self._push_prior()
-        if res is None and self._augdev is not None and acq != _lib.ACQ_NONE:
+        self._push_prior()                           # (the plain kind's step: nothing to do on a gradient model)
+        if self._augdev is not None and acq != _lib.ACQ_NONE:
             # augmented variance in force (addObservationPoint): mean and variance come from two
             # factors, so the acquisition is formed from them as the reference's classes do
             # (ego/acquisition/__init__.py:68-71,107-110,150-164), per point on the host
@@ -390,16 +374,9 @@ class GaussianProcess(object):
                 else:
                     val = yd * CDF(Z) + sig * PDF(Z)
             return {"mu": mu, "s2": s2, "acq": val, "best_val": float(np.max(val)), "best_idx": int(np.argmax(val))}
-        if res is None:
-            res = {k: np.empty(M) for k in want}
-            ptr = lambda k: _lib.dp(res[k]) if k in res else None
-            _lib.check(_lib.lib.ibo_acq_batch(self._handle(), M, _lib.dp(Q), acq, float(parm), erf_mode, clamp_lo,
-                                              float('nan') if ymax is None else float(ymax), ptr("mu"), ptr("s2"), ptr("acq")))
-        if "acq" in res:                             # first maximiser, NaNs never win: what the device arg-max does
-            score = np.where(np.isnan(res["acq"]), -np.inf, res["acq"])
-            k = int(np.argmax(score))
-            res["best_val"], res["best_idx"] = float(score[k]), k
-        return res
+        if self.G is None:
+            self._handle()                           # (creates the plain handle when there is none yet)
+        return _acq_batch(self._owner(), Q, acq, parm, erf_mode, clamp_lo, want, ymax)
 
     # ------------------------------------------------------------------ reference API
     def posterior(self, X, getvar=True):
@@ -418,7 +395,7 @@ class GaussianProcess(object):
         Q = _lib.f64(np.atleast_2d(Q))
         M = len(Q)
         if self.G is not None:
-            res = self._ggp_eval(Q, _lib.ACQ_NONE, 0.0, _lib.ERF_NR, _lib.CLAMP_PY, ("mu", "s2") if getvar else ("mu",), None)
+            res = _acq_batch(self._gdev, Q, _lib.ACQ_NONE, 0.0, _lib.ERF_NR, _lib.CLAMP_PY, ("mu", "s2") if getvar else ("mu",), None)
             return res["mu"], res.get("s2")
         self._push_prior()
         mu = np.empty(M)

@@ -13,14 +13,17 @@ accumulates into the device's kept Gram matrix -- O(n m^2 + m^3), no stored data
 the plain model's attributes are; nothing reads them after the first fit but max(Y) for the acquisition classes -- and nlml_gradient /
 learn, which stream them through ibo_sgp_nlml_grad again.)
 
-EI / PI / UCB(model).f / .negf / .values, acquisition.sweep and maximizeEI / PI / UCB work on it; everything else that takes a model
-refuses it with a NotImplementedError that names the call.
+EI / PI / UCB(model).f / .negf / .values, acquisition.sweep and maximizeEI / PI / UCB work on it, through the routes every kind of model
+takes (the handle is a gaussianprocess._Device of kind 'sgp': ibo_sgp_acq_batch, ibo_sgp_acq_sweep, ibo_sgp_direct_max); everything else
+that takes a model refuses it with a NotImplementedError that names the call.
 """
 import ctypes
 
 import numpy as np
 
 from .. import _lib
+from . import _Device, _acq_batch
+from .trainhyper import _grad_spec, _learn
 
 _METHOD = {'fitc': 0, 'dtc': 1}
 _NLML_MODEL, _NLML_VFE = 0, 1
@@ -44,14 +47,8 @@ def nlml_grad_raw(kernel, X, Y, Z, noise, jitter, kind, ngrad=None, want=('hyper
     if Zc.shape[1] != D:
         raise ValueError("Z has %d columns, the data %d" % (Zc.shape[1], D))
     ktype, hyper, sf2, _ = kernel._ibo_spec()
-    spec = kernel._ibo_grad_spec(D)
-    if ngrad is not None:
-        if len(spec) < ngrad:
-            raise ValueError("kernel has %d hyperparameters, %d gradients requested" % (len(spec), ngrad))
-        spec = spec[:ngrad]
-    n = len(spec) if 'hyper' in want else 0
-    modes = (ctypes.c_int * max(n, 1))(*[s[0] for s in spec[:n]])
-    dims = (ctypes.c_int * max(n, 1))(*[s[1] for s in spec[:n]])
+    modes, dims = _grad_spec(kernel, D, ngrad)
+    n = len(modes) if 'hyper' in want else 0
     gh = np.empty(n) if n else None
     gn = ctypes.c_double() if 'noise' in want else None
     gz = np.empty(Zc.shape) if 'Z' in want else None
@@ -95,30 +92,13 @@ def inducingPoints(X, m, method='subset', seed=None):
     raise ValueError("unknown selection method %r ('subset' or 'kcenter')" % (method,))
 
 
-class _DeviceSGP(object):
-    """owner of one ibo_sgp_t handle"""
-
-    def __init__(self, device=None):
-        self.device = _lib.default_device() if device is None else device
-        h = ctypes.c_void_p()
-        _lib.check(_lib.lib.ibo_sgp_create(self.device, ctypes.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            try:
-                _lib.lib.ibo_sgp_destroy(self.h)
-            except Exception:
-                pass
-            self.h = None
-
-    def __del__(self):
-        self.close()
+class _DeviceSGP(_Device):
+    kind = 'sgp'
 
 
 class SparseGaussianProcess(object):
 
-    _sparse = True
+    _kind = 'sgp'          # the kind of the model's handle (_Device)
 
     def __init__(self, kernel, X=None, Y=None, Z=None, m=None, noise=.1, jitter=1e-6, method='fitc', seed=None, device=None,
                  prior=None, selection='subset'):
@@ -180,6 +160,12 @@ class SparseGaussianProcess(object):
     # ------------------------------------------------------------------ device plumbing
     @property
     def _dev(self):
+        return self._sdev
+
+    def _owner(self):
+        """the handle owner (_Device) that _eval, sweep and cdirectGP run on"""
+        if self._sdev is None:
+            raise ValueError("model has no data")
         return self._sdev
 
     def _fit(self, X, Y):
@@ -265,19 +251,7 @@ class SparseGaussianProcess(object):
 
     def _eval(self, Q, acq=_lib.ACQ_NONE, parm=0.0, erf_mode=_lib.ERF_NR, clamp_lo=_lib.CLAMP_PY, want=("mu", "s2"), ymax=None):
         """host points in, host arrays out (ibo_sgp_acq_batch): the plain model's _eval"""
-        if self._sdev is None:
-            raise ValueError("model has no data")
-        Q = _lib.f64(np.atleast_2d(Q))
-        M = len(Q)
-        res = {k: np.empty(M) for k in want}
-        ptr = lambda k: _lib.dp(res[k]) if k in res else None
-        _lib.check(_lib.lib.ibo_sgp_acq_batch(self._sdev.h, M, _lib.dp(Q), acq, float(parm), erf_mode, clamp_lo,
-                                              float('nan') if ymax is None else float(ymax), ptr("mu"), ptr("s2"), ptr("acq")))
-        if "acq" in res:                             # first maximiser, NaNs never win: what the device arg-max does
-            score = np.where(np.isnan(res["acq"]), -np.inf, res["acq"])
-            k = int(np.argmax(score))
-            res["best_val"], res["best_idx"] = float(score[k]), k
-        return res
+        return _acq_batch(self._owner(), _lib.f64(np.atleast_2d(Q)), acq, parm, erf_mode, clamp_lo, want, ymax)
 
     # ------------------------------------------------------------------ the plain model's API
     def posterior(self, X, getvar=True):
@@ -348,18 +322,15 @@ class SparseGaussianProcess(object):
         at a finite value below the one it started from -- also when it stopped for lack of iterations -- the kernel is rebuilt as
         kernel.__class__(exp(log theta)), noise and Z are set and the model is refitted; a failing refit leaves the model as it was.
         Otherwise (the start does not factor, nothing lower was found) the model is not touched.  Returns the scipy result with
-        .start_value, .end_value and .applied."""
+        .start_value, .end_value, .evaluations and .applied (trainhyper._learn)."""
         if self._sdev is None:
             raise ValueError("model has no data")
-        from scipy.optimize import minimize
         kind = self._objective(kind)
         cls = self.kernel.__class__
         th0 = np.log(np.asarray(self.kernel.hyperparams, dtype=float))
         Z0 = np.array(self.Z, dtype=float)
         nh = len(th0) if learn_hyper else 0
         x0 = np.r_[th0[:nh], [np.log(float(self.noise))] if learn_noise else [], Z0.ravel() if learn_Z else []]
-        if len(x0) == 0:
-            raise ValueError("nothing to learn")
         want = tuple(w for w, on in (('hyper', learn_hyper), ('noise', learn_noise), ('Z', learn_Z)) if on)
         dev = self._sdev.device
 
@@ -369,66 +340,11 @@ class SparseGaussianProcess(object):
             noise = float(self.noise)
             if learn_noise:
                 noise = float(np.exp(x[o])); o += 1
-            return kern, noise, (x[o:].reshape(Z0.shape) if learn_Z else Z0)
-
-        values = []
+            return dict(kernel=kern, noise=noise, Z=np.array(x[o:].reshape(Z0.shape) if learn_Z else Z0, dtype=float))
 
         def fg(x):
-            kern, noise, Z = unpack(x)
-            try:
-                v, g = nlml_grad_raw(kern, self.X, self.Y, Z, noise, self.jitter, kind, want=want, device=dev)
-            except _lib.NotPositiveDefinite:
-                return np.inf, np.zeros(len(x))
-            values.append(v)
+            p = unpack(x)
+            v, g = nlml_grad_raw(p["kernel"], self.X, self.Y, p["Z"], p["noise"], self.jitter, kind, want=want, device=dev)
             return v, np.r_[g.get('hyper', []), [g['noise']] if learn_noise else [], g['Z'].ravel() if learn_Z else []]
 
-        res = minimize(fg, x0, jac=True, method='L-BFGS-B', bounds=bounds, options=dict(maxiter=int(maxiter)))
-        res.start_value = values[0] if values else float('nan')
-        res.end_value = float(res.fun)
-        # the point found is taken when it is an improvement, whatever stopped the search (L-BFGS-B reports success=False when it runs out
-        # of iterations); a start that does not factor, or a search that found nothing lower, leaves the model alone
-        res.applied = bool(values) and np.isfinite(res.end_value) and res.end_value < res.start_value
-        if not res.applied:
-            return res
-        kern, noise, Z = unpack(np.asarray(res.x, dtype=float))
-        keep = self.kernel, self.noise, self.Z
-        self.kernel, self.noise, self.Z = kern, noise, np.array(Z, dtype=float)
-        try:
-            self._fit(self.X, self.Y)
-        except Exception:
-            self.kernel, self.noise, self.Z = keep
-            raise
-        return res
-
-    def _sweep(self, candidates, code, parm, native, ymax, exclude, exclude_radius, index_base, outputs):
-        """acquisition.sweep on this model (ibo_sgp_acq_sweep): the model's own signal variance in both modes"""
-        if self._sdev is None:
-            raise ValueError("model has no data")
-        dev = self._sdev.device
-        cand = candidates if isinstance(candidates, _lib.DeviceArray) else _lib.DeviceArray.from_host(np.atleast_2d(candidates), dev)
-        M = cand.shape[0]
-        outs = {k: _lib.DeviceArray((M,), dev) for k in outputs}
-        ex = None if exclude is None or len(exclude) == 0 else _lib.f64(np.atleast_2d(exclude))
-        bv = ctypes.c_double(); bi = ctypes.c_int64()
-        t0 = _lib.gpu_time_ms(dev)
-        _lib.check(_lib.lib.ibo_sgp_acq_sweep(
-            self._sdev.h, M, cand.ptr, code, float(parm), _lib.ERF_LIBM if native else _lib.ERF_NR,
-            _lib.CLAMP_NATIVE if native else _lib.CLAMP_PY, float('nan') if ymax is None else float(ymax),
-            0 if ex is None else len(ex), None if ex is None else _lib.dp(ex), float(exclude_radius), int(index_base),
-            outs["mu"].ptr if "mu" in outs else None, outs["s2"].ptr if "s2" in outs else None,
-            outs["acq"].ptr if "acq" in outs else None, ctypes.byref(bv), ctypes.byref(bi)))
-        res = dict(best_val=bv.value, best_idx=bi.value, kernel_ms=_lib.gpu_time_ms(dev) - t0, kernel="sparse two-frame sweep")
-        for k, v in outs.items():
-            res[k] = v.to_host()
-        return res
-
-    def _direct(self, lb, ub, code, parm, maxiter, maxtime, maxsample, compat):
-        """DIRECT on this model (ibo_sgp_direct_max): libm erf and the native clamp, as cdirectGP runs the plain model"""
-        if self._sdev is None:
-            raise ValueError("model has no data")
-        D = len(lb)
-        opt = ctypes.c_double(); optx = np.empty(D); ns = ctypes.c_int64()
-        _lib.check(_lib.lib.ibo_sgp_direct_max(self._sdev.h, D, _lib.dp(lb), _lib.dp(ub), code, float(parm), _lib.ERF_LIBM,
-                                               _lib.CLAMP_NATIVE, int(maxiter), int(maxtime), int(maxsample), 1 if compat else 0,
-                                               ctypes.byref(opt), _lib.dp(optx), ctypes.byref(ns)))
-        return opt.value, optx, ns.value
+        return _learn(self, x0, fg, unpack, lambda: self._fit(self.X, self.Y), maxiter, bounds)

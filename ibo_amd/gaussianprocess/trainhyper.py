@@ -20,6 +20,9 @@ predictions come from ibo_loo_grad: the same sequence up to K^-1, then T = K^-1 
 These three factor N x N; the sparse model's likelihood on m inducing points, O(N m^2), comes from ibo_sgp_nlml_grad, and the
 N (D + 1)-row likelihood of values and slopes from ibo_ggp_nlml_grad.
 """
+import ctypes
+import hashlib
+
 import numpy as np
 from numpy.linalg import LinAlgError
 
@@ -39,6 +42,98 @@ def _spec_rows(kernels):
     thetas = _lib.f64(np.array([s[1] for s in specs]))
     sf2 = _lib.f64([s[2] for s in specs])
     return ktype, thetas, sf2
+
+
+def _grad_spec(kernel, D, nhyper):
+    """(modes, dims): kernel._ibo_grad_spec(D)'s first nhyper rows (None: all of them) as the two int arrays the *_grad entries take"""
+    spec = kernel._ibo_grad_spec(D)
+    if nhyper is not None:
+        if len(spec) < nhyper:
+            raise ValueError("kernel has %d hyperparameters, %d gradients requested" % (len(spec), nhyper))
+        spec = spec[:nhyper]
+    return (ctypes.c_int * len(spec))(*[m for m, _ in spec]), (ctypes.c_int * len(spec))(*[d for _, d in spec])
+
+
+class _Memo(object):
+    """one likelihood's last (value, gradient): fmin_bfgs asks for f(x) and then f'(x) at the same x (also inside its line search); both
+    come out of one factorisation, so the pair is computed once and the last one is remembered"""
+
+    def __init__(self, likelihood):
+        self.likelihood, self.key, self.pair = likelihood, None, None      # (the likelihood's name: looked up in this module at every call)
+
+    def __call__(self, loghyper, kernel, arrays, key=(), **kwargs):
+        """likelihood(kernel(exp(loghyper)), *arrays, len(loghyper), **kwargs), or the remembered pair.  arrays: X, Y (, G); key: what
+        the kwargs add to the key"""
+        loghyper = np.asarray(loghyper, dtype=float)
+        # keyed on the CONTENT of the data (a digest: 0.1 ms at N=4096, D=16 against a 9 ms factorisation), so an
+        # in-place edit of X or Y can never return the pair computed for the old data
+        dig = hashlib.blake2b(_lib.rows(arrays[0]).tobytes(), digest_size=16)
+        for a in arrays[1:]:
+            dig.update(_lib.f64(a).tobytes())
+        key = (loghyper.tobytes(), kernel, dig.digest()) + tuple(key)
+        if self.key != key:
+            self.key = None
+            self.pair = globals()[self.likelihood](kernel(np.exp(loghyper)), *(tuple(arrays) + (len(loghyper),)), **kwargs)
+            self.key = key
+        return self.pair
+
+
+def _or_100(name, pair):
+    """pair()[0], or 100 when the matrix is not PD (trainhyper.py:99-115)"""
+    try:
+        return pair()[0]
+    except LinAlgError as e:
+        print(e)
+        print('returning %s = 100' % name)
+        return 100
+
+
+def _gnoise_row(gnoise, D):
+    """the D gradient noises: one number stands for every dimension"""
+    gn = np.asarray(gnoise, dtype=float).reshape(-1)
+    gn = _lib.f64(np.tile(gn, D) if len(gn) == 1 else gn)
+    if len(gn) != D:
+        raise ValueError("gnoise has %d entries, the data %d dimensions" % (len(gn), D))
+    return gn
+
+
+def _learn(model, x0, fg, unpack, refit, maxiter, bounds):
+    """what the learn methods share: L-BFGS-B from x0 on fg(x) -> (value, gradient), a point where the matrix does not factor
+    (LinAlgError) counting as +inf for the line search.  The point found is taken when it is an improvement, whatever stopped the search
+    (L-BFGS-B reports success=False when it runs out of iterations): unpack(x) -> {attribute: value} is set on the model and refit() called,
+    a failing refit putting the attributes back.  A start that does not factor, or a search that found nothing lower, leaves the model
+    alone.  Returns the scipy result with .start_value, .end_value, .evaluations and .applied."""
+    from scipy.optimize import minimize
+    if len(x0) == 0:
+        raise ValueError("nothing to learn")
+    values = []
+
+    def objective(x):
+        try:
+            v, g = fg(x)
+        except LinAlgError:
+            return np.inf, np.zeros(len(x))
+        values.append(v)
+        return v, g
+
+    res = minimize(objective, x0, jac=True, method='L-BFGS-B', bounds=bounds, options=dict(maxiter=int(maxiter)))
+    res.start_value = values[0] if values else float('nan')
+    res.end_value = float(res.fun)
+    res.evaluations = len(values)
+    res.applied = bool(values) and np.isfinite(res.end_value) and res.end_value < res.start_value
+    if not res.applied:
+        return res
+    new = unpack(np.asarray(res.x, dtype=float))
+    keep = {k: getattr(model, k) for k in new}
+    try:
+        for k in new:
+            setattr(model, k, new[k])
+        refit()
+    except Exception:
+        for k in keep:
+            setattr(model, k, keep[k])
+        raise
+    return res
 
 
 def nlml_values(kernels, X, Y, noise=1e-3, device=None, spec=None, G=None):
@@ -77,15 +172,10 @@ def marginalLikelihood(kernel, X, Y, nhyper, computeGradient=True, useCholesky=T
         return v
     # value and gradient in one device call: Cholesky, L^-1, K^-1 = W^T W, then
     # dnlml_i = sum((K^-1 - alpha alpha^T) * dK/dtheta_i) / 2   (:70-71)
-    import ctypes
     Xa = _lib.rows(X); Ya = _lib.f64(Y)
     N, D = Xa.shape
     ktype, hyper, sf2, _ = kernel._ibo_spec()
-    spec = kernel._ibo_grad_spec(D)[:nhyper]
-    if len(spec) < nhyper:
-        raise ValueError("kernel has %d hyperparameters, %d gradients requested" % (len(spec), nhyper))
-    modes = (ctypes.c_int * nhyper)(*[m for m, _ in spec])
-    dims = (ctypes.c_int * nhyper)(*[d for _, d in spec])
+    modes, dims = _grad_spec(kernel, D, nhyper)
     v = ctypes.c_double()
     g = np.empty(nhyper)
     try:
@@ -96,36 +186,12 @@ def marginalLikelihood(kernel, X, Y, nhyper, computeGradient=True, useCholesky=T
     return v.value, g
 
 
-# fmin_bfgs asks for f(x) and then f'(x) at the same x (also inside its line search); both come out of one
-# factorisation, so the pair is computed once and the last one is remembered
-_last = {"key": None, "value": None, "grad": None}
-
-
-def _value_and_grad(loghyper, kernel, X, Y):
-    loghyper = np.asarray(loghyper, dtype=float)
-    # keyed on the CONTENT of the data (a digest: 0.1 ms at N=4096, D=16 against a 9 ms factorisation), so an
-    # in-place edit of X or Y can never return the pair computed for the old data
-    import hashlib
-    dig = hashlib.blake2b(_lib.rows(X).tobytes(), digest_size=16)
-    dig.update(_lib.f64(Y).tobytes())
-    key = (loghyper.tobytes(), kernel, dig.digest())
-    if _last["key"] != key:
-        k = kernel(np.exp(loghyper))
-        _last["key"] = None
-        _last["value"], _last["grad"] = marginalLikelihood(k, X, Y, len(loghyper), computeGradient=True)
-        _last["key"] = key
-    return _last["value"], _last["grad"]
+_nlml_memo = _Memo('marginalLikelihood')
 
 
 def nlml(loghyper, kernel, X, Y, *args):
     """NLML as a function of LOG hyper-parameters (trainhyper.py:99-115); 100 when not PD."""
-    try:
-        ml = _value_and_grad(loghyper, kernel, X, Y)[0]
-    except LinAlgError as e:
-        print(e)
-        ml = 100
-        print('returning nlml = 100')
-    return ml
+    return _or_100('nlml', lambda: _nlml_memo(loghyper, kernel, (X, Y)))
 
 
 def nlmlMulti(loghyper, kernel, X, Y, *args):
@@ -137,7 +203,7 @@ def nlmlMulti(loghyper, kernel, X, Y, *args):
 
 
 def dnlml(loghyper, kernel, X, Y):
-    return _value_and_grad(loghyper, kernel, X, Y)[1]
+    return _nlml_memo(loghyper, kernel, (X, Y))[1]
 
 
 # ---------------------------------------------------------------------------------------- leave-one-out cross-validation
@@ -146,7 +212,6 @@ def looLikelihood(kernel, X, Y, nhyper, computeGradient=True, noise=1e-3, predic
     (to be minimised, like marginalLikelihood) and, with computeGradient, its partial derivatives w.r.t. each log hyper-parameter:
     `value` or `(value, grad)`.  predictions=True appends (mu_-i, s2_-i), the leave-one-out predictions at this theta, as a
     last element.  LinAlgError when K is not positive definite.  G: refused (NotImplementedError)."""
-    import ctypes
     _no_gradient_data(G, "looLikelihood")
     assert len(X) == len(Y)
     Xa = _lib.rows(X); Ya = _lib.f64(Y)
@@ -155,11 +220,7 @@ def looLikelihood(kernel, X, Y, nhyper, computeGradient=True, noise=1e-3, predic
     modes = dims = None
     g = None
     if computeGradient:
-        spec = kernel._ibo_grad_spec(D)[:nhyper]
-        if len(spec) < nhyper:
-            raise ValueError("kernel has %d hyperparameters, %d gradients requested" % (len(spec), nhyper))
-        modes = (ctypes.c_int * nhyper)(*[m for m, _ in spec])
-        dims = (ctypes.c_int * nhyper)(*[d for _, d in spec])
+        modes, dims = _grad_spec(kernel, D, nhyper)
         g = np.empty(nhyper)
     mu = np.empty(N) if predictions else None
     s2 = np.empty(N) if predictions else None
@@ -177,36 +238,16 @@ def looLikelihood(kernel, X, Y, nhyper, computeGradient=True, noise=1e-3, predic
     return out if len(out) > 1 else out[0]
 
 
-_last_loo = {"key": None, "value": None, "grad": None}      # (as _last: f(x) and f'(x) at one x cost one device call)
-
-
-def _loo_value_and_grad(loghyper, kernel, X, Y, noise=1e-3):
-    loghyper = np.asarray(loghyper, dtype=float)
-    import hashlib
-    dig = hashlib.blake2b(_lib.rows(X).tobytes(), digest_size=16)
-    dig.update(_lib.f64(Y).tobytes())
-    key = (loghyper.tobytes(), kernel, dig.digest(), float(noise))
-    if _last_loo["key"] != key:
-        k = kernel(np.exp(loghyper))
-        _last_loo["key"] = None
-        _last_loo["value"], _last_loo["grad"] = looLikelihood(k, X, Y, len(loghyper), computeGradient=True, noise=noise)
-        _last_loo["key"] = key
-    return _last_loo["value"], _last_loo["grad"]
+_loo_memo = _Memo('looLikelihood')
 
 
 def nloo(loghyper, kernel, X, Y, noise=1e-3):
     """the leave-one-out objective as a function of LOG hyper-parameters, for fmin_bfgs; 100 when not PD (as nlml)"""
-    try:
-        v = _loo_value_and_grad(loghyper, kernel, X, Y, noise)[0]
-    except LinAlgError as e:
-        print(e)
-        v = 100
-        print('returning nloo = 100')
-    return v
+    return _or_100('nloo', lambda: _loo_memo(loghyper, kernel, (X, Y), (float(noise),), noise=noise))
 
 
 def dnloo(loghyper, kernel, X, Y, noise=1e-3):
-    return _loo_value_and_grad(loghyper, kernel, X, Y, noise)[1]
+    return _loo_memo(loghyper, kernel, (X, Y), (float(noise),), noise=noise)[1]
 
 
 # ---------------------------------------------------------------------------------------- the sparse (inducing-point) model
@@ -228,14 +269,6 @@ def sparseLikelihood(kernel, X, Y, Z, nhyper, noise, jitter=1e-6, kind='vfe', co
 
 
 # ---------------------------------------------------------------------------------------- the model observed with gradients
-def _gnoise_row(gnoise, D):
-    gn = np.asarray(gnoise, dtype=float).reshape(-1)
-    gn = _lib.f64(np.tile(gn, D) if len(gn) == 1 else gn)
-    if len(gn) != D:
-        raise ValueError("gnoise has %d entries, the data %d dimensions" % (len(gn), D))
-    return gn
-
-
 def gradientLikelihood(kernel, X, Y, G, nhyper, noise=1e-3, gnoise=1e-4, computeGradient=True, gradNoise=False):
     """the negative log marginal likelihood of the N (D + 1)-row model of values Y and slopes G (GaussianProcess(kernel, X, Y, G=G)) with
     A = C + diag(noise, gnoise_1 .. gnoise_D) per point, C the derivative covariance with the kernel's own diagonal (marginalLikelihood's
@@ -244,7 +277,6 @@ def gradientLikelihood(kernel, X, Y, G, nhyper, noise=1e-3, gnoise=1e-4, compute
     grad_lognoise, grad_loggnoise)` -- w.r.t. the log of the kernel's first nhyper hyper-parameters, the log noise and the log of each
     of the D gradient noises.  gnoise: one number or one per dimension.  One device call (ibo_ggp_nlml_grad).  LinAlgError when A is
     not positive definite, ValueError for G.shape != X.shape."""
-    import ctypes
     Xa = _lib.rows(X); Ya = _lib.f64(Y).reshape(-1)
     Ga = _lib.f64(np.array(G, dtype=float, ndmin=2))
     if Ga.shape != Xa.shape:
@@ -256,11 +288,7 @@ def gradientLikelihood(kernel, X, Y, G, nhyper, noise=1e-3, gnoise=1e-4, compute
     modes = dims = None
     g = None
     if computeGradient:
-        spec = kernel._ibo_grad_spec(D)[:nhyper]
-        if len(spec) < nhyper:
-            raise ValueError("kernel has %d hyperparameters, %d gradients requested" % (len(spec), nhyper))
-        modes = (ctypes.c_int * nhyper)(*[m for m, _ in spec])
-        dims = (ctypes.c_int * nhyper)(*[d for _, d in spec])
+        modes, dims = _grad_spec(kernel, D, nhyper)
         g = np.empty(nhyper)
     gnz = np.empty(D + 1) if computeGradient and gradNoise else None
     v = ctypes.c_double()
@@ -276,33 +304,17 @@ def gradientLikelihood(kernel, X, Y, G, nhyper, noise=1e-3, gnoise=1e-4, compute
     return (v.value, g, gnz[0], gnz[1:].copy()) if gradNoise else (v.value, g)
 
 
-_last_g = {"key": None, "value": None, "grad": None}      # (as _last: f(x) and f'(x) at one x cost one device call)
+_g_memo = _Memo('gradientLikelihood')
 
 
-def _g_value_and_grad(loghyper, kernel, X, Y, G, noise=1e-3, gnoise=1e-4):
-    loghyper = np.asarray(loghyper, dtype=float)
-    import hashlib
-    dig = hashlib.blake2b(_lib.rows(X).tobytes(), digest_size=16)
-    dig.update(_lib.f64(Y).tobytes())
-    dig.update(_lib.f64(G).tobytes())
-    key = (loghyper.tobytes(), kernel, dig.digest(), float(noise), _lib.f64(np.asarray(gnoise, dtype=float).reshape(-1)).tobytes())
-    if _last_g["key"] != key:
-        k = kernel(np.exp(loghyper))
-        _last_g["key"] = None
-        _last_g["value"], _last_g["grad"] = gradientLikelihood(k, X, Y, G, len(loghyper), noise=noise, gnoise=gnoise)
-        _last_g["key"] = key
-    return _last_g["value"], _last_g["grad"]
+def _g_value_and_grad(loghyper, kernel, X, Y, G, noise, gnoise):
+    return _g_memo(loghyper, kernel, (X, Y, G), (float(noise), _lib.f64(np.asarray(gnoise, dtype=float).reshape(-1)).tobytes()),
+                   noise=noise, gnoise=gnoise)
 
 
 def ngnlml(loghyper, kernel, X, Y, G, noise=1e-3, gnoise=1e-4):
     """gradientLikelihood as a function of LOG hyper-parameters, for fmin_bfgs; 100 when not PD (as nlml)"""
-    try:
-        v = _g_value_and_grad(loghyper, kernel, X, Y, G, noise, gnoise)[0]
-    except LinAlgError as e:
-        print(e)
-        v = 100
-        print('returning ngnlml = 100')
-    return v
+    return _or_100('ngnlml', lambda: _g_value_and_grad(loghyper, kernel, X, Y, G, noise, gnoise))
 
 
 def dgnlml(loghyper, kernel, X, Y, G, noise=1e-3, gnoise=1e-4):
