@@ -498,16 +498,7 @@ extern "C" int ibo_gp_destroy(ibo_gp_t *g)
     (void)hipSetDevice(g->device);
     (void)hipDeviceSynchronize();                    // once, for every buffer handed back below
     g_pool_quiet = true;
-    g->Xp.release(); g->Xs.release(); g->ak.release(); g->XA.release(); g->Y.release(); g->R.release(); g->A.release(); g->L.release(); g->W.release();
-    g->T.release(); g->Wp.release(); g->diag64.release(); g->alphaY.release(); g->alpha1.release();
-    g->tmp.release(); g->cand.release(); g->outs.release(); g->excl.release(); g->qpart.release();
-    g->mupart.release(); g->partv.release(); g->res_v.release(); g->parti.release(); g->res_i.release(); g->state.release(); g->small_ws.release();
-    g->grad_ws.release(); g->grad_cand.release(); g->grad_out.release();
-    g->tile_done.release(); g->tile_ub.release(); g->part_words.release(); g->tile_rows.release(); g->tile_sel.release();
-    g->done_count.release(); g->tall.release(); g->Pk2.release();
-    g->pw.Rinv.release(); g->pw.A.release(); g->pw.Lh.release(); g->pw.E.release(); g->pw.Et.release(); g->pw.d64.release();
-    g->pw.vec.release(); g->pw.tmp.release(); g->pw.val.release(); g->pw.lin.release(); g->pw.info.release();
-    g->info.release(); g->pmeans.release(); g->pbeta.release(); g->plowerb.release(); g->pwidth.release();
+    g->release();
     g_pool_quiet = false;
     if (g->h2d_stream) {
         for (int b = 0; b < 2; b++) { (void)hipEventDestroy(g->pe_in[b]); (void)hipEventDestroy(g->pe_k[b]); (void)hipEventDestroy(g->pe_out[b]); }

@@ -145,7 +145,5 @@ extern "C" int ibo_ehvi_direct_max(ibo_gp_t *const *obj, int nfront, const doubl
 
 extern "C" int ibo_ehvi_scan_ms(double *ms, int reset)
 {
-    if (ms) *ms = t_ehvi_ms;
-    if (reset) t_ehvi_ms = 0.0;
-    return IBO_OK;
+    return read_stage_sums(&t_ehvi_ms, 1, ms, reset);
 }

@@ -1,5 +1,6 @@
 // abi_eval.h -- what the evaluation units (abi_sweep.hip, abi_batch.hip, abi_cacq.hip, abi_ehvi.hip, abi_mes.hip, abi_kg.hip, abi_paths.hip, abi_qei.hip, abi_gradobs.hip, abi_sparse.hip, abi_rows.hip, abi_moments.hip) share beyond
-// abi_internal.h: the sweep request, the host batch, and the ONE copy of the arg-max read-back, the exclusion upload, the padding of a short sweep to its size class, the timed span, the span clock, the V^T rows and the DIRECT driver.
+// abi_internal.h: the sweep request, the host batch, and the ONE copy of the arg-max read-back, the exclusion upload, the padding of a short sweep to its size class, the timed span, the two clocks
+// (abi_nlml.hip times with them too) and the read-back of their sums, the wrapped models' argument check, the V^T rows and the DIRECT driver.
 #pragma once
 #include "abi_internal.h"
 
@@ -64,6 +65,46 @@ struct SpanClock {
         return IBO_OK;
     }
 };
+// The other clock: marks on the stream around the stages of one call as they are queued, accounted after the call's own synchronisation (no wait of its own)
+struct StageClock {
+    hipStream_t s = nullptr;
+    double *ms = nullptr;                            // the unit's thread-local sums
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool on = false;
+    ~StageClock() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    int make(hipStream_t stream, double *sums, bool timing)
+    {
+        s = stream; ms = sums; on = timing;
+        for (hipEvent_t &e : ev) if (on) HIP_TRY(hipEventCreate(&e));
+        return IBO_OK;
+    }
+    int mark(int k) { if (on) HIP_TRY(hipEventRecord(ev[k], s)); return IBO_OK; }
+    int account(int k0, int k1, int stage)           // after a synchronisation: the time between marks k0 and k1 goes to stage `stage`
+    {
+        float t = 0.f;
+        if (on) { HIP_TRY(hipEventElapsedTime(&t, ev[k0], ev[k1])); ms[stage] += t; }
+        return IBO_OK;
+    }
+};
+// what every ibo_*_stage_ms / ibo_*_scan_ms entry does with its unit's n thread-local sums
+static inline int read_stage_sums(double *sums, size_t n, double *ms, int reset)
+{
+    if (ms) memcpy(ms, sums, sizeof(double) * n);
+    if (reset) memset(sums, 0, sizeof(double) * n);
+    return IBO_OK;
+}
+// What the evaluating entries of the models that wrap frames (ibo_ggp, ibo_sgp) check alike: the device first, the arguments, the state
+template <typename Handle>
+int wrapped_check(Handle *h, const char *noun, bool ptrs_ok, int64_t M, int acq, int erf_mode, bool none_ok)
+{
+    IBO_TRY(use_device(h ? h->device : 0));
+    if (!h || !ptrs_ok) return fail(IBO_ERR_ARG, "NULL argument");
+    if (M < 1) return fail(IBO_ERR_ARG, "M=%lld", (long long)M);
+    if (acq < 0 || acq > (none_ok ? IBO_ACQ_NONE : IBO_ACQ_UCB)) return fail(IBO_ERR_ARG, "unknown acquisition %d", acq);
+    if (erf_mode != IBO_ERF_LIBM && erf_mode != IBO_ERF_NR) return fail(IBO_ERR_ARG, "unknown erf flavour %d", erf_mode);
+    if (!h->fitted) return fail(IBO_ERR_STATE, "%s model before a successful fit", noun);
+    return IBO_OK;
+}
 
 // ---- abi_batch.hip
 // host points in, host arrays out (any of mu / s2 / acq may be NULL): one sweep, or the pipelined chunks of a large batch

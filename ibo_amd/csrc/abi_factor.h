@@ -44,6 +44,17 @@ struct FactorBufs {
 // Queues the factorisation of b.A (its first N rows are the matrix's own) on `route` and the inversion on s; waits for nothing.
 int factor_invert(FactorRoute route, int N, int Np, const FactorBufs &b, hipStream_t s);
 
+// ---- the frame of an Np-row matrix that asks as FACTOR_FIT: out of place on every route -- the matrix in T, the factor into L, the identity's
+// working copy in W, (L^-1)^T (or the doubling's scratch) in Et; in super-panels matrix and identity are the halves of ONE tall buffer with
+// a packed store of its own (`tall`, `Pk2`: sized here).  Wp (W's packed copy) and Pk (the two-level order's packed-update store) are the
+// caller's to lend or not (null): the fits lend T -- free by then, T and Wp then trade places -- and W (free until the inversion), the
+// likelihood frame neither (nothing sweeps it).  Picks *route, fills *b with info_zero set; eye_ready is the caller's to set.
+int fit_frame(int Np, double *T, double *L, double *W, double *Et, double *Wp, double *Pk, double *d64, int *info,
+              DevBuf<double> &tall, DevBuf<double> &Pk2, FactorRoute *route, FactorBufs *b);
+// abi_fit.hip: that frame on a handle's own buffers (the caller writes the matrix to b->A), and factor_invert on it with the trade of T and Wp
+int fit_operands(ibo_gp *g, FactorRoute *route, FactorBufs *b);
+int fit_invert(ibo_gp *g, FactorRoute route, const FactorBufs &b, int N);
+
 // ---- the info word: IBO_ERR_NOT_PD "<noun> is not positive definite (pivot ..)" unless it is zero; *info_out (if given) receives it
 int factor_info_word(int h, const char *noun, int *info_out);
 int factor_info(const int *info_dev, hipStream_t s, const char *noun, int *info_out);      // fetches it behind everything queued on s (synchronises)

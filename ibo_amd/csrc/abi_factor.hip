@@ -43,6 +43,21 @@ int factor_invert(FactorRoute route, int N, int Np, const FactorBufs &b, hipStre
     return IBO_OK;
 }
 
+int fit_frame(int Np, double *T, double *L, double *W, double *Et, double *Wp, double *Pk, double *d64, int *info,
+              DevBuf<double> &tall, DevBuf<double> &Pk2, FactorRoute *route, FactorBufs *b)
+{
+    const size_t nn = (size_t)Np * Np;
+    IBO_TRY(factor_route(Np, FACTOR_FIT, route));
+    *b = FactorBufs{};
+    b->A = T; b->eye = W; b->Pk = Pk;
+    if (*route == ROUTE_RIDE_SUPER) {
+        IBO_TRY(tall.ensure(2 * nn)); IBO_TRY(Pk2.ensure(2 * nn));
+        b->A = tall.p; b->eye = tall.p + nn; b->Pk = Pk2.p;
+    }
+    b->L = L; b->Et = Et; b->W = W; b->Wp = Wp; b->d64 = d64; b->info = info; b->info_zero = true;
+    return IBO_OK;
+}
+
 int factor_info_word(int h, const char *noun, int *info_out)
 {
     if (info_out) *info_out = h;

@@ -45,6 +45,22 @@ static int dot_form_ok(const KParams &kp, const double *X, int N, int D)
     return mx <= IBO_DOT_GUARD;
 }
 
+// the factor-side buffers of a handle whose frame has Np rows: what a fit writes, from the targets on (the gradient-observation frame has no others)
+int fit_buffers(ibo_gp *g, int Np)
+{
+    const size_t nn = (size_t)Np * Np;
+    IBO_TRY(g->Y.ensure(Np)); IBO_TRY(g->L.ensure(nn)); IBO_TRY(g->W.ensure(nn));
+    IBO_TRY(g->T.ensure(nn)); IBO_TRY(g->Wp.ensure(nn)); IBO_TRY(g->diag64.ensure(diag64_size(Np)));
+    // sweep2's stages cover rows up to the next multiple of 128: the tail of both alpha vectors stays zero
+    IBO_TRY(g->alphaY.ensure((size_t)Np + 128)); IBO_TRY(g->alpha1.ensure((size_t)Np + 128));
+    if (g->alpha_tail_Y != g->alphaY.p || g->alpha_tail_1 != g->alpha1.p || g->alpha_tail_Np != Np) {     // (nothing writes there)
+        HIP_TRY(hipMemsetAsync(g->alphaY.p + Np, 0, 128 * sizeof(double), g->stream));
+        HIP_TRY(hipMemsetAsync(g->alpha1.p + Np, 0, 128 * sizeof(double), g->stream));
+        g->alpha_tail_Y = g->alphaY.p; g->alpha_tail_1 = g->alpha1.p; g->alpha_tail_Np = Np;
+    }
+    IBO_TRY(g->tmp.ensure(alpha_scratch(Np) + (size_t)Np));     // launch_alpha's scratch, then one vector (ibo_gp_extend)
+    return g->info.ensure(1);
+}
 
 // stage observations (optionally in reverse order) and size every buffer
 static int stage_data(ibo_gp *g, int N, int D, const double *X, const double *Y, bool reverse)
@@ -55,21 +71,9 @@ static int stage_data(ibo_gp *g, int N, int D, const double *X, const double *Y,
     g->reversed = reverse;
     g->R_valid = false;             // new points: R is formed again when someone asks (ensure_R)
     const int Np = g->Npad, DP = g->DP;
-    size_t nn = (size_t)Np * Np;
     IBO_TRY(g->Xp.ensure((size_t)Np * DP)); IBO_TRY(g->Xs.ensure((size_t)Np * DP)); IBO_TRY(g->ak.ensure(Np));
     IBO_TRY(g->XA.ensure((size_t)((Np + 127) / 128 * 8) * ((D + 5) / 4) * 64));
-    IBO_TRY(g->Y.ensure(Np));
-    IBO_TRY(g->L.ensure(nn)); IBO_TRY(g->W.ensure(nn));
-    IBO_TRY(g->T.ensure(nn)); IBO_TRY(g->Wp.ensure(nn)); IBO_TRY(g->diag64.ensure(diag64_size(Np)));
-    // sweep2's stages cover rows up to the next multiple of 128: the tail of both alpha vectors stays zero
-    IBO_TRY(g->alphaY.ensure((size_t)Np + 128)); IBO_TRY(g->alpha1.ensure((size_t)Np + 128));
-    if (g->alpha_tail_Y != g->alphaY.p || g->alpha_tail_1 != g->alpha1.p || g->alpha_tail_Np != Np) {     // (nothing writes there)
-        HIP_TRY(hipMemsetAsync(g->alphaY.p + Np, 0, 128 * sizeof(double), g->stream));
-        HIP_TRY(hipMemsetAsync(g->alpha1.p + Np, 0, 128 * sizeof(double), g->stream));
-        g->alpha_tail_Y = g->alphaY.p; g->alpha_tail_1 = g->alpha1.p; g->alpha_tail_Np = Np;
-    }
-    IBO_TRY(g->tmp.ensure(alpha_scratch(Np) + (size_t)Np));     // launch_alpha's scratch, then one vector (ibo_gp_extend)
-    IBO_TRY(g->info.ensure(1));
+    IBO_TRY(fit_buffers(g, Np));
     // staged through the handle's pinned buffer: the copies are truly asynchronous and nothing has to be waited for before the fit's
     // kernels are queued (a pageable source is staged by the runtime and had to be kept alive by a stream synchronise: ~25 us of a 0.37 ms fit)
     IBO_TRY(ensure_pinned(g, (size_t)Np * DP + Np));
@@ -91,9 +95,9 @@ static int stage_data(ibo_gp *g, int N, int D, const double *X, const double *Y,
 }
 
 // synchronises; a failed pivot leaves the handle unfitted
-static int check_info(ibo_gp *g, int *info)
+static int check_info(ibo_gp *g, int *info, const char *noun = "matrix")
 {
-    const int rc = factor_info(g->info.p, g->stream, "matrix", info);
+    const int rc = factor_info(g->info.p, g->stream, noun, info);
     if (rc != IBO_OK) g->fitted = false;
     return rc;
 }
@@ -134,16 +138,35 @@ int fit_begin(ibo_gp *g, int ktype, int N, int D, const double *X, const double 
     g->dot_form = dot_form_ok(*kp, X, N, D);
     return IBO_OK;
 }
-// ... and ends with, W in place: both alpha vectors, the info word (synchronises), the span fit0 -> fit1
-static int fit_end(ibo_gp *g, int N, bool plain, int *info)
+// ... and ends with, W in place, in two halves (a caller that times its stages marks the stream between them): both alpha vectors, queued ...
+int fit_alpha(ibo_gp *g, int N)
 {
     KERNEL_TRY(launch_alpha(g->W.p, N, g->Npad, g->Y.p, g->tmp.p, g->alphaY.p, g->alpha1.p, g->stream));
+    return IBO_OK;
+}
+// ... then the info word (synchronises; noun: what the message calls the matrix) and the span fit0 -> fit1
+int fit_end(ibo_gp *g, bool plain, const char *noun, int *info)
+{
     HIP_TRY(hipEventRecord(g->fit1, g->stream));
-    IBO_TRY(check_info(g, info));
+    IBO_TRY(check_info(g, info, noun));
     IBO_TRY(fit_span(g));
     g->fitted = true;
     g->plain_fit = plain;
     g->fit_epoch++;
+    return IBO_OK;
+}
+
+// A handle's frame for its Npad rows (fit_frame, abi_factor.h, which says why T and W are lent twice): the matrix goes to b->A ...
+int fit_operands(ibo_gp *g, FactorRoute *route, FactorBufs *b)
+{
+    return fit_frame(g->Npad, g->T.p, g->L.p, g->W.p, g->Wp.p, g->T.p, g->W.p, g->diag64.p, g->info.p, g->tall, g->Pk2, route, b);
+}
+// ... and the factorisation and inversion of the matrix in it (N rows its own), queued: T and Wp then trade places
+int fit_invert(ibo_gp *g, FactorRoute route, const FactorBufs &b, int N)
+{
+    IBO_TRY(factor_invert(route, N, g->Npad, b, g->stream));
+    std::swap(g->T, g->Wp);
+    g->L_upper_dirty = true;        // the strict upper blocks of L are scratch until someone asks for L
     return IBO_OK;
 }
 
@@ -152,25 +175,14 @@ static int fit_end(ibo_gp *g, int N, bool plain, int *info)
 int fit_factor(ibo_gp *g, const KParams &kp, int N, double noise, bool have_A, int *info)
 {
     const int Np = g->Npad;
-    const size_t nn = (size_t)Np * Np;
     hipStream_t s = g->stream;
     FactorRoute route;
-    IBO_TRY(factor_route(Np, FACTOR_FIT, &route));
+    FactorBufs b;
     HIP_TRY(hipEventRecord(g->fit0, s));
-    // Out of place on every route: the matrix in T, the factor into L; (L^-1)^T or the doubling's scratch in Wp, W's packed copy into T
-    // -- free by then --, and T and Wp then trade places.  Super-panels: matrix and identity are the halves of ONE tall buffer.  The
-    // two-level order borrows W as its packed-update store (free until the inversion).
-    FactorBufs b = {};
-    b.A = g->T.p; b.eye = g->W.p; b.Pk = g->W.p;
-    if (route == ROUTE_RIDE_SUPER) {
-        IBO_TRY(g->tall.ensure(2 * nn)); IBO_TRY(g->Pk2.ensure(2 * nn));
-        b.A = g->tall.p; b.eye = g->tall.p + nn; b.Pk = g->Pk2.p;
-    }
-    b.L = g->L.p; b.Et = g->Wp.p; b.W = g->W.p; b.Wp = g->T.p; b.d64 = g->diag64.p; b.info = g->info.p;
+    IBO_TRY(fit_operands(g, &route, &b));
     // R's identity-padded working copy and in the same pass, on the ride-along, the identity it starts from; and the cleared info word
     // (GP.R itself is not written here: 33 MB of stores at N = 2048 that only ibo_gp_get_R and ibo_pref_finish read -- ensure_R;
     // stage_data marked it stale)
-    b.info_zero = true;
     b.eye_ready = !have_A && route != ROUTE_TWO_LEVEL;
     if (!have_A)
         KERNEL_TRY(launch_cov_fit(kp, N, g->Xp.p, g->DP, IBO_DIAG_UNIT_PLUS_NOISE, noise, b.A, Np, b.eye_ready ? b.eye : nullptr, g->info.p, s));
@@ -178,10 +190,9 @@ int fit_factor(ibo_gp *g, const KParams &kp, int N, double noise, bool have_A, i
         HIP_TRY(hipMemsetAsync(g->info.p, 0, sizeof(int), s));
         KERNEL_TRY(launch_pad_copy(g->A.p, N, N, b.A, Np, 1.0, s));
     }
-    IBO_TRY(factor_invert(route, N, Np, b, s));
-    std::swap(g->T, g->Wp);
-    g->L_upper_dirty = true;        // the strict upper blocks of L are scratch until someone asks for L
-    return fit_end(g, N, !have_A, info);
+    IBO_TRY(fit_invert(g, route, b, N));
+    IBO_TRY(fit_alpha(g, N));
+    return fit_end(g, !have_A, "matrix", info);
 }
 
 static int fit_impl(ibo_gp *g, int ktype, int N, int D, const double *X, const double *Y,
@@ -356,7 +367,8 @@ int fit_from_inverse(ibo_gp *g, int ktype, int N, int D, const double *X, const 
     KERNEL_TRY(launch_pad_copy(g->A.p, N, N, g->L.p, Np, 1.0, s));
     KERNEL_TRY(launch_cholesky(g->L.p, Np, g->diag64.p, g->info.p, s));          // (FACTOR_IN_PLACE's route; only the factor is wanted)
     KERNEL_TRY(launch_pack_w(g->L.p, N, Np, 1, g->W.p, g->Wp.p, s));
-    return fit_end(g, N, false, nullptr);
+    IBO_TRY(fit_alpha(g, N));
+    return fit_end(g, false, "matrix", nullptr);
 }
 
 extern "C" int ibo_gp_set_y(ibo_gp_t *g, const double *Y_host)

@@ -26,6 +26,7 @@ struct ibo_ggp {
     KParams kp;
     double noise = 0.0, maxY = 0.0;
     DevBuf<double> X, gnoise;         // N x D, D
+    void release() { X.release(); gnoise.release(); }
 };
 
 namespace {
@@ -38,18 +39,6 @@ struct GgpRun {
     double *mu_dev = nullptr, *s2_dev = nullptr;
     RowPipeline rows;
 };
-
-// What the evaluating entries check alike: the device first, the arguments, the handle's state.
-int ggp_check(ibo_ggp *h, bool ptrs_ok, int64_t M, int acq, int erf_mode, bool none_ok)
-{
-    IBO_TRY(use_device(h ? h->device : 0));
-    if (!h || !ptrs_ok) return fail(IBO_ERR_ARG, "NULL argument");
-    if (M < 1) return fail(IBO_ERR_ARG, "M=%lld", (long long)M);
-    if (acq < 0 || acq > (none_ok ? IBO_ACQ_NONE : IBO_ACQ_UCB)) return fail(IBO_ERR_ARG, "unknown acquisition %d", acq);
-    if (erf_mode != IBO_ERF_LIBM && erf_mode != IBO_ERF_NR) return fail(IBO_ERR_ARG, "unknown erf flavour %d", erf_mode);
-    if (!h->fitted) return fail(IBO_ERR_STATE, "gradient model before a successful fit");
-    return IBO_OK;
-}
 
 int ggp_begin(ibo_ggp *h, GgpRun &st, int acq, double parm, int erf_mode, double clamp_lo, double ymax)
 {
@@ -91,7 +80,7 @@ extern "C" int ibo_ggp_destroy(ibo_ggp_t *h)
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
     g_pool_quiet = true;
-    h->X.release(); h->gnoise.release();
+    h->release();
     g_pool_quiet = false;
     const int rc = ibo_gp_destroy(h->g);
     delete h;
@@ -124,17 +113,13 @@ extern "C" int ibo_ggp_fit(ibo_ggp_t *h, int ktype, int N, int D, const double *
     ibo_gp *g = h->g;
     hipStream_t s = g->stream;
     const int P = N * (D + 1), Np = round_up(P, 64);
-    const size_t nn = (size_t)Np * Np;
     h->fitted = false; g->fitted = false;
     h->N = N; h->D = D; h->P = P; h->kp = kp; h->noise = noise;
     // the frame: P rows, no points of its own, no prior
     g->N = P; g->D = D; g->Npad = Np; g->DP = D; g->kp = kp; g->kp_fit = kp; g->noise = noise; g->nb = 0;
     g->reversed = false; g->R_valid = false; g->st_gen = 0; g->pw.ready = false;
     IBO_TRY(h->X.ensure((size_t)N * D)); IBO_TRY(h->gnoise.ensure((size_t)D));
-    IBO_TRY(g->Y.ensure(Np)); IBO_TRY(g->L.ensure(nn)); IBO_TRY(g->W.ensure(nn)); IBO_TRY(g->T.ensure(nn)); IBO_TRY(g->Wp.ensure(nn));
-    IBO_TRY(g->diag64.ensure(diag64_size(Np)));
-    IBO_TRY(g->alphaY.ensure((size_t)Np + 128)); IBO_TRY(g->alpha1.ensure((size_t)Np + 128));
-    IBO_TRY(g->tmp.ensure(alpha_scratch(Np) + (size_t)Np)); IBO_TRY(g->info.ensure(1));
+    IBO_TRY(fit_buffers(g, Np));
     // [Y; G] interleaved point by point, through the frame's pinned buffer (see stage_data in abi_fit.hip)
     IBO_TRY(ensure_pinned(g, (size_t)N * D + D + Np));
     double *xp = g->pin, *gp = xp + (size_t)N * D, *yp = gp + D;
@@ -151,38 +136,25 @@ extern "C" int ibo_ggp_fit(ibo_ggp_t *h, int ktype, int N, int D, const double *
     HIP_TRY(hipMemcpyAsync(h->X.p, xp, sizeof(double) * (size_t)N * D, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(h->gnoise.p, gp, sizeof(double) * D, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(g->Y.p, yp, sizeof(double) * Np, hipMemcpyHostToDevice, s));
-    // the buffers of a plain fit (fit_factor in abi_fit.hip): the matrix in T, the factor into L, W's packed copy into T, T and Wp trade places
+    // the frame and the tail of a plain fit (abi_fit.hip), around this model's own assembly
     FactorRoute route;
-    IBO_TRY(factor_route(Np, FACTOR_FIT, &route));
-    FactorBufs b = {};
-    b.A = g->T.p; b.eye = g->W.p; b.Pk = g->W.p;
-    if (route == ROUTE_RIDE_SUPER) {
-        IBO_TRY(g->tall.ensure(2 * nn)); IBO_TRY(g->Pk2.ensure(2 * nn));
-        b.A = g->tall.p; b.eye = g->tall.p + nn; b.Pk = g->Pk2.p;
-    }
-    b.L = g->L.p; b.Et = g->Wp.p; b.W = g->W.p; b.Wp = g->T.p; b.d64 = g->diag64.p; b.info = g->info.p;
-    b.info_zero = true; b.eye_ready = false;
+    FactorBufs b;
+    IBO_TRY(fit_operands(g, &route, &b));                        // (eye_ready false: the factorisation writes the identity)
     StageClock clock;
-    clock.s = s; clock.ms = t_ggp_ms; clock.on = g_ggp_timing != 0;
-    if (clock.on)
-        for (int k = 0; k < 4; k++) HIP_TRY(hipEventCreate(&clock.ev[k]));
+    IBO_TRY(clock.make(s, t_ggp_ms, g_ggp_timing != 0));
     HIP_TRY(hipMemsetAsync(g->info.p, 0, sizeof(int), s));
     HIP_TRY(hipEventRecord(g->fit0, s));
     IBO_TRY(clock.mark(0));
     KERNEL_TRY(launch_gradobs_assemble(kp, h->X.p, N, 1.0 + noise, h->gnoise.p, b.A, Np, s));
     IBO_TRY(clock.mark(1));
-    IBO_TRY(factor_invert(route, P, Np, b, s));
-    std::swap(g->T, g->Wp);
-    g->L_upper_dirty = true;
+    IBO_TRY(fit_invert(g, route, b, P));
     IBO_TRY(clock.mark(2));
-    KERNEL_TRY(launch_alpha(g->W.p, P, Np, g->Y.p, g->tmp.p, g->alphaY.p, g->alpha1.p, s));
-    IBO_TRY(clock.mark(3));
-    HIP_TRY(hipEventRecord(g->fit1, s));
-    IBO_TRY(factor_info(g->info.p, s, "gradient-observation matrix", info));       // synchronises; a failed pivot leaves the handle unfitted
-    HIP_TRY(hipEventElapsedTime(&g->fit_ms, g->fit0, g->fit1));
-    gpu_time_add(g->device, g->fit_ms);
-    IBO_TRY(clock.account(0, 1, GGP_ST_ASSEMBLE)); IBO_TRY(clock.account(1, 2, GGP_ST_FACTOR)); IBO_TRY(clock.account(2, 3, GGP_ST_ALPHA));
-    g->fitted = true; g->plain_fit = false; g->fit_epoch++;
+    IBO_TRY(fit_alpha(g, P));
+    IBO_TRY(clock.mark(3));                                      // (on the stream before fit_end waits for anything)
+    IBO_TRY(fit_end(g, false, "gradient-observation matrix", info));      // synchronises; a failed pivot leaves the handle unfitted
+    const int stage[3] = {GGP_ST_ASSEMBLE, GGP_ST_FACTOR, GGP_ST_ALPHA};
+    for (int k = 0; k < 3; k++)
+        if (const int rc = clock.account(k, k + 1, stage[k])) { g->fitted = false; return rc; }      // (as before: neither handle counts as fitted)
     h->fitted = true;
     return IBO_OK;
 }
@@ -214,7 +186,7 @@ extern "C" int ibo_ggp_get_L(ibo_ggp_t *h, double *L_host)
 extern "C" int ibo_ggp_acq_batch(ibo_ggp_t *h, int64_t M, const double *Q_host, int acq, double parm, int erf_mode,
                                  double clamp_lo, double ymax, double *mu_host, double *s2_host, double *acq_host)
 {
-    IBO_TRY(ggp_check(h, Q_host != nullptr, M, acq, erf_mode, true));
+    IBO_TRY(wrapped_check(h, "gradient", Q_host != nullptr, M, acq, erf_mode, true));
     if (!mu_host && !s2_host && !acq_host) return fail(IBO_ERR_ARG, "every output is NULL");
     HIP_TRY(hipEventRecord(h->g->ev0, h->g->stream));
     GgpRun st;
@@ -227,7 +199,7 @@ extern "C" int ibo_ggp_acq_sweep(ibo_ggp_t *h, int64_t M, const double *cand_dev
                                  double clamp_lo, double ymax, int64_t index_base,
                                  double *mu_dev, double *s2_dev, double *acq_dev, double *best_val, int64_t *best_idx)
 {
-    IBO_TRY(ggp_check(h, cand_dev != nullptr, M, acq, erf_mode, true));
+    IBO_TRY(wrapped_check(h, "gradient", cand_dev != nullptr, M, acq, erf_mode, true));
     if (!mu_dev && !s2_dev && !acq_dev && !best_val && !best_idx) return fail(IBO_ERR_ARG, "every output is NULL");
     HIP_TRY(hipEventRecord(h->g->ev0, h->g->stream));
     GgpRun st;
@@ -240,7 +212,7 @@ extern "C" int ibo_ggp_direct_max(ibo_ggp_t *h, int D, const double *lb, const d
                                   double clamp_lo, int maxiter, int maxtime, int maxsample, int compat,
                                   double *opt, double *optx, int64_t *nsamples)
 {
-    IBO_TRY(ggp_check(h, lb && ub, 1, acq, erf_mode, false));
+    IBO_TRY(wrapped_check(h, "gradient", lb && ub, 1, acq, erf_mode, false));
     if (!opt && !optx && !nsamples) return fail(IBO_ERR_ARG, "every output is NULL");
     if (D != h->D) return fail(IBO_ERR_ARG, "bounds have %d dimensions, the model has %d", D, h->D);
     GgpRun st;
@@ -253,7 +225,5 @@ extern "C" int ibo_ggp_direct_max(ibo_ggp_t *h, int D, const double *lb, const d
 
 extern "C" int ibo_ggp_stage_ms(double *ms, int reset)
 {
-    if (ms) memcpy(ms, t_ggp_ms, sizeof(t_ggp_ms));
-    if (reset) memset(t_ggp_ms, 0, sizeof(t_ggp_ms));
-    return IBO_OK;
+    return read_stage_sums(t_ggp_ms, IBO_GGP_STAGES, ms, reset);
 }

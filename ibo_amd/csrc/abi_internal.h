@@ -1,9 +1,9 @@
 // abi_internal.h -- what the translation units behind the C ABI (include/ibo_abi.h) share: the error channel, the option switches, the
 // per-device memory pool and its buffer type, the handle (struct ibo_gp) and the helpers one unit lends another.
 //   abi_core.hip    library / options / device memory / pools / handle life cycle
-//   abi_fit.hip     fit, block extension, removal of rows, set_y, prior, accessors, ibo_cov_matrix
+//   abi_fit.hip     fit (its pieces -- buffers, frame, tail -- serve abi_gradobs.hip's fit too), block extension, removal of rows, set_y, prior, accessors, ibo_cov_matrix
 //   abi_pref.hip    the preference GP's device steps (ibo_pref_*)
-//   abi_factor.hip  factor-and-invert for all of these and the gradients: route choice, the routine, the info word; ibo_spd_* (abi_factor.h)
+//   abi_factor.hip  factor-and-invert for all of these and the gradients: route choice, the fit's frame, the routine, the info word; ibo_spd_* (abi_factor.h)
 //   abi_sweep.hip   candidate sweeps: the routes, run_sweep, the sweep entries
 //   abi_batch.hip   host batches, query-point gradients, joint posterior and draws, DIRECT on a GPU objective
 //   abi_cacq.hip    the constrained acquisition (ibo_cacq_*)
@@ -18,8 +18,9 @@
 //   abi_moments.hip the moments pipeline of abi_cacq, abi_ehvi, abi_mes and abi_sparse: the plain sweeps of a chunk into scratch, the
 //                   stream rule, the padded tail, host batch, device sweep (abi_moments.h)
 //                   (these twelve are the evaluation units: what they share among themselves is in abi_eval.h)
-//   abi_nlml.hip    marginal-likelihood grid and gradient, ibo_trim
+//   abi_nlml.hip    marginal-likelihood grid and the three gradients (one prepare step, one rule for resident data), ibo_trim
 //   abi_legacy.hip  libego's symbols (acqmaxGP, direct, logCDFs) and ibo_direct_host
+// A struct that owns DevBufs has a release() directly under its member list, which ibo_trim and the destroy entries call.
 // There is no CPU fallback anywhere behind this header: without a gfx950 device every compute entry point returns IBO_ERR_NO_DEVICE.
 #pragma once
 #include "../../include/ibo_abi.h"
@@ -162,10 +163,20 @@ struct ibo_gp {
         DevBuf<int> info;
         bool ready = false;
         unsigned epoch = 0; int N = 0, Npad = 0;     // the model ibo_pref_begin ran on (pref_owned): its fit_epoch, rows and padded rows
+        void release() { for (DevBuf<double> *b : {&Rinv, &A, &Lh, &E, &Et, &d64, &vec, &tmp, &val}) b->release(); lin.release(); info.release(); }
     } pw;
     // prior
     int nb = 0; double ptheta = 0.0;
     DevBuf<double> pmeans, pbeta, plowerb, pwidth;
+    // every DevBuf above, back to the pool (ibo_gp_destroy; streams, events and the pinned block are its own business).  Keep THIS order and
+    // append: the order in which blocks return to the pool decides where the next handle's buffers lie
+    void release()
+    {
+        for (DevBuf<double> *b : {&Xp, &Xs, &ak, &XA, &Y, &R, &A, &L, &W, &T, &Wp, &diag64, &alphaY, &alpha1, &tmp, &cand, &outs, &excl, &qpart, &mupart, &partv, &res_v}) b->release();
+        parti.release(); res_i.release(); state.release(); small_ws.release(); grad_ws.release(); grad_cand.release(); grad_out.release();
+        tile_done.release(); tile_ub.release(); part_words.release(); tile_rows.release(); tile_sel.release(); done_count.release(); tall.release(); Pk2.release();
+        pw.release(); info.release(); pmeans.release(); pbeta.release(); plowerb.release(); pwidth.release();
+    }
 };
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
@@ -190,6 +201,12 @@ int ensure_R(ibo_gp *g);                                                        
 int fit_begin(ibo_gp *g, int ktype, int N, int D, const double *X, const double *Y, const double *hyper, int nhyper, double sf2,
               double noise, bool reverse, KParams *kp);                                                   // abi_fit.hip: what every fit starts with (the staging)
 int fit_factor(ibo_gp *g, const KParams &kp, int N, double noise, bool have_A, int *info);                // abi_fit.hip: a fit after staging (have_A: of g->A)
+// abi_fit.hip, what fit_factor is made of, for the model that assembles its own matrix (abi_gradobs.hip): the factor-side buffers of an Np-row
+// frame; the tail (between them fit_operands and fit_invert, abi_factor.h): both alpha vectors, queued; then the info word ("<noun> is not
+// positive definite"; synchronises), the span fit0 -> fit1, fitted / plain_fit / fit_epoch
+int fit_buffers(ibo_gp *g, int Np);
+int fit_alpha(ibo_gp *g, int N);
+int fit_end(ibo_gp *g, bool plain, const char *noun, int *info);
 int fit_from_inverse(ibo_gp *g, int ktype, int N, int D, const double *X, const double *Y,
                      const double *hyper, int nhyper, double sf2, double noise, const double *invR);      // abi_fit.hip
 int direct_on_gp(ibo_gp *g, int D, const double *lb, const double *ub, int acq, double parm, int erf_mode,

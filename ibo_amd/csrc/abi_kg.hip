@@ -131,7 +131,5 @@ extern "C" int ibo_kg_direct_max(ibo_gp_t *g, int nref, const double *ref_host, 
 
 extern "C" int ibo_kg_stage_ms(double *ms, int reset)
 {
-    if (ms) memcpy(ms, t_kg_ms, sizeof(t_kg_ms));
-    if (reset) memset(t_kg_ms, 0, sizeof(t_kg_ms));
-    return IBO_OK;
+    return read_stage_sums(t_kg_ms, IBO_KG_STAGES, ms, reset);
 }

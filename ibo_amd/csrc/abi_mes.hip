@@ -175,7 +175,5 @@ extern "C" int ibo_mes_maxcdf(ibo_gp_t *gp, int64_t M, const double *cand_dev, i
 
 extern "C" int ibo_mes_scan_ms(double *ms, int reset)
 {
-    if (ms) *ms = t_mes_ms;
-    if (reset) t_mes_ms = 0.0;
-    return IBO_OK;
+    return read_stage_sums(&t_mes_ms, 1, ms, reset);
 }

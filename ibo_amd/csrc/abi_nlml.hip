@@ -1,6 +1,7 @@
 // abi_nlml.hip -- the marginal-likelihood side of the C ABI: the batched theta-grid, one value + gradient (of the plain model, of leave-one-out
 // and of the gradient-observation model) and ibo_trim (which owns their per-device workspaces).
 #include "abi_factor.h"
+#include "abi_eval.h"       // (the stage clock)
 #include "loo.h"
 #include "gradobs.h"
 
@@ -13,22 +14,47 @@ struct NlmlWorkspace {
     int pad_Np = 0, pad_N = 0, pad_B = 0;           // and for which geometry
     hipStream_t streams[4] = {nullptr, nullptr, nullptr, nullptr};     // sub-batches of a grid run side by side (created on first use, kept)
     hipEvent_t t0[4] = {nullptr, nullptr, nullptr, nullptr}, t1[4] = {nullptr, nullptr, nullptr, nullptr};     // a sub-batch's span on its stream (ibo_gpu_time_ms)
+    void release()                                  // (ibo_trim; the streams and events are its own business)
+    { for (DevBuf<double> *b : {&dX, &dY, &dout, &dL, &d64, &dP}) b->release(); dinfo.release(); dflags.release(); dkp.release(); padded = nullptr; }
 };
 static NlmlWorkspace g_nlml_ws[16];
 static const int kSyrk3From = 1792;          // rows from which ibo_nlml_grad forms K^-1 = W^T W on the packed-operand kernel (launch_syrk3)
+// data a learning loop sends dozens of times (the same X and Y with another theta): kept on the device with a host mirror, compared by content
+struct Resident {
+    DevBuf<double> d;
+    std::vector<double> host;                       // what d holds (np doubles), or empty: nothing known
+    // d = the n values at src, zeros behind them up to np; uploaded unless the mirror has np entries of which the first n are src's
+    int put(const double *src, size_t n, size_t np)
+    {
+        IBO_TRY(d.ensure(np));
+        if (host.size() == np && memcmp(host.data(), src, sizeof(double) * n) == 0) return IBO_OK;
+        std::vector<double> v(np, 0.0);
+        memcpy(v.data(), src, sizeof(double) * n);
+        host.clear();                               // (not valid while the copy is in flight or if it fails)
+        HIP_TRY(hipMemcpy(d.p, v.data(), sizeof(double) * np, hipMemcpyHostToDevice));
+        host.swap(v);
+        return IBO_OK;
+    }
+    void release() { d.release(); host.clear(); }   // (nothing of this data is on the device any more)
+};
 struct GradWorkspace {
-    DevBuf<double> dX, dY, dL, dW, dT, dKi, d64, dal, da1, tmp, dpart, dout, dpiece, tall, Pk2;     // tall, Pk2: the super-panel order's (launch_cholesky_super)
+    DevBuf<double> dL, dW, dT, dKi, d64, dal, da1, tmp, dpart, dout, dpiece, tall, Pk2;     // tall, Pk2: the super-panel order's (launch_cholesky_super)
     DevBuf<double> lpart, lout, lmu;                // ibo_loo_grad: one pass' partial sums, [gradient, value], [mu_-i, s2_-i]
     DevBuf<int> dinfo, dtasks, dsums;
     int plan_Np = 0, ntasks = 0, nsums = 0;         // launch_syrk3's lists on the device, for this Npad
     hipEvent_t t0 = nullptr, t1 = nullptr;          // the evaluation's span on the device (ibo_gpu_time_ms)
-    // a learning loop calls with the same data and another theta dozens of times: what is on the device is kept (compared by content) and
-    // the results come back through one pinned block behind one synchronisation
-    std::vector<double> hostX, hostY;
-    double *pin = nullptr;                          // kGradPin doubles: the results, the info word at kGradPinInfo
+    Resident X, Y;                                  // the plain entries' data: N x D; the targets, padded to the frame
+    double *pin = nullptr;                          // kGradPin doubles: the results come back through it, the info word at kGradPinInfo, behind ONE synchronisation
     // ibo_ggp_nlml_grad's data, in buffers of their own: the plain entries' resident X and Y are never touched
-    DevBuf<double> gX, gT, gN, gpart, gout;         // X, the interleaved targets (padded), gnoise, the contraction's partial sums, the results
-    std::vector<double> hostGX, hostGT, hostGN;
+    Resident gX, gT, gN;                            // X, the interleaved targets (padded), gnoise
+    DevBuf<double> gpart, gout;                     // the contraction's partial sums, the results
+    void release()                                  // (ibo_trim; the events stay, the pinned block is its own business)
+    {
+        for (DevBuf<double> *b : {&dL, &dW, &dT, &dKi, &d64, &dal, &da1, &tmp, &dpart, &dout, &dpiece, &tall, &Pk2, &lpart, &lout, &lmu, &gpart, &gout}) b->release();
+        for (DevBuf<int> *b : {&dinfo, &dtasks, &dsums}) b->release();
+        for (Resident *r : {&X, &Y, &gX, &gT, &gN}) r->release();
+        plan_Np = 0;                                // (launch_syrk3's lists went with dtasks / dsums)
+    }
 };
 static const int kGradPin = 2 * IBO_GRAD_MAX + 8, kGradPinInfo = 2 * IBO_GRAD_MAX + 6;     // (ibo_ggp_nlml_grad: ngrad + 1 + D + 2 results)
 static GradWorkspace g_grad_ws[16];
@@ -38,19 +64,13 @@ extern "C" int ibo_trim(int device)
     IBO_TRY(use_device(device));
     std::lock_guard<std::mutex> lk(g_dev_mu[device & 15]);
     NlmlWorkspace &ws = g_nlml_ws[device & 15];
-    ws.dX.release(); ws.dY.release(); ws.dout.release(); ws.dL.release(); ws.d64.release(); ws.dP.release(); ws.dinfo.release(); ws.dflags.release(); ws.dkp.release();
-    ws.padded = nullptr;
+    ws.release();
     for (int g = 0; g < 4; g++) if (ws.streams[g]) {
         (void)hipStreamDestroy(ws.streams[g]); ws.streams[g] = nullptr;
         if (ws.t0[g]) { (void)hipEventDestroy(ws.t0[g]); (void)hipEventDestroy(ws.t1[g]); ws.t0[g] = ws.t1[g] = nullptr; }
     }
     GradWorkspace &gw = g_grad_ws[device & 15];
-    gw.dX.release(); gw.dY.release(); gw.dL.release(); gw.dW.release(); gw.dT.release(); gw.dKi.release(); gw.d64.release();
-    gw.dal.release(); gw.da1.release(); gw.tmp.release(); gw.dpart.release(); gw.dout.release(); gw.dinfo.release();
-    gw.dpiece.release(); gw.dtasks.release(); gw.dsums.release(); gw.plan_Np = 0; gw.tall.release(); gw.Pk2.release();
-    gw.lpart.release(); gw.lout.release(); gw.lmu.release();
-    gw.gX.release(); gw.gT.release(); gw.gN.release(); gw.gpart.release(); gw.gout.release();
-    gw.hostX.clear(); gw.hostY.clear(); gw.hostGX.clear(); gw.hostGT.clear(); gw.hostGN.clear();      // (dX / dY went back to the pool: nothing of this data is on the device any more)
+    gw.release();
     if (gw.pin) { (void)hipHostFree(gw.pin); gw.pin = nullptr; }
     sgp_grad_trim(device);                           // (ibo_sgp_nlml_grad's private handle)
     pool_trim(device);
@@ -204,27 +224,17 @@ extern "C" int ibo_nlml_grid(int device, int ktype, int N, int D, const double *
 }
 
 // The frame of one evaluation on the device's GradWorkspace (the caller holds its mutex): the buffers of an Np-row factorisation, the pinned
-// result block, the fit's route for Np rows and the operands factor_invert takes on it -- the matrix in dT (in super-panels: in the tall
-// buffer, with the ride-along's identity), the factor into dL, (L^-1)^T (or the doubling's scratch) in dKi, W into dW -- no packed copy:
-// nothing sweeps here; the two-level order is lent no packed-update store.  The caller sets b->eye_ready.
+// result block and the fit's frame for Np rows (fit_frame, abi_factor.h) -- the matrix in dT, the factor into dL, (L^-1)^T (or the doubling's
+// scratch) in dKi, W into dW -- no packed copy: nothing sweeps here; the two-level order is lent no packed-update store.
 static int grad_frame(GradWorkspace &ws, int Np, FactorRoute *route, FactorBufs *b)
 {
     const size_t nn = (size_t)Np * Np;
     // workspace kept between calls (BFGS calls this dozens of times; five N^2 buffers allocated and freed per
     // call cost as much as the arithmetic); ibo_trim() releases it
     IBO_TRY(ws.dL.ensure(nn)); IBO_TRY(ws.dW.ensure(nn)); IBO_TRY(ws.dT.ensure(nn)); IBO_TRY(ws.dKi.ensure(nn)); IBO_TRY(ws.d64.ensure(diag64_size(Np)));
-    IBO_TRY(ws.dal.ensure(Np)); IBO_TRY(ws.da1.ensure(Np)); IBO_TRY(ws.tmp.ensure(alpha_scratch(Np)));
-    IBO_TRY(ws.dinfo.ensure(1));
+    IBO_TRY(ws.dal.ensure(Np)); IBO_TRY(ws.da1.ensure(Np)); IBO_TRY(ws.tmp.ensure(alpha_scratch(Np))); IBO_TRY(ws.dinfo.ensure(1));
     if (!ws.pin) HIP_TRY(hipHostMalloc((void **)&ws.pin, sizeof(double) * kGradPin, hipHostMallocDefault));
-    IBO_TRY(factor_route(Np, FACTOR_FIT, route));
-    *b = FactorBufs{};
-    b->A = ws.dT.p; b->eye = ws.dW.p;
-    if (*route == ROUTE_RIDE_SUPER) {
-        IBO_TRY(ws.tall.ensure(2 * nn)); IBO_TRY(ws.Pk2.ensure(2 * nn));
-        b->A = ws.tall.p; b->eye = ws.tall.p + nn; b->Pk = ws.Pk2.p;
-    }
-    b->L = ws.dL.p; b->Et = ws.dKi.p; b->W = ws.dW.p; b->d64 = ws.d64.p; b->info = ws.dinfo.p;
-    b->info_zero = true;
+    IBO_TRY(fit_frame(Np, ws.dT.p, ws.dL.p, ws.dW.p, ws.dKi.p, nullptr, nullptr, ws.d64.p, ws.dinfo.p, ws.tall, ws.Pk2, route, b));
     if (!ws.t0) { HIP_TRY(hipEventCreate(&ws.t0)); HIP_TRY(hipEventCreate(&ws.t1)); }
     return IBO_OK;
 }
@@ -266,35 +276,40 @@ static int grad_factor(GradWorkspace &ws, FactorRoute route, const FactorBufs &b
     return IBO_OK;
 }
 
-// What ibo_nlml_grad and ibo_loo_grad share, on the device's one GradWorkspace (the caller holds its mutex): X and Y resident (compared by
-// content), the covariance matrix, then grad_factor -- queued on the null stream behind ws.t0, nothing waited for.
-static int grad_prepare(GradWorkspace &ws, const KParams &kp, int N, int D, const double *X, const double *Y, double noise, double *scalars,
-                        const double **Kinv_out)
+// What the three gradient entries share, on the device's one GradWorkspace (the caller holds its mutex): the data resident, the frame of the
+// N-row matrix with targets y, then -- queued on the null stream behind ws.t0, nothing waited for -- the caller's assembly into b.A and
+// grad_factor.  one_pass: the assembly clears the info word and, where b.eye_ready, writes the identity to b.eye (launch_cov_fit); else the word
+// is cleared here and the factorisation writes the identity.  clock: marks 0 .. 3 around assembly, factorisation with alpha, and the product.
+struct ResidentPut { Resident &r; const double *src; size_t n, np; };
+template <typename Assemble>
+static int grad_prepare(GradWorkspace &ws, std::initializer_list<ResidentPut> data, int N, int Np, const Resident &y, bool one_pass,
+                        const Assemble &assemble, StageClock &clock, double *scalars, const double **Kinv_out)
 {
-    const int Np = round_up(N, 64);
-    DevBuf<double> &dX = ws.dX, &dY = ws.dY;
-    IBO_TRY(dX.ensure((size_t)N * D)); IBO_TRY(dY.ensure(Np));
+    for (const ResidentPut &p : data) IBO_TRY(p.r.put(p.src, p.n, p.np));
     FactorRoute route;
     FactorBufs b;
     IBO_TRY(grad_frame(ws, Np, &route, &b));
     hipStream_t s = nullptr;
-    if (ws.hostX.size() != (size_t)N * D || memcmp(ws.hostX.data(), X, sizeof(double) * N * D) != 0) {
-        ws.hostX.clear();                            // (not valid while the copy is in flight or if it fails)
-        HIP_TRY(hipMemcpy(dX.p, X, sizeof(double) * N * D, hipMemcpyHostToDevice));
-        ws.hostX.assign(X, X + (size_t)N * D);
-    }
-    if (ws.hostY.size() != (size_t)Np || memcmp(ws.hostY.data(), Y, sizeof(double) * N) != 0) {
-        std::vector<double> yp(Np, 0.0);
-        for (int i = 0; i < N; i++) yp[i] = Y[i];
-        ws.hostY.clear();
-        HIP_TRY(hipMemcpy(dY.p, yp.data(), sizeof(double) * Np, hipMemcpyHostToDevice));
-        ws.hostY.swap(yp);
-    }
-    const bool fused = route != ROUTE_TWO_LEVEL;
-    b.eye_ready = fused;                                 // (launch_cov_fit's one pass)
+    b.eye_ready = one_pass && route != ROUTE_TWO_LEVEL;
+    if (!one_pass) HIP_TRY(hipMemsetAsync(ws.dinfo.p, 0, sizeof(int), s));
     HIP_TRY(hipEventRecord(ws.t0, s));
-    KERNEL_TRY(launch_cov_fit(kp, N, dX.p, D, IBO_DIAG_KERNEL_PLUS_NOISE, noise, b.A, Np, fused ? b.eye : nullptr, ws.dinfo.p, s));
-    return grad_factor(ws, route, b, N, Np, dY.p, scalars, Kinv_out);
+    IBO_TRY(clock.mark(0));
+    IBO_TRY(assemble(b, s));
+    IBO_TRY(clock.mark(1));
+    IBO_TRY(grad_factor(ws, route, b, N, Np, y.d.p, scalars, Kinv_out, clock.ev[2]));
+    return clock.mark(3);
+}
+// ibo_nlml_grad's and ibo_loo_grad's: X and Y resident, the covariance matrix by launch_cov_fit's one pass; untimed
+static int plain_prepare(GradWorkspace &ws, const KParams &kp, int N, int D, const double *X, const double *Y, double noise, double *scalars,
+                         const double **Kinv_out)
+{
+    const int Np = round_up(N, 64);
+    StageClock off;                                  // (every mark a no-op)
+    return grad_prepare(ws, {{ws.X, X, (size_t)N * D, (size_t)N * D}, {ws.Y, Y, (size_t)N, (size_t)Np}}, N, Np, ws.Y, true,
+        [&](const FactorBufs &b, hipStream_t s) -> int {
+            KERNEL_TRY(launch_cov_fit(kp, N, ws.X.d.p, D, IBO_DIAG_KERNEL_PLUS_NOISE, noise, b.A, Np, b.eye_ready ? b.eye : nullptr, ws.dinfo.p, s));
+            return IBO_OK;
+        }, off, scalars, Kinv_out);
 }
 
 // modes / dims -> the derivative spec the contraction kernels take (ngrad = 0: none)
@@ -341,12 +356,12 @@ extern "C" int ibo_nlml_grad(int device, int ktype, int N, int D, const double *
     const int Np = round_up(N, 64);
     const int nblk = ((N + 15) / 16) * ((N + 15) / 16);
     GradWorkspace &ws = g_grad_ws[device & 15];
-    DevBuf<double> &dX = ws.dX, &dal = ws.dal, &dpart = ws.dpart, &dout = ws.dout;
+    DevBuf<double> &dal = ws.dal, &dpart = ws.dpart, &dout = ws.dout;
     IBO_TRY(dpart.ensure((size_t)ngrad * nblk)); IBO_TRY(dout.ensure(ngrad + 2));
     hipStream_t s = nullptr;
     const double *Kinv = nullptr;
-    IBO_TRY(grad_prepare(ws, kp, N, D, X, Y, noise, dout.p + ngrad, &Kinv));
-    KERNEL_TRY(launch_nlml_grad(kp, gs, N, dX.p, D, Kinv, Np, dal.p, dpart.p, dout.p, s));
+    IBO_TRY(plain_prepare(ws, kp, N, D, X, Y, noise, dout.p + ngrad, &Kinv));
+    KERNEL_TRY(launch_nlml_grad(kp, gs, N, ws.X.d.p, D, Kinv, Np, dal.p, dpart.p, dout.p, s));
     IBO_TRY(grad_finish(ws, device, dout.p, ngrad + 2));
     const double *res = ws.pin;
     for (int i = 0; i < ngrad; i++) grad_host[i] = res[i];
@@ -375,10 +390,10 @@ extern "C" int ibo_loo_grad(int device, int ktype, int N, int D, const double *X
     if (gs.nh) IBO_TRY(ws.lpart.ensure(loo_contract_scratch(Np)));
     hipStream_t s = nullptr;
     const double *Kinv = nullptr;
-    IBO_TRY(grad_prepare(ws, kp, N, D, X, Y, noise, nullptr, &Kinv));
+    IBO_TRY(plain_prepare(ws, kp, N, D, X, Y, noise, nullptr, &Kinv));
     double *dmu = ws.lmu.p, *ds2 = ws.lmu.p + Np;
-    KERNEL_TRY(launch_loo_value(Kinv, (size_t)Np, N, ws.dY.p, ws.dal.p, mu_host ? dmu : nullptr, s2_host ? ds2 : nullptr, ws.lout.p + IBO_GRAD_MAX, s));
-    if (gs.nh) KERNEL_TRY(launch_loo_contract(kp, gs, N, Np, ws.dX.p, D, Kinv, ws.dal.p, ws.lpart.p, ws.lout.p, s));
+    KERNEL_TRY(launch_loo_value(Kinv, (size_t)Np, N, ws.Y.d.p, ws.dal.p, mu_host ? dmu : nullptr, s2_host ? ds2 : nullptr, ws.lout.p + IBO_GRAD_MAX, s));
+    if (gs.nh) KERNEL_TRY(launch_loo_contract(kp, gs, N, Np, ws.X.d.p, D, Kinv, ws.dal.p, ws.lpart.p, ws.lout.p, s));
     IBO_TRY(grad_finish(ws, device, ws.lout.p, IBO_GRAD_MAX + 1));
     if (mu_host) HIP_TRY(hipMemcpy(mu_host, dmu, sizeof(double) * N, hipMemcpyDeviceToHost));
     if (s2_host) HIP_TRY(hipMemcpy(s2_host, ds2, sizeof(double) * N, hipMemcpyDeviceToHost));
@@ -412,54 +427,27 @@ extern "C" int ibo_ggp_nlml_grad(int device, int ktype, int N, int D, const doub
     const bool want_grad = gs.nh > 0 || grad_noise_host;
     const int nres = gs.nh + B + 2;                              // the derivatives, the 1 + D noise terms, (t . alpha, sum log L_ii)
     GradWorkspace &ws = g_grad_ws[device & 15];
-    IBO_TRY(ws.gX.ensure((size_t)N * D)); IBO_TRY(ws.gT.ensure(Np)); IBO_TRY(ws.gN.ensure(D)); IBO_TRY(ws.gout.ensure(kGradPin));
+    IBO_TRY(ws.gout.ensure(kGradPin));
     if (want_grad) IBO_TRY(ws.gpart.ensure(gradobs_contract_scratch(N, D)));
-    FactorRoute route;
-    FactorBufs b;
-    IBO_TRY(grad_frame(ws, Np, &route, &b));
     hipStream_t s = nullptr;
-    if (ws.hostGX.size() != (size_t)N * D || memcmp(ws.hostGX.data(), X, sizeof(double) * N * D) != 0) {
-        ws.hostGX.clear();                           // (not valid while the copy is in flight or if it fails)
-        HIP_TRY(hipMemcpy(ws.gX.p, X, sizeof(double) * N * D, hipMemcpyHostToDevice));
-        ws.hostGX.assign(X, X + (size_t)N * D);
+    std::vector<double> tp(Np, 0.0);                 // [Y; G] interleaved point by point, zero in the pad (compared over all Np)
+    for (int i = 0; i < N; i++) {
+        tp[(size_t)i * B] = Y[i];
+        for (int d = 0; d < D; d++) tp[(size_t)i * B + 1 + d] = G[(size_t)i * D + d];
     }
-    {
-        std::vector<double> tp(Np, 0.0);             // [Y; G] interleaved point by point, zero in the pad
-        for (int i = 0; i < N; i++) {
-            tp[(size_t)i * B] = Y[i];
-            for (int d = 0; d < D; d++) tp[(size_t)i * B + 1 + d] = G[(size_t)i * D + d];
-        }
-        if (ws.hostGT.size() != tp.size() || memcmp(ws.hostGT.data(), tp.data(), sizeof(double) * Np) != 0) {
-            ws.hostGT.clear();
-            HIP_TRY(hipMemcpy(ws.gT.p, tp.data(), sizeof(double) * Np, hipMemcpyHostToDevice));
-            ws.hostGT.swap(tp);
-        }
-    }
-    if (ws.hostGN.size() != (size_t)D || memcmp(ws.hostGN.data(), gnoise, sizeof(double) * D) != 0) {
-        ws.hostGN.clear();
-        HIP_TRY(hipMemcpy(ws.gN.p, gnoise, sizeof(double) * D, hipMemcpyHostToDevice));
-        ws.hostGN.assign(gnoise, gnoise + D);
-    }
-    const bool timing = g_ggp_timing != 0;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct EvDrop { hipEvent_t *e; ~EvDrop() { for (int k = 0; k < 5; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } drop{ev};
-    if (timing)
-        for (int k = 0; k < 5; k++) HIP_TRY(hipEventCreate(&ev[k]));
-    b.eye_ready = false;
-    HIP_TRY(hipMemsetAsync(ws.dinfo.p, 0, sizeof(int), s));
-    HIP_TRY(hipEventRecord(ws.t0, s));
-    if (timing) HIP_TRY(hipEventRecord(ev[0], s));
-    KERNEL_TRY(launch_gradobs_assemble(kp, ws.gX.p, N, sf2 + noise, ws.gN.p, b.A, Np, s));
-    if (timing) HIP_TRY(hipEventRecord(ev[1], s));
+    StageClock clock;
+    IBO_TRY(clock.make(s, t_ggp_grad_ms, g_ggp_timing != 0));
     const double *Kinv = nullptr;
     double *res = ws.gout.p;
-    IBO_TRY(grad_factor(ws, route, b, P, Np, ws.gT.p, res + gs.nh + B, want_grad ? &Kinv : nullptr, ev[2]));
-    if (timing) HIP_TRY(hipEventRecord(ev[3], s));
-    if (want_grad) KERNEL_TRY(launch_gradobs_contract(kp, gs, ws.gX.p, N, Kinv, Np, ws.dal.p, noise, ws.gN.p, ws.gpart.p, res, s));
-    if (timing) HIP_TRY(hipEventRecord(ev[4], s));
-    const int rc = grad_finish(ws, device, res, nres);
-    if (timing)
-        for (int k = 0; k < 4; k++) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) t_ggp_grad_ms[k] += ms; }
+    IBO_TRY(grad_prepare(ws, {{ws.gX, X, (size_t)N * D, (size_t)N * D}, {ws.gT, tp.data(), (size_t)Np, (size_t)Np}, {ws.gN, gnoise, (size_t)D, (size_t)D}},
+        P, Np, ws.gT, false, [&](const FactorBufs &b, hipStream_t q) -> int {
+            KERNEL_TRY(launch_gradobs_assemble(kp, ws.gX.d.p, N, sf2 + noise, ws.gN.d.p, b.A, Np, q));
+            return IBO_OK;
+        }, clock, res + gs.nh + B, want_grad ? &Kinv : nullptr));
+    if (want_grad) KERNEL_TRY(launch_gradobs_contract(kp, gs, ws.gX.d.p, N, Kinv, Np, ws.dal.p, noise, ws.gN.d.p, ws.gpart.p, res, s));
+    IBO_TRY(clock.mark(4));
+    const int rc = grad_finish(ws, device, res, nres);           // (synchronises; the sums are taken whatever it says, quietly: rc's text stays)
+    for (int k = 0; clock.on && k < 4; k++) { float ms = 0.f; if (hipEventElapsedTime(&ms, clock.ev[k], clock.ev[k + 1]) == hipSuccess) t_ggp_grad_ms[k] += ms; }
     IBO_TRY(rc);
     const double *r = ws.pin;
     for (int i = 0; i < gs.nh; i++) grad_host[i] = r[i];
@@ -471,7 +459,5 @@ extern "C" int ibo_ggp_nlml_grad(int device, int ktype, int N, int D, const doub
 
 extern "C" int ibo_ggp_grad_stage_ms(double *ms, int reset)
 {
-    if (ms) memcpy(ms, t_ggp_grad_ms, sizeof(t_ggp_grad_ms));
-    if (reset) memset(t_ggp_grad_ms, 0, sizeof(t_ggp_grad_ms));
-    return IBO_OK;
+    return read_stage_sums(t_ggp_grad_ms, IBO_GGP_GRAD_STAGES, ms, reset);
 }

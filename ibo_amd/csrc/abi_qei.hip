@@ -223,7 +223,5 @@ extern "C" int ibo_qei_direct_max(ibo_gp_t *g, int npend, const double *pend_hos
 
 extern "C" int ibo_qei_stage_ms(double *ms, int reset)
 {
-    if (ms) memcpy(ms, t_qei_ms, sizeof(t_qei_ms));
-    if (reset) memset(t_qei_ms, 0, sizeof(t_qei_ms));
-    return IBO_OK;
+    return read_stage_sums(t_qei_ms, IBO_QEI_STAGES, ms, reset);
 }

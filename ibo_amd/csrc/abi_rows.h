@@ -1,6 +1,6 @@
 // abi_rows.h -- the row pipeline of the acquisitions built on kg.hip's row kernel (abi_kg.hip, abi_qei.hip, abi_gradobs.hip): a chunk of candidates goes
 // through K*, V^T = K* W^T and the row kernel, then the unit's own tail (its cross launch and its last kernel).  The ONE copy of the chunk,
-// the chunk length, the scratch, the stage clock, the host batch and the device sweep -- abi_rows.hip.
+// the chunk length, the scratch, the stages' marks (StageClock: abi_eval.h), the host batch and the device sweep -- abi_rows.hip.
 #pragma once
 #include "abi_eval.h"
 #include "cov.h"
@@ -9,17 +9,6 @@
 // what ibo_kg_stage_ms and ibo_qei_stage_ms index alike: the unit's resident state, then the five stages of a chunk
 enum { ST_STATE = 0, ST_KSTAR, ST_TRI, ST_ROWS, ST_CROSS, ST_TAIL, ROW_STAGES };
 static_assert(IBO_KG_STAGES == ROW_STAGES && IBO_QEI_STAGES == ROW_STAGES, "one stage layout");
-
-// HIP events around the stages of one entry call; everything is a no-op unless the unit's timing option was set when the call began
-struct StageClock {
-    hipStream_t s = nullptr;
-    double *ms = nullptr;                            // the unit's thread-local sums, ROW_STAGES of them
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool on = false;
-    ~StageClock() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    int mark(int k) { if (on) HIP_TRY(hipEventRecord(ev[k], s)); return IBO_OK; }
-    int account(int k0, int k1, int stage);          // after a synchronisation: the time between marks k0 and k1 goes to stage `stage`
-};
 
 // the stages after the row kernel: the cross launch, mark(4), the last kernel into out, mark(5)
 typedef std::function<int(int m, int mp, const double *cand, double *out)> rows_tail_t;

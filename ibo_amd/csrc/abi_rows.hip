@@ -3,15 +3,6 @@
 // value is the same bits from a sweep, a host batch and a DIRECT batch, whatever the chunk.
 #include "abi_rows.h"
 
-int StageClock::account(int k0, int k1, int stage)
-{
-    if (!on) return IBO_OK;
-    float t = 0.f;
-    HIP_TRY(hipEventElapsedTime(&t, ev[k0], ev[k1]));
-    ms[stage] += t;
-    return IBO_OK;
-}
-
 KgRowsArgs rows_args(const ibo_gp *g, const double *Kt, const double *Vt, const double *Q, int m, double clamp_lo)
 {
     KgRowsArgs r;
@@ -34,9 +25,7 @@ static int64_t chunk_length(int opt, int Npad, size_t cross_width)
 int RowPipeline::begin(ibo_gp *gp, double clamp, int chunk_opt, size_t cross_width, size_t ld, bool q_kept, bool timing, double *ms)
 {
     g = gp; clamp_lo = clamp; ldx = ld; keep_q = q_kept;
-    clock.s = g->stream; clock.ms = ms; clock.on = timing;
-    if (timing)
-        for (hipEvent_t &e : clock.ev) HIP_TRY(hipEventCreate(&e));
+    IBO_TRY(clock.make(g->stream, ms, timing));
     mc = chunk_length(chunk_opt, g->Npad, cross_width);
     return IBO_OK;
 }

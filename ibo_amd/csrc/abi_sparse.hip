@@ -37,6 +37,7 @@ struct ibo_sgp {
     double noise = 0.0, jitter = 0.0, maxY = 0.0, ll = 0.0, tt = 0.0;
     double logdet_u = 0.0, logdet_a = 0.0, wb2 = 0.0;      // 2 sum log L_ii of both factors; |W_A b|^2
     DevBuf<double> Gp;                       // (mp + 64)^2
+    void release() { Gp.release(); }
     double *pin = nullptr; size_t pin_cap = 0;
 };
 
@@ -144,25 +145,13 @@ int sgp_refactor(ibo_sgp *h, int *info)
     if (rc == IBO_ERR_NOT_PD) return fail(IBO_ERR_NOT_PD, "A = K~uu + G is not positive definite (pivot %d)", info ? *info : -1);
     IBO_TRY(rc);
     IBO_TRY(clock.stop(sa, &t_sgp_ms[SGP_ST_FACTOR]));
-    // |W_A b|^2 from launch_alpha's first product (fit_end left W_A b at the head of the frame's scratch)
+    // |W_A b|^2 from launch_alpha's first product (fit_alpha left W_A b at the head of the frame's scratch)
     std::vector<double> wb((size_t)m);
     HIP_TRY(hipMemcpy(wb.data(), ga->tmp.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost));
     double s = 0.0;
     for (int i = 0; i < m; i++) s += wb[i] * wb[i];
     h->wb2 = s;
     return sgp_logdet(ga, &h->logdet_a);
-}
-
-// What the evaluating entries check alike: the device first, the arguments, the handle's state.
-int sgp_check(ibo_sgp *h, bool ptrs_ok, int64_t M, int acq, int erf_mode, bool none_ok)
-{
-    IBO_TRY(use_device(h ? h->device : 0));
-    if (!h || !ptrs_ok) return fail(IBO_ERR_ARG, "NULL argument");
-    if (M < 1) return fail(IBO_ERR_ARG, "M=%lld", (long long)M);
-    if (acq < 0 || acq > (none_ok ? IBO_ACQ_NONE : IBO_ACQ_UCB)) return fail(IBO_ERR_ARG, "unknown acquisition %d", acq);
-    if (erf_mode != IBO_ERF_LIBM && erf_mode != IBO_ERF_NR) return fail(IBO_ERR_ARG, "unknown erf flavour %d", erf_mode);
-    if (!h->fitted) return fail(IBO_ERR_STATE, "sparse model before a successful fit");
-    return IBO_OK;
 }
 
 struct SgpCall { int acq, erf_mode; double parm, clamp_lo, ymax; };
@@ -220,7 +209,7 @@ extern "C" int ibo_sgp_destroy(ibo_sgp_t *h)
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
     g_pool_quiet = true;
-    h->Gp.release();
+    h->release();
     g_pool_quiet = false;
     if (h->pin) (void)hipHostFree(h->pin);
     const int r1 = ibo_gp_destroy(h->gu), r2 = ibo_gp_destroy(h->ga);
@@ -286,7 +275,7 @@ extern "C" int ibo_sgp_add(ibo_sgp_t *h, int64_t n, const double *X, const doubl
 extern "C" int ibo_sgp_acq_batch(ibo_sgp_t *h, int64_t M, const double *Q_host, int acq, double parm, int erf_mode,
                                  double clamp_lo, double ymax, double *mu_host, double *s2_host, double *acq_host)
 {
-    IBO_TRY(sgp_check(h, Q_host != nullptr, M, acq, erf_mode, true));
+    IBO_TRY(wrapped_check(h, "sparse", Q_host != nullptr, M, acq, erf_mode, true));
     if (!mu_host && !s2_host && !acq_host) return fail(IBO_ERR_ARG, "every output is NULL");
     const SgpCall c = {acq, erf_mode, parm, clamp_lo, ymax};
     return sgp_eval_host(h, c, M, Q_host, mu_host, s2_host, acq_host);
@@ -296,7 +285,7 @@ extern "C" int ibo_sgp_acq_sweep(ibo_sgp_t *h, int64_t M, const double *cand_dev
                                  int n_excl, const double *excl_host, double excl_radius, int64_t index_base,
                                  double *mu_dev, double *s2_dev, double *acq_dev, double *best_val, int64_t *best_idx)
 {
-    IBO_TRY(sgp_check(h, cand_dev != nullptr, M, acq, erf_mode, true));
+    IBO_TRY(wrapped_check(h, "sparse", cand_dev != nullptr, M, acq, erf_mode, true));
     if (!mu_dev && !s2_dev && !acq_dev && !best_val && !best_idx) return fail(IBO_ERR_ARG, "every output is NULL");
     const SgpCall c = {acq, erf_mode, parm, clamp_lo, ymax};
     MomentsPipeline p;
@@ -309,7 +298,7 @@ extern "C" int ibo_sgp_direct_max(ibo_sgp_t *h, int D, const double *lb, const d
                                   double clamp_lo, int maxiter, int maxtime, int maxsample, int compat,
                                   double *opt, double *optx, int64_t *nsamples)
 {
-    IBO_TRY(sgp_check(h, lb && ub, 1, acq, erf_mode, false));
+    IBO_TRY(wrapped_check(h, "sparse", lb && ub, 1, acq, erf_mode, false));
     if (!opt && !optx && !nsamples) return fail(IBO_ERR_ARG, "every output is NULL");
     if (D != h->D) return fail(IBO_ERR_ARG, "bounds have %d dimensions, the model has %d", D, h->D);
     const SgpCall c = {acq, erf_mode, parm, clamp_lo, NAN};
@@ -377,9 +366,7 @@ extern "C" int ibo_sgp_get(ibo_sgp_t *h, int what, double *out)
 
 extern "C" int ibo_sgp_stage_ms(double *ms, int reset)
 {
-    if (ms) memcpy(ms, t_sgp_ms, sizeof(t_sgp_ms));
-    if (reset) memset(t_sgp_ms, 0, sizeof(t_sgp_ms));
-    return IBO_OK;
+    return read_stage_sums(t_sgp_ms, IBO_SGP_STAGES, ms, reset);
 }
 
 // ------------------------------------------------------------------------ the marginal likelihood's gradient
@@ -580,7 +567,5 @@ extern "C" int ibo_sgp_nlml_grad(int device, int ktype, int D, const double *hyp
 
 extern "C" int ibo_sgp_grad_stage_ms(double *ms, int reset)
 {
-    if (ms) memcpy(ms, t_sgp_grad_ms, sizeof(t_sgp_grad_ms));
-    if (reset) memset(t_sgp_grad_ms, 0, sizeof(t_sgp_grad_ms));
-    return IBO_OK;
+    return read_stage_sums(t_sgp_grad_ms, IBO_SGP_GRAD_STAGES, ms, reset);
 }
