@@ -36,10 +36,31 @@ std::atomic<int> g_nlml_groups{2};    // IBO_NLML_GROUPS=1..4 (env): a batch of 
 // if unspecified-moment, change); the per-device workspaces of ibo_nlml_grid / ibo_nlml_grad and ibo_trim are serialised by
 // g_dev_mu (the exp table has its own lock, held only while it is created); handles are independent of each other (own stream,
 // events, buffers) -- two threads may drive two handles on one device at once.  ONE handle is for one thread at a time.
+std::atomic<int> g_alloc_fill{-1};     // ibo_set_option("alloc_fill", -1 / 0..255): the byte every newly obtained buffer is filled with (abi_internal.h); -1: off
 std::mutex g_dev_mu[16];
 std::atomic<size_t> g_pool_limit{(size_t)2 << 30};
 static std::atomic<long long> g_arena_mb{1024};                  // ibo_set_option("arena_mb", n) / env IBO_ARENA_MB: MiB per slab of the buffer arena (0: none)
     // ibo_set_option("pool_limit_mb", n) / env IBO_POOL_LIMIT_MB
+
+int alloc_fill_device(void *p, size_t bytes)
+{
+    const int v = g_alloc_fill.load(std::memory_order_relaxed);
+    if (v < 0 || !p || !bytes) return IBO_OK;
+    HIP_TRY(hipMemset(p, v, bytes));
+    HIP_TRY(hipDeviceSynchronize());
+    return IBO_OK;
+}
+void alloc_fill_host(void *p, size_t bytes)
+{
+    const int v = g_alloc_fill.load(std::memory_order_relaxed);
+    if (v >= 0 && p && bytes) memset(p, v, bytes);
+}
+// comm.hip's buffers (it shares no header with the other units): a device block and its pinned mirror
+int ibo_internal_alloc_fill(void *dev, void *host, size_t bytes)
+{
+    alloc_fill_host(host, bytes);
+    return alloc_fill_device(dev, bytes);
+}
 
 int use_device(int device)
 {
@@ -361,6 +382,7 @@ extern "C" int ibo_set_option(const char *key, int value)
     if (!strcmp(key, "ggp_timing")) { g_ggp_timing = value; return IBO_OK; }
     if (!strcmp(key, "sgp_chunk")) { if (value < 0) return fail(IBO_ERR_ARG, "sgp_chunk < 0"); g_sgp_chunk = value; return IBO_OK; }
     if (!strcmp(key, "sgp_timing")) { g_sgp_timing = value; return IBO_OK; }
+    if (!strcmp(key, "alloc_fill")) { if (value < -1 || value > 255) return fail(IBO_ERR_ARG, "alloc_fill outside -1 .. 255"); g_alloc_fill = value; return IBO_OK; }
     if (!strcmp(key, "arena_mb")) { if (value < 0) return fail(IBO_ERR_ARG, "arena_mb < 0"); g_arena_mb = value; return IBO_OK; }
     if (!strcmp(key, "pool_limit_mb")) { if (value < 0) return fail(IBO_ERR_ARG, "pool_limit_mb < 0"); g_pool_limit = (size_t)value << 20; return IBO_OK; }
     return fail(IBO_ERR_ARG, "unknown option");
@@ -409,6 +431,7 @@ extern "C" int ibo_dev_alloc(int device, size_t bytes, void **dev_ptr)
     if (!dev_ptr) return fail(IBO_ERR_ARG, "dev_ptr is NULL");
     IBO_TRY(use_device(device));
     HIP_TRY(hipMalloc(dev_ptr, bytes ? bytes : 8));
+    IBO_TRY(alloc_fill_device(*dev_ptr, bytes ? bytes : 8));
     std::lock_guard<std::mutex> lk(g_alloc_mu);
     g_allocs.push_back({(char *)*dev_ptr, bytes ? bytes : 8, device, ++g_gen_counter});
     return IBO_OK;
@@ -471,6 +494,7 @@ extern "C" int ibo_gp_create(int device, ibo_gp_t **out)
         g->stream = x.stream; g->ev0 = x.ev0; g->ev1 = x.ev1; g->fit0 = x.fit0; g->fit1 = x.fit1;
         g->pin = x.pin; g->pin_cap = x.pin_cap; g->done_flag = x.done_flag;
         if (g->done_flag) *g->done_flag = 0;
+        alloc_fill_host(g->pin, g->pin_cap * sizeof(double));
         *out = g;
         return IBO_OK;
     }
@@ -523,6 +547,7 @@ int ensure_pinned(ibo_gp *g, size_t need)
     size_t cap = need < 4096 ? 4096 : (need < ((size_t)1 << 20) ? need * 2 : need);
     HIP_TRY(hipHostMalloc((void **)&g->pin, cap * sizeof(double), hipHostMallocDefault));
     g->pin_cap = cap;
+    alloc_fill_host(g->pin, cap * sizeof(double));
     return IBO_OK;
 }
 

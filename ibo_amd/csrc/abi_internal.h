@@ -79,6 +79,12 @@ void pool_put(void *p, size_t bytes);
 void pool_trim(int dev);
 void pool_warm(int dev);
 extern thread_local bool g_pool_quiet;       // the caller has synchronised the device already (ibo_gp_destroy: once for all its buffers)
+// ibo_set_option("alloc_fill", v), a test hook: -1 off; 0 .. 255: every block DevBuf::ensure or ibo_dev_alloc obtains is filled with that byte
+// and the device synchronised before it is handed out, pinned staging is filled on the host.  A new buffer's content is undefined: no result
+// may depend on it (tests/test_gpu_alloc_fill.py)
+extern std::atomic<int> g_alloc_fill;
+int alloc_fill_device(void *p, size_t bytes);      // (only while the hook is on) hipMemset + hipDeviceSynchronize
+void alloc_fill_host(void *p, size_t bytes);       // memset while the hook is on, nothing otherwise
 
 template <typename T>
 struct DevBuf {
@@ -105,6 +111,7 @@ struct DevBuf {
         p = (T *)q;
         cap = got / sizeof(T);
         bytes = got;
+        if (g_alloc_fill.load(std::memory_order_relaxed) >= 0) return alloc_fill_device(q, got);
         return IBO_OK;
     }
     void release() { if (p) pool_put(p, bytes); p = nullptr; cap = 0; bytes = 0; }

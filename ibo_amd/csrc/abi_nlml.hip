@@ -233,7 +233,10 @@ static int grad_frame(GradWorkspace &ws, int Np, FactorRoute *route, FactorBufs 
     // call cost as much as the arithmetic); ibo_trim() releases it
     IBO_TRY(ws.dL.ensure(nn)); IBO_TRY(ws.dW.ensure(nn)); IBO_TRY(ws.dT.ensure(nn)); IBO_TRY(ws.dKi.ensure(nn)); IBO_TRY(ws.d64.ensure(diag64_size(Np)));
     IBO_TRY(ws.dal.ensure(Np)); IBO_TRY(ws.da1.ensure(Np)); IBO_TRY(ws.tmp.ensure(alpha_scratch(Np))); IBO_TRY(ws.dinfo.ensure(1));
-    if (!ws.pin) HIP_TRY(hipHostMalloc((void **)&ws.pin, sizeof(double) * kGradPin, hipHostMallocDefault));
+    if (!ws.pin) {
+        HIP_TRY(hipHostMalloc((void **)&ws.pin, sizeof(double) * kGradPin, hipHostMallocDefault));
+        alloc_fill_host(ws.pin, sizeof(double) * kGradPin);
+    }
     IBO_TRY(fit_frame(Np, ws.dT.p, ws.dL.p, ws.dW.p, ws.dKi.p, nullptr, nullptr, ws.d64.p, ws.dinfo.p, ws.tall, ws.Pk2, route, b));
     if (!ws.t0) { HIP_TRY(hipEventCreate(&ws.t0)); HIP_TRY(hipEventCreate(&ws.t1)); }
     return IBO_OK;

@@ -50,6 +50,7 @@ int sgp_pinned(ibo_sgp *h, size_t need)
     h->pin = nullptr; h->pin_cap = 0;
     HIP_TRY(hipHostMalloc((void **)&h->pin, sizeof(double) * need, hipHostMallocDefault));
     h->pin_cap = need;
+    alloc_fill_host(h->pin, sizeof(double) * need);
     return IBO_OK;
 }
 

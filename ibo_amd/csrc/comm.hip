@@ -42,6 +42,7 @@ static struct {
 } R;
 
 void ibo_internal_set_error(const char *msg);     // abi.hip: the one buffer behind ibo_last_error()
+int ibo_internal_alloc_fill(void *dev, void *host, size_t bytes);     // abi_core.hip: ibo_set_option("alloc_fill") for the two buffers below
 static int cfail(int code, const char *msg, int rc = 0)
 {
     char c_err[256];
@@ -87,6 +88,7 @@ static int comm_reserve(ibo_comm *c, size_t n)
     if (hipMalloc((void **)&c->dbuf, cap * sizeof(double)) != hipSuccess) return cfail(IBO_ERR_HIP, "hipMalloc failed");
     if (hipHostMalloc((void **)&c->hpin, cap * sizeof(double), hipHostMallocDefault) != hipSuccess) return cfail(IBO_ERR_HIP, "hipHostMalloc failed");
     c->cap = cap;
+    if (ibo_internal_alloc_fill(c->dbuf, c->hpin, cap * sizeof(double)) != IBO_OK) return IBO_ERR_HIP;
     return IBO_OK;
 }
 

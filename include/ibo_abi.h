@@ -121,7 +121,7 @@ int         ibo_selftest_mfma(int device, double *max_abs_err);
  * gradients.  DIRECT's small batches and the copies are not event-timed and not in it.  bench.py reports it as gpu_kernel_s_total
  * so that a line can be related to an outside observer's busy-GPU samples. */
 int         ibo_gpu_time_ms(int device, double *ms);
-/* The twenty-six option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
+/* The twenty-seven option keys (everything else is decided by the data: sizes, dimensions, what the caller asks for).
  * Functional:  "legacy_exact" 1/0 -- acqmaxGP in libego's operation order (default) or on the MFMA sweep kernels (see acqmaxGP);
  *   "nlml_batch" B -- matrices per batched factorisation in ibo_nlml_grid (0: as many as 12 GB hold; the values do not depend on it);
  *   "pool_limit_mb" n -- the per-device free list of recycled buffers (ibo_trim);
@@ -145,6 +145,12 @@ int         ibo_gpu_time_ms(int device, double *ms);
  *   rounded up to 256, 0: by bytes -- identical bits);  "sgp_chunk" n (observations and candidates per chunk of the ibo_sgp_* entries,
  *   rounded up to 256, 0: by bytes -- see those entries for what stays bit-identical).
  * Diagnostic:  "sgp_timing" 1/0 (see ibo_sgp_stage_ms);  "ggp_timing" 1/0 (see ibo_ggp_stage_ms);  "kg_timing" 1/0 (see ibo_kg_stage_ms);  "qei_timing" 1/0 (see ibo_qei_stage_ms);  "ehvi_timing" 1/0 (see ibo_ehvi_scan_ms);  "mes_timing" 1/0 (see ibo_mes_scan_ms).
+ * Test hook:  "alloc_fill" -1 (off, the default) / 0 .. 255 (anything else: IBO_ERR_ARG) -- while it is on, every device buffer the library
+ *   newly obtains (from its arena, its free list or the device; a buffer that already has the capacity is live and left alone) and every
+ *   array of ibo_dev_alloc is filled with that byte and the device synchronised before it is handed out; the pinned staging of a handle is
+ *   filled on the host when the handle takes it over and when it grows.  A new buffer's content is undefined, and no result, status or info
+ *   word may depend on it: 0xFF makes every unwritten double a NaN and every int -1, 0x7F a finite 1.4e306 and 0x7F7F7F7F
+ *   (tests/test_gpu_alloc_fill.py).  Off, it costs one relaxed atomic load per allocation and changes no kernel, launch or allocation order.
  * Env: IBO_SWEEP_IMPL=gemv|mfma, IBO_DOT_FORM, IBO_POOL_LIMIT_MB, IBO_HOST_THREADS (the legacy symbol's host crew), IBO_DEVICE (legacy symbols),
  *   IBO_NLML_GROUPS=1..4 (sub-batches of an ibo_nlml_grid batch, each on its own stream; 2; the values do not depend on it).
  * Threading (the reference's library keeps its whole model in process-wide statics, cpp/optimizeGP.cpp:36-55,240-259, and is not
