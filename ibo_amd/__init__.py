@@ -33,6 +33,7 @@ def install_as_ego():
     import importlib
     names = ["", ".gaussianprocess", ".gaussianprocess.kernel", ".gaussianprocess.prior",
              ".gaussianprocess.trainhyper", ".acquisition", ".acquisition.gallery", ".acquisition.constrained", ".acquisition.multiobjective", ".utils",
+             ".gaussianprocess.hypersample", ".gaussianprocess.ensemble", ".acquisition.integrated",      # (additions: the reference has no such paths)
              ".utils.optimize", ".utils.latinhypercube", ".utils.testfunctions"]
     for n in names:
         sys.modules["ego" + n] = importlib.import_module("ibo_amd" + n)

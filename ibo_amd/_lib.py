@@ -10,6 +10,9 @@ the header and to the library), the ibo_qei_* entries of the parallel expected i
 two-objective hypervolume improvement, the ibo_ggp_* entries of a GP observed with gradients, the ibo_mes_* entries of
 max-value entropy search, the ibo_sgp_* entries of the sparse GP with its likelihood gradient and ibo_ggp_nlml_grad, the
 gradient-observation model's likelihood with its gradient, among them.
+
+The five ibo_iacq_* entries of include/ibo_abi_ensemble.h -- acquisitions integrated over an ensemble of handles -- are bound the same
+way and listed in EXPORTED_ENSEMBLE (tests/test_marginal_reference.py holds that list to its header and to the library).
 """
 import ctypes
 import os
@@ -216,6 +219,19 @@ EXPORTED = ["ibo_abi_version", "ibo_last_error", "ibo_device_count", "ibo_device
             "ibo_sgp_nlml", "ibo_sgp_get", "ibo_sgp_stage_ms", "ibo_sgp_nlml_grad", "ibo_sgp_grad_stage_ms", "ibo_direct_host", "ibo_nlml_grid", "ibo_nlml_grad", "ibo_gp_loo", "ibo_loo_grad",
             "ibo_comm_get_unique_id", "ibo_comm_init", "ibo_comm_destroy", "ibo_comm_count", "ibo_comm_argmax", "ibo_comm_allreduce_sum", "ibo_acq_sweep_exchange", "ibo_comm_barrier",
             "acqmaxGP", "direct", "logCDFs"]
+
+# include/ibo_abi_ensemble.h: the integrated acquisitions over an ensemble of handles.  A list of its own, as the header is a file of its
+# own: EXPORTED is held to ibo_abi.h symbol for symbol.  A library without these fails at import like one without any other entry.
+_IACQ = (POINTER(c_void_p), c_int, _DP)                                   # gp, S, w of the ibo_iacq_* entries
+_IACQ_SPEC = (c_int, c_double, c_int, c_double, c_double)                  # acq, parm, erf_mode, clamp_lo, ymax
+_sig("ibo_iacq_sweep", c_int, *(_IACQ + (c_int64, c_void_p) + _IACQ_SPEC + (c_int, _DP, c_double, c_int64, c_void_p, c_void_p, c_void_p,
+                                                                          _DP, POINTER(c_int64))))
+_sig("ibo_iacq_batch", c_int, *(_IACQ + (c_int64, _DP) + _IACQ_SPEC + (_DP, _DP, _DP)))
+_sig("ibo_iacq_grad_batch", c_int, *(_IACQ + (c_int64, _DP) + _IACQ_SPEC + (_DP, _DP)))
+_sig("ibo_iacq_direct_max", c_int, *(_IACQ + (c_int, _DP, _DP) + _IACQ_SPEC + (c_int, c_int, c_int, c_int, _DP, _DP, POINTER(c_int64))))
+_sig("ibo_iacq_stage_ms", c_int, _DP, c_int)
+
+EXPORTED_ENSEMBLE = ["ibo_iacq_sweep", "ibo_iacq_batch", "ibo_iacq_grad_batch", "ibo_iacq_direct_max", "ibo_iacq_stage_ms"]
 
 
 def check(rc):

@@ -22,6 +22,8 @@ Posterior draws as functions -- Thompson sampling over whole candidate arrays (p
 with .gradient / .negf_grad (ibo_paths_grad_batch), .maximize(polish=True) and .maxima, every path's maximum by a lock-step ascent.
 Max-value entropy search against samples of the maximum's value, exact (path maxima) or from a Gumbel fit that also serves a
 preference GP (entropy.py): MaxValueEntropy, maxValueSamples, sweepMES, maximizeMES, gumbelFit.
+Acquisitions integrated over samples of the hyper-parameters, on a GaussianProcessEnsemble (integrated.py): IntegratedEI, IntegratedPI,
+IntegratedUCB, sweepIntegrated, maximizeIntegratedEI, maximizeIntegratedPI, maximizeIntegratedUCB.
 
 The default maximize* path is the reference's cdirectGP -> acqmaxGP -> DIRECT
 (ego/acquisition/__init__.py:307-447, cpp/optimizeGP.cpp:262-349) with the tree
@@ -327,3 +329,5 @@ from .knowledge import KnowledgeGradient, sweepKG, maximizeKG, referenceSet     
 from .batch import baseSamples, ParallelEI, sweepQEI, maximizeQEI, jointQEI, proposeBatch      # noqa: E402,F401
 from .pathwise import PosteriorPaths, spectralDraws                                  # noqa: E402,F401
 from .entropy import MaxValueEntropy, maxValueSamples, sweepMES, maximizeMES, gumbelFit      # noqa: E402,F401
+from .integrated import (IntegratedEI, IntegratedPI, IntegratedUCB, sweepIntegrated, maximizeIntegratedEI,      # noqa: E402,F401
+                         maximizeIntegratedPI, maximizeIntegratedUCB)

@@ -141,13 +141,13 @@ static void exec_sets_prewarm(int dev);
 // one kernel of every translation unit (each defines its ibo_touch_*): their code objects are loaded now, not in the middle of the first
 // call that needs them
 void ibo_touch_small2(); void ibo_touch_sweep(); void ibo_touch_sweep2(); void ibo_touch_linalg(); void ibo_touch_assemble(); void ibo_touch_update3();
-void ibo_touch_legacy(); void ibo_touch_comm(); void ibo_touch_cov(); void ibo_touch_cacq(); void ibo_touch_kg(); void ibo_touch_paths(); void ibo_touch_qei(); void ibo_touch_ehvi(); void ibo_touch_gradobs(); void ibo_touch_mes(); void ibo_touch_sparse(); void ibo_touch_sparse_grad();
+void ibo_touch_legacy(); void ibo_touch_comm(); void ibo_touch_cov(); void ibo_touch_cacq(); void ibo_touch_kg(); void ibo_touch_paths(); void ibo_touch_qei(); void ibo_touch_ehvi(); void ibo_touch_gradobs(); void ibo_touch_mes(); void ibo_touch_sparse(); void ibo_touch_sparse_grad(); void ibo_touch_marg();
 void ibo_touch_s2fam_FAM_SE_0(); void ibo_touch_s2fam_FAM_SE_1(); void ibo_touch_s2fam_FAM_M3_0(); void ibo_touch_s2fam_FAM_M3_1();
 void ibo_touch_s2fam_FAM_M5_0(); void ibo_touch_s2fam_FAM_M5_1();
 static void load_code_objects()
 {
     ibo_touch_small2(); ibo_touch_sweep(); ibo_touch_sweep2(); ibo_touch_linalg(); ibo_touch_assemble(); ibo_touch_update3();
-    ibo_touch_legacy(); ibo_touch_comm(); ibo_touch_cov(); ibo_touch_cacq(); ibo_touch_kg(); ibo_touch_paths(); ibo_touch_qei(); ibo_touch_ehvi(); ibo_touch_gradobs(); ibo_touch_mes(); ibo_touch_sparse(); ibo_touch_sparse_grad();
+    ibo_touch_legacy(); ibo_touch_comm(); ibo_touch_cov(); ibo_touch_cacq(); ibo_touch_kg(); ibo_touch_paths(); ibo_touch_qei(); ibo_touch_ehvi(); ibo_touch_gradobs(); ibo_touch_mes(); ibo_touch_sparse(); ibo_touch_sparse_grad(); ibo_touch_marg();
     ibo_touch_s2fam_FAM_SE_0(); ibo_touch_s2fam_FAM_SE_1(); ibo_touch_s2fam_FAM_M3_0(); ibo_touch_s2fam_FAM_M3_1();
     ibo_touch_s2fam_FAM_M5_0(); ibo_touch_s2fam_FAM_M5_1();
     (void)hipGetLastError();
@@ -374,6 +374,8 @@ extern "C" int ibo_set_option(const char *key, int value)
     if (!strcmp(key, "ehvi_timing")) { g_ehvi_timing = value; return IBO_OK; }
     if (!strcmp(key, "mes_chunk")) { if (value < 0) return fail(IBO_ERR_ARG, "mes_chunk < 0"); g_mes_chunk = value; return IBO_OK; }
     if (!strcmp(key, "mes_timing")) { g_mes_timing = value; return IBO_OK; }
+    if (!strcmp(key, "iacq_chunk")) { if (value < 0) return fail(IBO_ERR_ARG, "iacq_chunk < 0"); g_iacq_chunk = value; return IBO_OK; }
+    if (!strcmp(key, "iacq_timing")) { g_iacq_timing = value; return IBO_OK; }
     if (!strcmp(key, "paths_chunk")) { if (value < 0) return fail(IBO_ERR_ARG, "paths_chunk < 0"); g_paths_chunk = value; return IBO_OK; }
     if (!strcmp(key, "kg_timing")) { g_kg_timing = value; return IBO_OK; }
     if (!strcmp(key, "qei_chunk")) { if (value < 0) return fail(IBO_ERR_ARG, "qei_chunk < 0"); g_qei_chunk = value; return IBO_OK; }

@@ -9,15 +9,16 @@
 //   abi_cacq.hip    the constrained acquisition (ibo_cacq_*)
 //   abi_ehvi.hip    the two-objective expected hypervolume improvement (ibo_ehvi_*)
 //   abi_mes.hip     max-value entropy search and the max-value cdf (ibo_mes_*)
+//   abi_marg.hip    acquisitions integrated over an ensemble of models (ibo_iacq_*, include/ibo_abi_ensemble.h)
 //   abi_kg.hip      the knowledge gradient (ibo_kg_*)
 //   abi_paths.hip   pathwise posterior draws (ibo_paths_*)
 //   abi_qei.hip     the Monte-Carlo parallel expected improvement (ibo_qei_*)
 //   abi_gradobs.hip the GP observed with gradients (ibo_ggp_*): its own handle around a P-row frame, the row pipeline with its own K*
 //   abi_sparse.hip  the sparse GP on inducing points (ibo_sgp_*): its own handle around two m-row frames and the kept Gram matrix
 //   abi_rows.hip    the row pipeline of abi_kg, abi_qei and abi_gradobs: chunk, scratch, stage clock, host batch, device sweep (abi_rows.h)
-//   abi_moments.hip the moments pipeline of abi_cacq, abi_ehvi, abi_mes and abi_sparse: the plain sweeps of a chunk into scratch, the
+//   abi_moments.hip the moments pipeline of abi_cacq, abi_ehvi, abi_mes, abi_marg and abi_sparse: the plain sweeps of a chunk into scratch, the
 //                   stream rule, the padded tail, host batch, device sweep (abi_moments.h)
-//                   (these twelve are the evaluation units: what they share among themselves is in abi_eval.h)
+//                   (these thirteen are the evaluation units: what they share among themselves is in abi_eval.h)
 //   abi_nlml.hip    marginal-likelihood grid and the three gradients (one prepare step, one rule for resident data), ibo_trim
 //   abi_legacy.hip  libego's symbols (acqmaxGP, direct, logCDFs) and ibo_direct_host
 // A struct that owns DevBufs has a release() directly under its member list, which ibo_trim and the destroy entries call.
@@ -62,6 +63,7 @@ extern std::atomic<int> g_host_pipeline, g_fused2_min_nb, g_gallery_prune, g_nlm
 extern std::atomic<int> g_cacq_chunk;                // abi_cacq.hip: candidates per chunk of ibo_cacq_sweep (0: by bytes)
 extern std::atomic<int> g_ehvi_chunk, g_ehvi_timing; // abi_ehvi.hip: candidates per chunk of the ibo_ehvi_* entries (0: by bytes); HIP events around the scan kernel
 extern std::atomic<int> g_mes_chunk, g_mes_timing;   // abi_mes.hip: candidates per chunk of the ibo_mes_* entries (0: by bytes); HIP events around the scan kernels
+extern std::atomic<int> g_iacq_chunk, g_iacq_timing; // abi_marg.hip: candidates per chunk of the ibo_iacq_* entries (0: by bytes); HIP events around a chunk's sweeps and its finish
 extern std::atomic<int> g_kg_chunk, g_kg_timing;     // abi_kg.hip: candidates per chunk (0: by bytes); per-stage HIP events
 extern std::atomic<int> g_qei_chunk, g_qei_timing;   // abi_qei.hip: candidates per chunk (0: by bytes); per-stage HIP events
 extern std::atomic<int> g_ggp_chunk, g_ggp_timing;   // abi_gradobs.hip: candidates per chunk of the ibo_ggp_* entries (0: by bytes); per-stage HIP events

@@ -7,7 +7,7 @@
 
 #include <functional>
 
-#define MOMENT_SLOTS (IBO_CACQ_MAX_CON + 1)
+#define MOMENT_SLOTS (IBO_CACQ_MAX_CON + 1 > IBO_MARG_MAX ? IBO_CACQ_MAX_CON + 1 : IBO_MARG_MAX)        // (the constrained call's models; an ensemble's members)
 #define MOMENT_OUTS 3
 
 // One model of the call.  The scratch holds the arrays the slots ask for in slot order, mu before s2, `stride` doubles apart; a slot

@@ -270,6 +270,8 @@ __device__ __forceinline__ double cacq_value_dev(const CacqSpec &c, MS ms, doubl
     return v;
 }
 
+#define IBO_MARG_MAX 32         // IBO_IACQ_MAX of ibo_abi_ensemble.h: the members of an integrated acquisition (marg.h)
+
 // ---- host-side launch API of the kernels (defined in linalg.hip / assemble.hip / update3.hip / sweep*.hip / small2.hip)
 #define IBO_SPLIT_PANEL 64      // rows per workgroup of the small-batch (SPLIT) sweep
 #define IBO_S2_TCAND 32         // candidates per workgroup of sweep2_kernel (sweep2.hip)

@@ -3,11 +3,13 @@ Gaussian-process models with the reference's API (ego/gaussianprocess/__init__.p
 on the MI355X backend.
 
     GaussianProcess(kernel, X=None, Y=None, prior=None, noise=.1, gnoise=1e-4, G=None)
-        .addData(X, Y, G=None)  .removeData(indices)  .posterior(x, getvar=True)  .posteriors(X)  .mu(x)  .negmu(x)
+        .addData(X, Y, G=None)  .removeData(indices)  .refit(X=None, Y=None)  .posterior(x, getvar=True)  .posteriors(X)  .mu(x)  .negmu(x)
         .getYfromX(qx)  .done(x)   attributes X, Y, R, L, noise, kernel, prior, ...
         with G=: .nlml()  .learn(nhyper=None, noise=False, gnoise=False, maxiter=30, bounds=None)   (the likelihood of values and slopes)
     PrefGaussianProcess(kernel, prefs=None, **kw)
         .addPreferences(prefs)  .addObservationPoint(x)   attributes preferences, C
+    GaussianProcessEnsemble(kernels, X, Y, noise=1e-3, weights=None, prior=None)      (ensemble.py: plain members under several theta)
+    sampleHyper(kernel, X, Y, ...)  sliceSample  LogNormalPrior  BoxPrior              (hypersample.py: samples of log theta)
 
 Everything numerical -- K(X,X), Cholesky, L^-1, posterior mean/variance -- runs
 in libibo_hip on the GPU; this file holds the bookkeeping the reference keeps
@@ -547,6 +549,32 @@ class GaussianProcess(object):
     def negmu(self, x):
         return -self.mu(x)
 
+    def refit(self, X=None, Y=None):
+        """factor the model again from scratch -- on its own data, or, with X (N, D) and Y (N,) given, on these INSTEAD (all of them, not
+        appended).  The factor then has the bits of a new model of the same data, kernel and noise, which addData's in-place extension
+        agrees with to rounding only (GaussianProcessEnsemble.addData is built on this).  A matrix that does not factor leaves the model
+        as it was, factored again on the data it had, and the error is passed on.  Models observed with gradients: NotImplementedError
+        (addData(X, Y, G) refits them as it is)."""
+        self._no_gradient("refit")
+        if (X is None) != (Y is None):
+            raise ValueError("refit takes X and Y together, or neither")
+        oldX, oldY = self.X, self.Y
+        if X is not None:
+            X = np.array(X, dtype=float, ndmin=2)
+            Y = np.array(Y, dtype=float, ndmin=1).flatten()
+            if len(Y) != len(X):
+                raise ValueError("%d values for %d points" % (len(Y), len(X)))
+            self.X, self.Y = X, Y
+        if len(self.X) == 0:
+            raise ValueError("model has no data")
+        try:
+            self._fit_device()
+        except Exception:
+            self.X, self.Y = oldX, oldY
+            if len(oldX):
+                self._fit_device()
+            raise
+
     EXTEND_MAX = 16          # more points than this in one addData call: a refit is cheaper than point-by-point rows
 
     def addData(self, X, Y, G=None):
@@ -951,6 +979,9 @@ class PrefGaussianProcess(GaussianProcess):
     def removeData(self, indices, _route=None):
         raise NotImplementedError("the preference GP's factor is that of R + C^-1 and its targets are a MAP: removing a point changes C")
 
+    def refit(self, X=None, Y=None):
+        raise NotImplementedError("the preference GP's factor is that of R + C^-1 and its targets are a MAP: addPreferences fits it")
+
     def addObservationPoint(self, X):
         """add a point to observe at, without its observation (:502-519)"""
         X = np.array(X, dtype=float, ndmin=2)
@@ -986,3 +1017,5 @@ class PrefGaussianProcess(GaussianProcess):
 
 
 from .sparse import SparseGaussianProcess, inducingPoints      # noqa: E402,F401
+from .ensemble import GaussianProcessEnsemble                   # noqa: E402,F401
+from .hypersample import sampleHyper, sliceSample, LogNormalPrior, BoxPrior      # noqa: E402,F401

@@ -6,7 +6,7 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "rXX"
 rows = []
 units = [("sweep2_fam", ["-DS2_FAM=FAM_%s" % fam, "-DS2_PIECE=%d" % pc]) for fam in ("SE", "M3", "M5") for pc in (0, 1)]
-units += [(f, []) for f in ("sweep2", "sweep", "small2", "grad", "cov", "cacq", "ehvi", "mes", "kg", "qei", "gradobs", "sparse", "sparse_grad", "paths", "loo", "downdate", "update3", "linalg", "assemble", "legacy", "comm", "abi_core", "abi_fit", "abi_pref", "abi_factor", "abi_sweep", "abi_batch", "abi_cacq", "abi_ehvi", "abi_mes", "abi_kg", "abi_qei", "abi_rows", "abi_moments", "abi_paths", "abi_nlml", "abi_legacy")]
+units += [(f, []) for f in ("sweep2", "sweep", "small2", "grad", "cov", "cacq", "ehvi", "mes", "marg", "kg", "qei", "gradobs", "sparse", "sparse_grad", "paths", "loo", "downdate", "update3", "linalg", "assemble", "legacy", "comm", "abi_core", "abi_fit", "abi_pref", "abi_factor", "abi_sweep", "abi_batch", "abi_cacq", "abi_ehvi", "abi_mes", "abi_marg", "abi_kg", "abi_qei", "abi_rows", "abi_moments", "abi_paths", "abi_nlml", "abi_legacy")]
 for f, defs in units:
     out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-Rpass-analysis=kernel-resource-usage"] + defs +
                          ["-c", os.path.join(root, "ibo_amd", "csrc", f + ".hip"), "-o", "/dev/null"], capture_output=True, text=True).stderr
